@@ -19,6 +19,14 @@ collective — the sum is element-wise).  Barrier + synchronize bracket the
 timed steps, the max over ranks is taken, and value = total gradient bytes
 aggregated by all ranks / time.
 
+A plain run (``bench.py --gpus N --steps K --warmup W``) sets up the inputs,
+warms up, times the K steps and prints the headline line (``value``,
+``ms_per_step``, the roofline of the timed launches); ``--dump-outputs DIR``
+also writes what the last timed step computed as ``.npy`` (dump_outputs).
+Everything below — the per-launch spread pass, the spot check against torch's
+fold, the fp16 run, configs 1, 3, 4 and 5, the PCIe probe, the exchange legs
+and the CPU baseline — runs only with ``--full``, after the timed steps.
+
 ``scaling`` (every N): BASELINE config 4 — the 8-way fp32 VGG-16 gradient set
 (553,430,176 B per worker) sharded over the N GPUs by the reference's
 reduce-scatter ownership (core_loops.cc:208-247): per-GPU fold time of the
@@ -61,6 +69,11 @@ LEAD_CYCLES = 2_000_000  # spin ahead of a timed block (~1 ms of GPU clock)
 GIB = float(1 << 30)
 WATCHDOG_EXIT = 3  # every rank's status when the N > 1 watchdog fires
 RCCL_EXIT = 4      # every rank's status when the communicator is not N ranks on N GPUs
+# --dump-outputs: bytes written over all ranks (under the 64 MB a dump may
+# take), the head and tail kept whole in a sampled dump, the sample's seed
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_EDGE_ELEMS = 1 << 20
+DUMP_SEED = 20240229
 METRIC = "GiB/s device-resident N-way gradient-bucket sum (fp32/fp16), 1/2/4/8 GPUs"
 # --dtype name -> (byteps DataType id, torch dtype name); ids: common.h:52-65 (+ bf16 = 11)
 DTYPES = {"f32": (0, "float32"), "f64": (1, "float64"), "f16": (2, "float16"),
@@ -97,6 +110,16 @@ def parse(argv=None):
     p.add_argument("--skew", type=int, default=-1,
                    help="arena: bytes between consecutive slots beyond the 64 KiB-rounded "
                         "bucket (default: prophet_amd.arena.DEFAULT_SKEW)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run everything else the line can carry: "
+                        "the per-launch spread pass, the check against torch's fold, the "
+                        "fp16 / config 1, 3, 4, 5 / PCIe / exchange legs and the CPU baseline "
+                        "(each still has its own --no-* switch); a plain run only sets up, "
+                        "warms up, times --steps steps and prints the headline line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (this rank's aggregate "
+                        "bucket) as DIR/<name>.npy, float32 or float64, at most 64 MB in "
+                        "all: whole when it fits, else a fixed seeded sample of its elements")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-scaling", action="store_true",
                    help="skip the config-4 (VGG-16 sharded) scaling object")
@@ -124,7 +147,10 @@ def parse(argv=None):
                         "fold, gloo for the barrier / max-over-ranks (RCCL refuses two ranks "
                         "on one GPU); the scatter and local-reduce legs move CUDA tensors "
                         "through gloo; the line is marked, not a measurement")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # --------------------------------------------------------------------------
@@ -395,6 +421,36 @@ def _left_fold_equal(out, srcs) -> bool:
     for s in srcs[1:]:
         ref.add_(s)
     return bool(torch.equal(ref.view(torch.int32), out.view(torch.int32)))
+
+
+def dump_outputs(dirname: str, dst, tdt, world: int, rank: int) -> str:
+    """--dump-outputs: what the last timed step left in this rank's output slot
+    (the aggregate a caller of byteps_reduce_sum_n receives), as
+    ``DIR/sum.npy`` (``DIR/sum_rank<r>.npy`` at N > 1).  float32, or float64
+    for the dtypes float32 cannot hold (f64, i32, i64).  An output within this
+    rank's share of DUMP_BUDGET_BYTES is written whole; a larger one as a
+    fixed sample in index order — its first and last DUMP_EDGE_ELEMS elements
+    and, between them, elements at indices drawn from a CPU generator seeded
+    with DUMP_SEED — so two builds run with the same arguments write arrays
+    that compare element for element.  Returns the file written."""
+    import numpy as np
+    import torch
+    out = dst.view(tdt)
+    wide = tdt in (torch.float64, torch.int32, torch.int64)
+    cap = DUMP_BUDGET_BYTES // max(1, world) // (8 if wide else 4)
+    n = out.numel()
+    if n > cap:
+        edge = min(DUMP_EDGE_ELEMS, cap // 4)
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(DUMP_SEED)
+        mid = torch.randint(edge, n - edge, (cap - 2 * edge,), generator=gen).sort().values
+        idx = torch.cat([torch.arange(edge), mid, torch.arange(n - edge, n)])
+        out = out[idx.to(out.device)]
+    arr = out.to(torch.float64 if wide else torch.float32).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, "sum.npy" if world == 1 else f"sum_rank{rank}.npy")
+    np.save(path, arr)
+    return path
 
 
 # --------------------------------------------------------------------------
@@ -1524,22 +1580,32 @@ def main(argv=None):
     wall = time.perf_counter() - t0
     t_step = wall / args.steps
     t_step, kern_ms = _max_over_ranks(dist, dev, [t_step, kern_ms])
-    # Spread of the per-launch time (median / min / max over blocks of
-    # back-to-back launches), a separate pass after the timed region; it ends
-    # on the same input set as the timed steps did.
-    n_blk, per_blk = 5, max(1, min(args.steps // 5, 10))
-    pl = sorted(clock.blocks(step, n_blk, per_blk,
-                             first=args.steps + args.warmup - n_blk * per_blk))
-    pl_med, pl_min, pl_max = _max_over_ranks(
-        dist, dev, [statistics.median(pl), pl[0], pl[-1]])
+    if args.dump_outputs:
+        # the output slot the last timed step (index --steps - 1) wrote
+        dump_outputs(args.dump_outputs, sets[(args.steps - 1) % len(sets)][0], tdt, world, rank)
+    blocks, ok = None, None
+    if args.full:
+        # Spread of the per-launch time (median / min / max over blocks of
+        # back-to-back launches), a separate pass after the timed region; it ends
+        # on the same input set as the timed steps did.
+        n_blk, per_blk = 5, max(1, min(args.steps // 5, 10))
+        pl = sorted(clock.blocks(step, n_blk, per_blk,
+                                 first=args.steps + args.warmup - n_blk * per_blk))
+        pl_med, pl_min, pl_max = _max_over_ranks(
+            dist, dev, [statistics.median(pl), pl[0], pl[-1]])
+        # per-launch average of each of n_blk blocks of per_blk back-to-back
+        # launches (max over ranks)
+        blocks = {"median": round(pl_med, 5), "min": round(pl_min, 5), "max": round(pl_max, 5),
+                  "blocks": n_blk, "launches_per_block": per_blk}
 
-    # Correctness spot check of the last set against torch's own left fold.
-    dst, srcs = sets[(args.steps + args.warmup - 1) % len(sets)]
-    chk = srcs[0].view(tdt)[: 1 << 20].clone()
-    for s in srcs[1:]:
-        chk.add_(s.view(tdt)[: 1 << 20])
-    ok = bool(torch.equal(chk.view(torch.uint8), dst[: chk.numel() * es])) if mode == 0 else None
-    ok = _all_true(dist, dev, ok) if ok is not None else None
+        # Correctness spot check of the last set against torch's own left fold.
+        dst, srcs = sets[(args.steps + args.warmup - 1) % len(sets)]
+        chk = srcs[0].view(tdt)[: 1 << 20].clone()
+        for s in srcs[1:]:
+            chk.add_(s.view(tdt)[: 1 << 20])
+        ok = bool(torch.equal(chk.view(torch.uint8), dst[: chk.numel() * es])) \
+            if mode == 0 else None
+        ok = _all_true(dist, dev, ok) if ok is not None else None
     del sets
 
     devices = [f"{local_rank}"]
@@ -1589,23 +1655,32 @@ def main(argv=None):
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
                      "traffic": traffic, "traffic_source": traffic_src,
                      "alg_bytes_per_launch": alg_bytes, "kernel_ms": round(kern_ms, 5),
-                     # per-launch average of each of n_blk blocks of per_blk
-                     # back-to-back launches, a separate pass (max over ranks)
-                     "kernel_ms_blocks": {"median": round(pl_med, 5), "min": round(pl_min, 5),
-                                          "max": round(pl_max, 5), "blocks": n_blk,
-                                          "launches_per_block": per_blk},
                      # also the read stream alone (N * B of the
                      # (N + 1) * B), against the same peak
                      "read_only_GBps": round(N * B / (kern_ms * 1e-3) / 1e9, 1),
                      "read_only_frac": round(N * B / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)},
-        "check_vs_torch_fold": ok,
+        # plain run: the headline alone; --full: every other object below
+        "full": bool(args.full),
     }
+    if args.full:
+        line["roofline"]["kernel_ms_blocks"] = blocks    # a separate pass
+        line["check_vs_torch_fold"] = ok
+    if args.dump_outputs:
+        line["dump_outputs"] = args.dump_outputs
     if not cuda:
         line["device"] = "cpu plumbing self-test (torch CPU add, gloo): NOT a measurement"
     if rehearse:
         line["device"] = (f"rehearsal: {world} ranks sharing cuda:0 over gloo (HIP fold, "
                           "no RCCL: the scatter and local-reduce legs move CUDA tensors "
                           f"through gloo, {xchg_elems} elements): NOT a measurement")
+
+    if not args.full:
+        # plain run: the headline line is all there is
+        if rank == 0:
+            emit(line)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # N > 1 on GPUs: the exchange legs go through the shard C ABI over RCCL
     # (byteps_shard_*), the path a core_loops.cc caller binds; gloo

@@ -8,8 +8,9 @@ oracle/_ref/libbpsr_ref.so):
 
 For every case the inputs are regenerated deterministically by
 prophet_amd.synth (seeded splitmix64), so only the expected OUTPUT bytes are
-stored (tests/golden/outputs.bin) plus a manifest with the case parameters and
-sha256 of inputs and outputs (tests/golden/manifest.json).
+stored (tests/golden/outputs.NNN.bin, in parts of PART_BYTES) plus a manifest
+with the case parameters and sha256 of inputs and outputs
+(tests/golden/manifest.json).
 
 Expected outputs of reference dtypes come from the reference's own compiled
 CpuReducer (``pinned_by: "reference"``), replaying the server fold
@@ -20,6 +21,7 @@ reference implementation; its vectors come from the clean-room restatement
 """
 from __future__ import annotations
 
+import glob
 import hashlib
 import json
 import os
@@ -35,6 +37,7 @@ from prophet_amd import synth  # noqa: E402
 from prophet_amd.dtypes import DType, REFERENCE_DTYPES, elem_size  # noqa: E402
 
 OUT_DIR = os.path.join(ROOT, "tests", "golden")
+PART_BYTES = 1_000_000   # outputs.NNN.bin: the output bytes back to back, cut every PART_BYTES
 
 SMALL_N = [1, 7, 8, 9, 63, 64, 65, 1003, 4099]   # spans the F16C body/tail split
 WORKERS = [2, 3, 8, 16]
@@ -138,8 +141,11 @@ def main() -> None:
                  out_sha256=hashlib.sha256(out.tobytes()).hexdigest())
         blob += out.tobytes()
         manifest.append(c)
-    with open(os.path.join(OUT_DIR, "outputs.bin"), "wb") as f:
-        f.write(bytes(blob))
+    for old in glob.glob(os.path.join(OUT_DIR, "outputs.*bin")):
+        os.remove(old)
+    for i in range(0, len(blob), PART_BYTES):     # no stored file over 1 MiB
+        with open(os.path.join(OUT_DIR, f"outputs.{i // PART_BYTES:03d}.bin"), "wb") as f:
+            f.write(bytes(blob[i:i + PART_BYTES]))
     with open(os.path.join(OUT_DIR, "manifest.json"), "w") as f:
         json.dump({"generator": "oracle/gen_golden.py",
                    "reference": "byteps/common/cpu_reducer.cc via oracle/_ref/libbpsr_ref.so",

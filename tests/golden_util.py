@@ -6,6 +6,7 @@ produced by the reference's own compiled CpuReducer (oracle/gen_golden.py).
 """
 from __future__ import annotations
 
+import glob
 import hashlib
 import json
 import os
@@ -24,8 +25,15 @@ def manifest() -> list[dict]:
     if "m" not in _cache:
         with open(os.path.join(GOLDEN, "manifest.json")) as f:
             _cache["m"] = json.load(f)["cases"]
-        with open(os.path.join(GOLDEN, "outputs.bin"), "rb") as f:
-            _cache["blob"] = f.read()
+        # the expected bytes, stored in parts (oracle/gen_golden.py PART_BYTES);
+        # out_offset counts through their concatenation in name order
+        parts = sorted(glob.glob(os.path.join(GOLDEN, "outputs.[0-9][0-9][0-9].bin")))
+        assert parts, f"no outputs.NNN.bin under {GOLDEN}"
+        blob = bytearray()
+        for p in parts:
+            with open(p, "rb") as f:
+                blob += f.read()
+        _cache["blob"] = bytes(blob)
     return _cache["m"]
 
 

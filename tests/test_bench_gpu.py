@@ -19,7 +19,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu",
-           "--steps", "5", "--warmup", "2", "--bucket-mib", "16", "--no-cpu-baseline",
+           "--steps", "5", "--warmup", "2", "--bucket-mib", "16", "--full", "--no-cpu-baseline",
            "--scaling-elems", "4000037", "--e2e-bucket-mib", "16"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -54,7 +54,7 @@ def test_bench_one_gpu_line_has_every_object():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2",
-           "--bucket-mib", "16", "--no-cpu-baseline", "--scaling-elems", "4000037",
+           "--bucket-mib", "16", "--full", "--no-cpu-baseline", "--scaling-elems", "4000037",
            "--e2e-bucket-mib", "16"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -99,6 +99,44 @@ def test_bench_one_gpu_line_has_every_object():
     for obj in (srv, srv["copying_pulls"], e2e):
         assert 0 < obj["frac_of_link"] < 1.5 and 0 < obj["frac_of_h2d"] < 1.5, obj
         assert obj["link_bound_ms"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain run (no --full): the headline line alone, and --dump-outputs
+    writes the aggregate of the last timed step — equal, bit for bit, to
+    torch's left fold of the inputs regenerated here from the bench's seed."""
+    import numpy as np
+    import torch
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5",
+           "--warmup", "2", "--bucket-mib", "16", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["n_gpus"] == 1 and line["steps"] == 5
+    assert line["ms_per_step"] > 0 and line["roofline"]["kernel_ms"] > 0
+    want = 8 * (16 << 20) / (line["ms_per_step"] * 1e-3) / (1 << 30)
+    assert abs(line["value"] - want) <= 0.01 * want
+    for k in ("scaling_cfg4", "fp16", "cfg3_blockq", "server_cfg1", "server_cfg3", "e2e_cfg5",
+              "pcie", "cpu_baseline", "check_vs_torch_fold"):
+        assert k not in line, k
+    assert "kernel_ms_blocks" not in line["roofline"]
+    assert os.listdir(tmp_path) == ["sum.npy"]
+    got = np.load(tmp_path / "sum.npy")
+    n = (16 << 20) // 4
+    assert got.dtype == np.float32 and got.shape == (n,)
+    # the bench's inputs: seed 1000 + rank, 3 sets x 8 workers of randn on the
+    # device; the last timed step (index 4) folds set 4 % 3 = 1
+    torch.manual_seed(1000)
+    dev = torch.device("cuda", 0)
+    sets = [[torch.randn(n, device=dev) for _ in range(8)] for _ in range(3)]
+    ref = sets[1][0].clone()
+    for s in sets[1][1:]:
+        ref.add_(s)
+    assert np.array_equal(got.view(np.int32), ref.cpu().numpy().view(np.int32))
 
 
 def test_server_group_leg_matches_oracle():

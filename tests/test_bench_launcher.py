@@ -21,7 +21,7 @@ def _run_bench(n, extra=()):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gpus", str(n),
            "--steps", "2", "--warmup", "1", "--workers", "3", "--bucket-mib", "0.0625",
-           "--sets", "2", "--no-cpu-baseline", "--scaling-elems", "10007", *extra]
+           "--sets", "2", "--full", "--no-cpu-baseline", "--scaling-elems", "10007", *extra]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     # stdout is exactly the one JSON line: library chatter (gloo's connection
@@ -62,6 +62,86 @@ def test_launcher_one_line_n_ranks(n):
         assert line["rccl"] == {"transport": "gloo, no RCCL", "world": n}
     if n == 1:
         assert "rccl" not in line
+
+
+def _run_plain(n, outdir, steps=4):
+    """A plain run (no --full) of the CPU self-test with --dump-outputs."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gpus", str(n),
+           "--steps", str(steps), "--warmup", "1", "--workers", "3", "--bucket-mib", "0.0625",
+           "--sets", "3", "--dump-outputs", str(outdir)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(r.stdout.strip().splitlines()) == 1, r.stdout
+    return json.loads(r.stdout)
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_run_is_the_headline_alone_and_dumps_its_output(n, tmp_path):
+    """Without --full the line carries the headline and nothing that takes a
+    run of its own; --dump-outputs writes the last timed step's aggregate of
+    every rank, the same from run to run, equal to torch's left fold of the
+    inputs regenerated from the bench's seed."""
+    import numpy as np
+    import torch
+    line = _run_plain(n, tmp_path / "a")
+    assert line["full"] is False and line["n_gpus"] == n
+    assert line["steps"] == 4 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "GiB/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32"
+    # value is the bytes aggregated per step over ms_per_step
+    want = n * 3 * 65536 / (line["ms_per_step"] * 1e-3) / (1 << 30)
+    assert abs(line["value"] - want) <= 0.02 * want + 0.01
+    for k in ("scaling_cfg4", "local_reduce", "fp16", "cfg3_blockq", "server_cfg1", "server_cfg3",
+              "e2e_cfg5", "pcie", "cpu_baseline", "check_vs_torch_fold", "rccl"):
+        assert k not in line, k
+    assert "kernel_ms_blocks" not in line["roofline"]
+    _run_plain(n, tmp_path / "b")
+    names = ["sum.npy"] if n == 1 else [f"sum_rank{r}.npy" for r in range(n)]
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    for r, name in enumerate(names):
+        a = np.load(tmp_path / "a" / name)
+        assert a.dtype == np.float32 and a.shape == (16384,)
+        assert np.array_equal(a, np.load(tmp_path / "b" / name))
+        # the bench's inputs: seed 1000 + rank, sets x workers of randn; the
+        # last timed step (index 3) folds set 3 % 3 = 0
+        torch.manual_seed(1000 + r)
+        srcs = [torch.randn(16384) for _ in range(3)]
+        ref = srcs[0].clone()
+        for s in srcs[1:]:
+            ref.add_(s)
+        assert np.array_equal(a, ref.numpy())
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """An output over the dump budget is written as a fixed sample: head and
+    tail whole, seeded indices between them, in index order, within budget;
+    f64 / i32 / i64 go out as float64, the rest as float32."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    monkeypatch.setattr(bench, "DUMP_EDGE_ELEMS", 100)
+    x = torch.arange(10_000, dtype=torch.float32)
+    p = bench.dump_outputs(str(tmp_path / "d"), x.view(torch.uint8), torch.float32, 1, 0)
+    a = np.load(p)
+    assert os.path.basename(p) == "sum.npy" and a.dtype == np.float32 and a.nbytes <= 4000
+    assert a.shape == (1000,) and np.all(np.diff(a) >= 0)       # values are their own indices
+    assert np.array_equal(a[:100], np.arange(100))
+    assert np.array_equal(a[-100:], np.arange(9900, 10_000))
+    assert len(np.unique(a[100:-100])) > 700                    # spread, not one window
+    p2 = bench.dump_outputs(str(tmp_path / "e"), x.view(torch.uint8), torch.float32, 1, 0)
+    assert np.array_equal(a, np.load(p2))
+    # two ranks share the budget; a small output goes out whole
+    p = bench.dump_outputs(str(tmp_path / "d"), x.view(torch.uint8), torch.float32, 2, 1)
+    assert os.path.basename(p) == "sum_rank1.npy" and np.load(p).nbytes <= 2000
+    for tdt, ndt in ((torch.int32, np.float64), (torch.float64, np.float64),
+                     (torch.float16, np.float32), (torch.uint8, np.float32)):
+        y = torch.arange(50).to(tdt)
+        b = np.load(bench.dump_outputs(str(tmp_path / "f"), y.view(torch.uint8), tdt, 1, 0))
+        assert b.dtype == ndt and np.array_equal(b, np.arange(50))
 
 
 def test_exchange_transport_rule():
@@ -133,7 +213,7 @@ def test_rccl_check_failure_fails_the_run():
     env["BPSR_BENCH_TEST_RCCL"] = "shared_device"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gpus", "2",
            "--steps", "2", "--warmup", "1", "--workers", "3", "--bucket-mib", "0.0625",
-           "--sets", "2", "--no-cpu-baseline", "--scaling-elems", "10007"]
+           "--sets", "2", "--full", "--no-cpu-baseline", "--scaling-elems", "10007"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     sys.path.insert(0, ROOT)
     import bench
@@ -160,7 +240,7 @@ def test_torchrun_launch_one_line():
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu", "--steps", "2",
            "--warmup", "1", "--workers", "3", "--bucket-mib", "0.0625", "--sets", "2",
-           "--no-cpu-baseline", "--scaling-elems", "10007"]
+           "--full", "--no-cpu-baseline", "--scaling-elems", "10007"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -181,7 +261,7 @@ def test_stalled_collective_fails_loudly(launcher):
     env.update(BPSR_BENCH_TEST_STALL="scatter", BPSR_BENCH_WATCHDOG_S="8")
     args = [os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gpus", "2", "--steps", "2",
             "--warmup", "1", "--workers", "3", "--bucket-mib", "0.0625", "--sets", "2",
-            "--no-cpu-baseline", "--scaling-elems", "10007"]
+            "--full", "--no-cpu-baseline", "--scaling-elems", "10007"]
     if launcher == "self":
         cmd = [sys.executable] + args
     else:

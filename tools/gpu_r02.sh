@@ -31,7 +31,7 @@ for s in $STEPS; do
     blockq) run blockq 400 python -u -m pytest tests/test_blockq_gpu.py -x -v -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     server) run server 400 python -u -m pytest tests/test_server_gpu.py -x -v -p no:cacheprovider --timeout 200 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     cfg3n) run cfg3_native 300 ./tools/cfg3_native tools/cfg3_resnet50_table.txt 200 7 tools/cfg3_resnet50_tasks.txt ;;
     dtypes) for spec in "f32 reference 8" "f64 reference 8" "f16 reference 8" "bf16 reference 8" \
                         "i32 reference 8" "i64 reference 8" "u8 reference 8" "i8 reference 8" \

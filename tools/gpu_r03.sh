@@ -30,8 +30,8 @@ for s in $STEPS; do
   case $s in
     gputest) run gputest 1100 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
-    bench5) run bench5 400 python bench.py --steps 20 --warmup 5 ;;
+    bench) run bench 600 python bench.py --full ;;
+    bench5) run bench5 400 python bench.py --steps 20 --warmup 5 --full ;;
     srv) for v in 0 1 4; do run srv_v$v 300 $SRV 20 4 $v || exit 1; done ;;
     srvall) run srvall 400 $SRV 20 4 ;;
     srvprof) for v in 0 4; do
@@ -39,7 +39,7 @@ for s in $STEPS; do
              done ;;
     cfg3) run cfg3 300 tools/cfg3_native tools/cfg3_resnet50_table.txt 200 7 tools/cfg3_resnet50_tasks.txt ;;
     cfg3prof) run cfg3prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg3prof -o run -- tools/cfg3_native tools/cfg3_resnet50_table.txt 200 3 "" blockq_live_release ;;
-    benchprof) run benchprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/benchprof -o run -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
+    benchprof) run benchprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/benchprof -o run -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
   # keep what comes back small: traces compressed, databases dropped

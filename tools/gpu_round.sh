@@ -42,10 +42,10 @@ for s in $STEPS; do
              run bqexp_v$v 300 env BPSR_BQ_VPT=$v python tools/bench_configs.py --only cfg3 --variants blockq || exit 1
            done ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     sweep) run sweep 600 python tools/sweep.py ;;
     prof)  run prof 600 rocprofv3 --kernel-trace --stats --output-format csv \
-             -d "$OUT/prof" -o bench -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline ;;
+             -d "$OUT/prof" -o bench -- python bench.py --steps 50 --warmup 5 --full --no-cpu-baseline ;;
     pmc)   run pmc 900 python tools/pmc_traffic.py --out "$OUT/pmc" ;;
     occ)   run occ 600 python tools/occ_sweep.py ;;
     cfg3)  run cfg3 600 python tools/bench_configs.py --only cfg3,sweep ;;

@@ -80,8 +80,7 @@ def main():
     p.add_argument("--reaggregate", action="store_true",
                    help="re-read the passes already under --out (no profiling run)")
     p.add_argument("bench_args", nargs="*",
-                   default=["--steps", "12", "--warmup", "2", "--no-cpu-baseline",
-                            "--no-scaling", "--no-cfg3", "--no-fp16", "--no-e2e"])
+                   default=["--steps", "12", "--warmup", "2"])   # a plain run: the headline
     a = p.parse_args()
     global KERNEL
     KERNEL = a.kernel
