@@ -56,7 +56,8 @@ extern "C" {
 
 /* 3: byteps_server_config.engine_blocking; bpsr/shard.h
  * 4: byteps_server_config.release; byteps_shard_rccl_version
- * 5: byteps_server_create_sized (a caller states its config's size) */
+ * 5: byteps_server_create_sized (a caller states its config's size)
+ *    additive, still 5: byteps_reduce_compress_fp16 / _decompress_fp16 */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -287,6 +288,30 @@ int byteps_reduce_blockq_debug(byteps_reduce_blockq* q, uint32_t* out, int cap);
 
 /* CpuReducer::copy(dst, src, len), cpu_reducer.cc:209-220 (device to device). */
 int byteps_reduce_copy(void* dst, const void* src, size_t len, void* stream);
+
+/* FP16 gradient compression (byteps/torch/compression.py, FP16Compressor):
+ * the cast before a push and the cast back after the pull, device to device.
+ * `nelem` is in ELEMENTS — the one exception to "lengths are bytes", because
+ * the two operands differ in element size (fp16: 2 * nelem bytes; the other:
+ * nelem * sizeof(T)).  T (`src_dtype` / `dst_dtype`) is FLOAT32, FLOAT64 or
+ * BFLOAT16; anything else is EDTYPE.
+ *   compress:    dst[i] = fp16(src[i]), round to nearest even (subnormal
+ *                results kept, |x| >= 65520 -> +-inf, signed zeros kept);
+ *                f64 is rounded to f32 first, as the host conversion does;
+ *                bf16 is widened exactly.  A NaN gives a NaN (payload
+ *                unspecified).
+ *   decompress:  dst[i] = T(src[i]) for divisor 1 (exact for f32 / f64, RNE
+ *                for bf16); for divisor d > 1,
+ *                dst[i] = T(fp16(float(src[i]) / float(d))): the quotient is
+ *                rounded to fp16 BEFORE it is widened, because the
+ *                reference's average divides the compressed tensor in place
+ *                (byteps/torch/ops.cc:77-81) and decompresses afterwards.
+ * The two byte ranges must not overlap at all, divisor >= 1 (EARGS
+ * otherwise); nelem == 0 succeeds without a launch. */
+int byteps_reduce_compress_fp16(void* dst, const void* src, size_t nelem, int src_dtype,
+                                void* stream);
+int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
+                                  int divisor, void* stream);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

@@ -1485,6 +1485,41 @@ int byteps_reduce_copy(void* dst, const void* src, size_t len, void* stream) {
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "copy kernel launch");
 }
 
+// Shared checks of the two fp16 casts, all before any HIP call: h = the fp16
+// operand, w = the wide one.  Returns 1 when there is nothing to do.
+static int cast_check(const void* h, const void* w, size_t nelem, int dtype, int divisor) {
+  if (dtype != kFloat32 && dtype != kFloat64 && dtype != kBFloat16)
+    return fail(BYTEPS_REDUCE_EDTYPE, "fp16 compression of data type %d", dtype);
+  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  if (nelem == 0) return 1;
+  if (!h || !w) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
+  const size_t es = (size_t)elem_size(dtype);
+  if (nelem > SIZE_MAX / es) return fail(BYTEPS_REDUCE_EARGS, "element count overflows");
+  const uintptr_t x = (uintptr_t)h, y = (uintptr_t)w;
+  const size_t hb = nelem * 2, wb = nelem * es;
+  if (x > UINTPTR_MAX - hb || y > UINTPTR_MAX - wb)
+    return fail(BYTEPS_REDUCE_EARGS, "operand wraps the address space");
+  if (x < y + wb && y < x + hb) return fail(BYTEPS_REDUCE_EARGS, "dst and src overlap");
+  return BYTEPS_REDUCE_OK;
+}
+
+int byteps_reduce_compress_fp16(void* dst, const void* src, size_t nelem, int src_dtype,
+                                void* stream) {
+  const int rc = cast_check(dst, src, nelem, src_dtype, 1);
+  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
+  hipError_t e = launch_compress_fp16(dst, src, nelem, src_dtype, tuning(), to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "compress kernel launch");
+}
+
+int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
+                                  int divisor, void* stream) {
+  const int rc = cast_check(src, dst, nelem, dst_dtype, divisor);
+  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
+  hipError_t e = launch_decompress_fp16(dst, src, nelem, dst_dtype, divisor, tuning(),
+                                        to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "decompress kernel launch");
+}
+
 int byteps_reduce_sync(void* stream) {
   hipError_t e = hipStreamSynchronize(to_stream(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "hipStreamSynchronize");

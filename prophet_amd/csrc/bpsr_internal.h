@@ -343,6 +343,15 @@ int fold_any_alias(void* dst, const void* const* srcs, int n, size_t len, int dt
 hipError_t launch_copy(void* dst, const void* src, size_t len, const Tuning& tu,
                        hipStream_t s);
 
+// FP16 gradient compression (bpsr_k_cast.hip): nelem ELEMENTS of f32, f64 or
+// bf16 to fp16 and back; the way back divides by `divisor` on the fp16 value
+// (rounded to fp16) before widening when divisor > 1.  Operands validated by
+// the caller (byteps_reduce_compress_fp16 / _decompress_fp16).
+hipError_t launch_compress_fp16(void* dst, const void* src, size_t nelem, int src_dtype,
+                                const Tuning& tu, hipStream_t s);
+hipError_t launch_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
+                                  int divisor, const Tuning& tu, hipStream_t s);
+
 // Pull copy service (bpsr_copy_service.cpp, kernel in bpsr_k_service.hip):
 // a persistent kernel of a few workgroups serving copies that host threads
 // post into a pinned job ring — a blocking pull's copy with no HIP call and

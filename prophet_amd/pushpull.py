@@ -25,6 +25,14 @@ byteps/server/server.cc, with an in-process transport:
 
 Buffers may be host (numpy / CPU tensors) or device tensors; every byte of
 arithmetic is the server's HIP fold.
+
+``init_tensor(..., compression=Compression.fp16)`` makes a floating tensor
+travel as fp16 (byteps/torch/__init__.py:133-170): the context's size, dtype
+and partitions are those of the COMPRESSED tensor, every call casts into a
+per-context fp16 staging buffer, pushes and pulls that, and one fused launch
+widens the result into the output — dividing the fp16 value first when
+``average=True``, as the reference's callback does on the compressed tensor
+(byteps/torch/ops.cc:77-81).  DESIGN.md §11 has the stream-ordering argument.
 """
 from __future__ import annotations
 
@@ -33,6 +41,7 @@ from dataclasses import dataclass, field
 
 from .buckets import (DEFAULT_PARTITION_BYTES, cantor_command, depair_command,
                       local_size_from_env, partition_bound, partition_bytes_from_env)
+from .compression import Compression
 from .dtypes import DType, elem_size
 
 K_DEFAULT_PUSH_PULL = 0     # RequestType::kDefaultPushPull (common.h:68-71)
@@ -67,6 +76,13 @@ class Context:
     key_list: list = field(default_factory=list)
     parts: list = field(default_factory=list)      # (key, offset, len) in bytes
     initialized: bool = False
+    # fp16 compression (None: the tensor travels as it is): the compressor,
+    # the caller's dtype and byte size, and the fp16 buffer that is pushed
+    # from and pulled into; size / dtype / parts above are the compressed ones
+    compressor: object = None
+    orig_dtype: int = 0
+    orig_size: int = 0
+    staging: object = None
     init_lock: threading.Lock = field(default_factory=threading.Lock)
 
 
@@ -114,10 +130,13 @@ class Worker:
             acc += ln
         return out
 
-    def init_tensor(self, name: str, data, dtype: int) -> Context:
+    def init_tensor(self, name: str, data, dtype: int, compression=Compression.none) -> Context:
         """InitTensor (operations.cc:219-316): keys, then one blocking init push
         per partition (every worker's init push of a key returns only once all
-        of them arrived: the global barrier)."""
+        of them arrived: the global barrier).  ``compression``: how the tensor
+        travels from now on (``Compression.fp16``: floating tensors as fp16 —
+        the keys, partitions and request dtype are the compressed tensor's;
+        integers and fp16 tensors pass through as with ``Compression.none``)."""
         self.declare(name)
         ctx = self.contexts[name]
         size = _nbytes(data)
@@ -126,6 +145,12 @@ class Worker:
                 return ctx
             if size <= 0:
                 raise ValueError("init tensor size not larger than 0")      # operations.cc:229
+            if compression.compresses(data):
+                ctx.compressor = compression
+                ctx.orig_dtype, ctx.orig_size = int(dtype), size
+                ctx.staging = _half_like(data)
+                data = compression.compress_into(ctx.staging, data)
+                size, dtype = _nbytes(data), DType.FLOAT16
             ctx.size, ctx.dtype = size, int(dtype)
             start = ctx.declared_key << 16
             ctx.parts = [(start + i, off, ln) for i, (off, ln) in enumerate(self._partition(size))]
@@ -149,6 +174,8 @@ class Worker:
         ctx = self.contexts[name]
         if not ctx.initialized:
             raise RuntimeError(f"{name}: init_tensor first")
+        if ctx.compressor is not None:
+            return self._push_pull_compressed(ctx, tensor, output, order, average)
         if _nbytes(tensor) != ctx.size:
             raise ValueError(f"{name}: {_nbytes(tensor)} bytes, declared {ctx.size}")
         out = tensor if output is None else output
@@ -166,6 +193,36 @@ class Worker:
             if not size:
                 raise ValueError("average: the frontend does not know the worker count")
             _divide_(out, size)
+
+    def _push_pull_compressed(self, ctx: Context, tensor, output, order, average: bool) -> None:
+        """push_pull of a context initialised with a compressor: cast into the
+        context's staging buffer, push and pull THAT (its partitions, FLOAT16
+        in the request word), then one launch widens it into the output,
+        dividing the fp16 value by the worker count first for ``average``.
+        Device tensors: both casts run on the calling thread's current stream;
+        the output is complete in that stream's order."""
+        out = tensor if output is None else output
+        for x, what in ((tensor, "tensor"), (out, "output tensor")):
+            if _nbytes(x) != ctx.orig_size:
+                raise ValueError(f"{ctx.name}: {what} of {_nbytes(x)} bytes, "
+                                 f"declared {ctx.orig_size}")
+            if x.dtype != tensor.dtype or not ctx.compressor.compresses(x):
+                raise ValueError(f"{ctx.name}: {what} dtype {x.dtype} does not match "
+                                 "the compressed context")
+        divisor = 1
+        if average:
+            divisor = getattr(self.frontend, "size", None)
+            if not divisor:
+                raise ValueError("average: the frontend does not know the worker count")
+        wire = ctx.compressor.compress_into(ctx.staging, _contiguous(tensor))
+        cmd = cantor_command(K_DEFAULT_PUSH_PULL, ctx.dtype)
+        idx = range(len(ctx.parts)) if order is None else order
+        for i in idx:
+            key, off, ln = ctx.parts[i]
+            self.frontend.push(cmd, key, self.rank, _slice(wire, off, ln), ln)
+        for key, off, ln in ctx.parts:
+            self.frontend.pull(key, _slice(wire, off, ln), ln)
+        ctx.compressor.decompress_into(_contiguous(out), wire, divisor)
 
     # byteps/torch/ops.py: push_pull_async -> handle, poll(handle),
     # synchronize(handle).  Calls run in call order on the worker's own
@@ -200,7 +257,10 @@ class Worker:
         tensor, every other rank pushes zeros, everyone pulls the sum into
         ``output`` (a new buffer like ``tensor`` if not given; the source is
         left untouched, as test_mxnet.py:116-158 requires).  The tensor must
-        have been through ``init_tensor``."""
+        have been through ``init_tensor`` — without compression: parameters
+        are broadcast exactly."""
+        if self.contexts[name].compressor is not None:
+            raise ValueError(f"{name}: broadcast needs a context without compression")
         src = tensor if self.rank == root_rank else _zeros_like(tensor)
         out = _zeros_like(tensor) if output is None else output
         self.push_pull(name, src, output=out)
@@ -224,15 +284,23 @@ class Worker:
             scheduler.reset()
             groups = release_groups(scheduler, arrivals)
         by_key = {c.declared_key: c for c in ctxs}
+        # what travels: the tensor itself, or a compressed context's staging
+        # buffer (cast once, before its first partition is pushed)
+        wire = {}
         for g in groups:
             for t in g:
                 c = by_key[t.grad]
+                if c.name not in wire:
+                    wire[c.name] = tensors[c.name] if c.compressor is None else \
+                        c.compressor.compress_into(c.staging, _contiguous(tensors[c.name]))
                 key, off, ln = c.parts[t.part]
                 self.frontend.push(cantor_command(K_DEFAULT_PUSH_PULL, c.dtype), key, self.rank,
-                                   _slice(tensors[c.name], off, ln), ln)
+                                   _slice(wire[c.name], off, ln), ln)
         for c in ctxs:
             for key, off, ln in c.parts:
-                self.frontend.pull(key, _slice(tensors[c.name], off, ln), ln)
+                self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
+            if c.compressor is not None:
+                c.compressor.decompress_into(_contiguous(tensors[c.name]), wire[c.name])
         return [[(t.grad, t.part) for t in g] for g in groups]
 
 
@@ -253,6 +321,24 @@ def _divide_(x, size: int) -> None:
     if not np.issubdtype(x.dtype, np.floating):
         raise ValueError("average needs a floating dtype")
     x /= size
+
+
+def _half_like(x):
+    """An fp16 buffer of x's kind, device and element count (a compressed
+    context's staging buffer, allocated once at init_tensor)."""
+    if hasattr(x, "data_ptr"):                             # torch
+        import torch
+        return torch.empty(x.numel(), dtype=torch.float16, device=x.device)
+    import numpy as np
+    return np.empty(x.size, dtype=np.float16)
+
+
+def _contiguous(x):
+    """x itself if contiguous (the casts write through it), else an error."""
+    ok = x.is_contiguous() if hasattr(x, "data_ptr") else x.flags["C_CONTIGUOUS"]
+    if not ok:
+        raise ValueError("push_pull needs contiguous tensors")
+    return x
 
 
 def _zeros_like(x):

@@ -9,6 +9,7 @@ reference                              here
 ``sum(dst, src, len, dtype)``          ``GpuReducer.sum`` -> ``byteps_reduce_sum``
 ``sum(dst, src1, src2, len, dtype)``   ``GpuReducer.sum3`` -> ``byteps_reduce_sum3``
 ``copy(dst, src, len)``                ``GpuReducer.copy`` -> ``byteps_reduce_copy``
+``FP16Compressor`` (torch front end)   ``GpuReducer.compress_fp16`` / ``decompress_fp16``
 ``GetDataType(int)``                   ``GpuReducer.GetDataType``
 server fold, server.cc:216-273         ``GpuReducer.sum_n`` -> ``byteps_reduce_sum_n``
 one Prophet block                      ``GpuReducer.sum_batched``
@@ -55,6 +56,7 @@ EXPORTS = (
     "byteps_reduce_blockq_release_host", "byteps_reduce_blockq_overlap",
     "byteps_reduce_blockq_join", "byteps_reduce_blockq_release_stream",
     "byteps_reduce_blockq_queue_ids",
+    "byteps_reduce_compress_fp16", "byteps_reduce_decompress_fp16",
 )
 
 
@@ -116,6 +118,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_blockq_join.argtypes = [_vp, _vp]
     L.byteps_reduce_blockq_release_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
     L.byteps_reduce_blockq_queue_ids.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64), _int]
+    L.byteps_reduce_compress_fp16.argtypes = [_vp, _vp, _sz, _int, _vp]
+    L.byteps_reduce_decompress_fp16.argtypes = [_vp, _vp, _sz, _int, _int, _vp]
     _LIB = L
     return L
 
@@ -144,6 +148,17 @@ def _fits(length: int, *xs) -> None:
             have = int(x.numel()) * int(x.element_size())
             if int(length) > have:
                 raise ValueError(f"{int(length)}-byte operation on a {have}-byte tensor")
+
+
+def _fits_cast(nelem: int, half, wide, wide_dtype: int) -> None:
+    """``_fits`` for the fp16 casts, whose operands differ in element size:
+    ``half`` holds ``nelem`` fp16 values, ``wide`` as many of ``wide_dtype``
+    (an unsupported dtype is left to the library: EDTYPE)."""
+    if int(nelem) < 0:
+        raise ValueError(f"negative element count {nelem}")
+    _fits(int(nelem) * 2, half)
+    if int(wide_dtype) in (DType.FLOAT32, DType.FLOAT64, DType.BFLOAT16):
+        _fits(int(nelem) * elem_size(wide_dtype), wide)
 
 
 def _stream_of(x, stream):
@@ -187,6 +202,25 @@ class GpuReducer:
         _fits(length, dst, src)
         _check(self.lib.byteps_reduce_copy(_ptr(dst), _ptr(src), int(length),
                                            _stream_of(dst, stream)))
+        return 0
+
+    def compress_fp16(self, dst, src, nelem: int, src_dtype: int, stream=None) -> int:
+        """``dst[i] = fp16(src[i])`` for ``nelem`` ELEMENTS of f32, f64 or bf16
+        (byteps_reduce_compress_fp16; round to nearest even, f64 through f32)."""
+        _fits_cast(nelem, dst, src, src_dtype)
+        _check(self.lib.byteps_reduce_compress_fp16(_ptr(dst), _ptr(src), int(nelem),
+                                                    int(src_dtype), _stream_of(dst, stream)))
+        return 0
+
+    def decompress_fp16(self, dst, src, nelem: int, dst_dtype: int, divisor: int = 1,
+                        stream=None) -> int:
+        """``dst[i] = T(src[i])``, or ``T(fp16(src[i] / divisor))`` for a
+        divisor above 1: the average of a compressed push_pull, divided on the
+        fp16 value as the reference does (byteps_reduce_decompress_fp16)."""
+        _fits_cast(nelem, src, dst, dst_dtype)
+        _check(self.lib.byteps_reduce_decompress_fp16(_ptr(dst), _ptr(src), int(nelem),
+                                                      int(dst_dtype), int(divisor),
+                                                      _stream_of(dst, stream)))
         return 0
 
     def sum_n(self, dst, srcs: Sequence, length: int, dtype: int,

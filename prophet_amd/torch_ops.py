@@ -19,6 +19,13 @@ op                                    reference / C ABI
                                       (left fold in list order) -> byteps_reduce_sum_n
 ``bpsr::sum_n_out(dst, srcs, mode)``  the same into ``dst`` (``dst`` may be
                                       ``srcs[0]``: the zero-copy accumulator)
+``bpsr::compress_fp16(src) -> out``   ``FP16Compressor.compress``,
+                                      byteps/torch/compression.py
+                                      -> byteps_reduce_compress_fp16
+``bpsr::compress_fp16_out(dst, src)`` the same into a preallocated fp16 ``dst``
+``bpsr::decompress_fp16_out(dst,      ``FP16Compressor.decompress`` fused with
+src, divisor)``                       average's divide on the fp16 value
+                                      -> byteps_reduce_decompress_fp16
 ====================================  ===========================================
 
 Tensors must be contiguous, on one CUDA (HIP) device, of one dtype among the
@@ -32,7 +39,7 @@ from typing import List
 import torch
 
 from .dtypes import from_torch
-from .reducer import MODE_REFERENCE, GpuReducer, ReduceError, EARGS
+from .reducer import MODE_REFERENCE, GpuReducer, ReduceError, EARGS, EDTYPE
 
 _RED = None
 
@@ -95,6 +102,61 @@ def sum_n(srcs: List[torch.Tensor], mode: int = MODE_REFERENCE) -> torch.Tensor:
     return out
 
 
+def _check_cast(half: torch.Tensor, wide: torch.Tensor) -> int:
+    """Operands of an fp16 cast: ``half`` fp16, ``wide`` f32 / f64 / bf16, as
+    many elements, one device, contiguous.  Returns the element count."""
+    for t in (half, wide):
+        if t.device.type != "cuda":
+            raise ReduceError(EARGS, f"bpsr ops need device tensors, got {t.device}")
+        if not t.is_contiguous():
+            raise ReduceError(EARGS, "bpsr ops need contiguous tensors")
+    if half.dtype != torch.float16:
+        raise ReduceError(EDTYPE, f"the compressed tensor must be float16, got {half.dtype}")
+    if wide.dtype not in (torch.float32, torch.float64, torch.bfloat16):
+        raise ReduceError(EDTYPE, f"fp16 compression of {wide.dtype}")
+    if half.numel() != wide.numel() or half.device != wide.device:
+        raise ReduceError(EARGS, "bpsr ops need tensors of one size and device")
+    return wide.numel()
+
+
+@torch.library.custom_op("bpsr::compress_fp16_out", mutates_args=("dst",), device_types="cuda")
+def compress_fp16_out(dst: torch.Tensor, src: torch.Tensor) -> None:
+    n = _check_cast(dst, src)
+    _red().compress_fp16(dst, src, n, from_torch(src.dtype), stream=_stream(dst))
+
+
+@torch.library.custom_op("bpsr::compress_fp16", mutates_args=(), device_types="cuda")
+def compress_fp16(src: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(src.shape, dtype=torch.float16, device=src.device)
+    n = _check_cast(out, src)
+    _red().compress_fp16(out, src, n, from_torch(src.dtype), stream=_stream(out))
+    return out
+
+
+@torch.library.custom_op("bpsr::decompress_fp16_out", mutates_args=("dst",),
+                         device_types="cuda")
+def decompress_fp16_out(dst: torch.Tensor, src: torch.Tensor, divisor: int = 1) -> None:
+    n = _check_cast(src, dst)
+    if divisor < 1:
+        raise ReduceError(EARGS, f"divisor {divisor} < 1")
+    _red().decompress_fp16(dst, src, n, from_torch(dst.dtype), divisor, stream=_stream(dst))
+
+
+@compress_fp16_out.register_fake
+def _(dst, src):
+    return None
+
+
+@compress_fp16.register_fake
+def _(src):
+    return torch.empty(src.shape, dtype=torch.float16, device=src.device)
+
+
+@decompress_fp16_out.register_fake
+def _(dst, src, divisor=1):
+    return None
+
+
 @sum_.register_fake
 def _(dst, src):
     return None
@@ -120,6 +182,8 @@ def _(srcs, mode=MODE_REFERENCE):
     return torch.empty_like(srcs[0])
 
 
-OPS = ("sum_", "sum3_", "copy_", "sum_n_out", "sum_n")
+OPS = ("sum_", "sum3_", "copy_", "sum_n_out", "sum_n",
+       "compress_fp16", "compress_fp16_out", "decompress_fp16_out")
 
-__all__ = ["sum_", "sum3_", "copy_", "sum_n_out", "sum_n", "OPS"]
+__all__ = ["sum_", "sum3_", "copy_", "sum_n_out", "sum_n", "compress_fp16",
+           "compress_fp16_out", "decompress_fp16_out", "OPS"]
