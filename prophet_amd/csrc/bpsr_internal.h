@@ -416,7 +416,7 @@ bool copysvc_wedged(const CopyService* svc);
 uint64_t copysvc_posted(CopyService* svc);
 void copysvc_set_trace(CopyService* svc, uint64_t* dev_trace);
 
-// Keyed block queue (bpsr_api.cpp): the PS server's device releases.  One
+// Keyed block queue (bpsr_keyq.cpp): the PS server's device releases.  One
 // block per key (bucket k: dst = the key's store, srcs = its receive slots in
 // WORKER order, n <= kKeyedMaxSrcs); launch k folds every key once, each tile
 // as soon as its own key is released for epoch k, in the arrival order its
@@ -434,7 +434,7 @@ uint32_t keyq_launched(struct byteps_reduce_blockq* q);
 // Pass epoch `epoch` without a launch (the next launch consumes epoch + 1):
 // an epoch no consumer folds.  False unless `epoch` is the next one to launch.
 bool keyq_advance(struct byteps_reduce_blockq* q, uint32_t epoch);
-// Both of the above under one lock.
+// keyq_next_epoch and keyq_launched in one call (two lock-free reads).
 void keyq_state(byteps_reduce_blockq* q, int key, uint32_t* next_epoch, uint32_t* launched);
 // `first` (optional): set when this release is the first one of its epoch
 // (keyq_opened; after keyq_close, none is).
