@@ -57,7 +57,9 @@ extern "C" {
 /* 3: byteps_server_config.engine_blocking; bpsr/shard.h
  * 4: byteps_server_config.release; byteps_shard_rccl_version
  * 5: byteps_server_create_sized (a caller states its config's size)
- *    additive, still 5: byteps_reduce_compress_fp16 / _decompress_fp16 */
+ *    additive, still 5: byteps_reduce_compress_fp16 / _decompress_fp16
+ *    additive, still 5: byteps_reduce_cast_plan_create / _compress /
+ *                       _decompress / _destroy (byteps_cast_desc) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -312,6 +314,37 @@ int byteps_reduce_compress_fp16(void* dst, const void* src, size_t nelem, int sr
                                 void* stream);
 int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
                                   int divisor, void* stream);
+
+/* Cast plan: the casts of a whole push_pull iteration — every gradient to
+ * fp16 before the pushes, every result back after the pulls — as ONE launch
+ * each way.  Segment i pairs `nelem` elements of the plan's wide type
+ * (`wide_dtype`: FLOAT32, FLOAT64 or BFLOAT16, one per plan; else EDTYPE) at
+ * `wide` with as many fp16 values at `half`.  compress writes every `half`
+ * from its `wide`, decompress every `wide` from its `half`, with the
+ * arithmetic and rounding of byteps_reduce_compress_fp16 / _decompress_fp16
+ * per segment: the bytes written are those of one such call per segment.  The
+ * divisor is given at the launch, so one plan serves every divisor.
+ *   create:  cuts the segments into a table resident in device memory, uploaded
+ *            once, on the calling thread's current device.  A null pointer
+ *            with nelem > 0 is EARGS; because a plan runs both ways, all
+ *            2 * nsegs byte ranges must be pairwise disjoint (EARGS).
+ *            Segments with nelem == 0 are skipped; a plan without a live
+ *            segment is valid and its launches succeed without a launch.
+ *   compress / decompress: asynchronous on `stream`; divisor < 1 is EARGS.
+ *   destroy: frees the table with hipFree, which waits for launches in flight.
+ * The plan holds raw pointers: the caller keeps the segments' memory alive
+ * and in place for as long as the plan is launched. */
+typedef struct byteps_cast_desc {
+  void* wide;
+  void* half;
+  size_t nelem; /* ELEMENTS, as in the one-tensor casts */
+} byteps_cast_desc;
+typedef struct byteps_reduce_cast_plan byteps_reduce_cast_plan;
+int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
+                                   byteps_reduce_cast_plan** out);
+int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* plan, void* stream);
+int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* plan, int divisor, void* stream);
+int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* plan);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

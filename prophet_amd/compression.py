@@ -22,8 +22,20 @@ uses: with ``divisor > 1`` the fp16 value is divided and rounded to fp16
 FIRST and widened afterwards — the reference's ``average=True`` divides the
 compressed tensor in place (byteps/torch/ops.cc:77-81) before it is
 decompressed (byteps/torch/__init__.py:166-170).
+
+``compress_many_into`` / ``decompress_many_into`` are the same casts for a
+whole iteration's tensors: the device tensors are grouped by (device, wide
+dtype) and each group is ONE launch of a cast plan
+(``byteps_reduce_cast_plan_*``, ``prophet_amd/csrc/bpsr_k_cast_plan.hip``) on
+the calling thread's current stream of that device; per tensor the bytes are
+those of ``compress_into`` / ``decompress_into``.  A :class:`CastPlanCache`
+keeps the plans between iterations.  There is no ``torch.library`` op for
+plans: a plan owns raw device pointers, which a traced graph cannot — the
+one-tensor ops stay the traceable form.
 """
 from __future__ import annotations
+
+from collections import OrderedDict
 
 import numpy as np
 
@@ -53,6 +65,86 @@ def _as_host_tensor(x):
     """A CPU torch view of a CPU tensor or numpy array (no copy)."""
     import torch
     return x if _is_torch(x) else torch.from_numpy(x)
+
+
+class CastPlanCache:
+    """The cast plans of the last few iterations, least recently used out
+    first.  A plan is found again by its wide dtype and the (wide address,
+    fp16 address, element count) of every segment, so a tensor that moved
+    misses and gets a new plan.  A cached plan holds its tensors: their
+    memory cannot be freed, so no other tensor can appear at a cached
+    address while the plan that names it is alive."""
+
+    def __init__(self, capacity: int = 4):
+        self.capacity = int(capacity)
+        self.built = 0                    # plans created so far
+        self._plans: OrderedDict = OrderedDict()
+
+    def __len__(self) -> int:
+        return len(self._plans)
+
+    def get(self, wide_dtype: int, pairs):
+        """The plan over ``pairs`` of flat ``(wide, half)`` device tensors on
+        the current device, built on a miss."""
+        key = (int(wide_dtype),) + tuple(
+            (int(w.data_ptr()), int(h.data_ptr()), int(w.numel())) for w, h in pairs)
+        plan = self._plans.get(key)
+        if plan is not None:
+            self._plans.move_to_end(key)
+            return plan
+        plan = _new_plan(wide_dtype, pairs)
+        self.built += 1
+        self._plans[key] = plan
+        while len(self._plans) > self.capacity:
+            _, old = self._plans.popitem(last=False)
+            old.close()                   # waits for its launches in flight
+        return plan
+
+    def close(self) -> None:
+        while self._plans:
+            _, plan = self._plans.popitem(last=False)
+            plan.close()
+
+
+def _new_plan(wide_dtype: int, pairs):
+    from .torch_ops import _red
+    return _red().cast_plan([(w, h, int(w.numel())) for w, h in pairs], wide_dtype)
+
+
+def _cast_many(pairs, compress: bool, divisor: int, plans) -> None:
+    """``pairs`` of ``(wide, half)`` tensors or arrays: the device ones as one
+    plan launch per (device, wide dtype), the host ones one by one."""
+    if int(divisor) < 1:
+        raise ValueError(f"divisor {divisor} < 1")
+    groups: dict = {}
+    for wide, half in pairs:
+        if not _on_device(wide) and not _on_device(half):
+            if compress:
+                FP16Compressor.compress_into(half, wide)
+            else:
+                FP16Compressor.decompress_into(wide, half, divisor)
+            continue
+        from .torch_ops import _check_cast
+        _check_cast(half, wide)
+        groups.setdefault((wide.device, wide.dtype), []).append(
+            (wide.reshape(-1), half.reshape(-1)))
+    if not groups:
+        return
+    import torch
+    from .dtypes import from_torch
+    for (device, dtype), segs in groups.items():
+        with torch.cuda.device(device):
+            plan = plans.get(from_torch(dtype), segs) if plans is not None \
+                else _new_plan(from_torch(dtype), segs)
+            stream = torch.cuda.current_stream(device)
+            try:
+                if compress:
+                    plan.compress(stream=stream)
+                else:
+                    plan.decompress(int(divisor), stream=stream)
+            finally:
+                if plans is None:
+                    plan.close()          # waits for the launch
 
 
 class Compressor:
@@ -154,6 +246,29 @@ class FP16Compressor(Compressor):
         return out
 
 
+    @staticmethod
+    def compress_many_into(outs, tensors, plans: CastPlanCache | None = None):
+        """``compress_into(outs[i], tensors[i])`` for every i, the device
+        tensors as one cast-plan launch per (device, dtype); returns ``outs``.
+        ``plans`` keeps the plans for the next call over the same tensors;
+        without it a plan is built and destroyed here."""
+        if len(outs) != len(tensors):
+            raise ValueError("compress_many_into: as many outputs as tensors")
+        _cast_many(list(zip(tensors, outs)), True, 1, plans)
+        return outs
+
+    @staticmethod
+    def decompress_many_into(outs, compressed, divisor: int = 1,
+                             plans: CastPlanCache | None = None):
+        """``decompress_into(outs[i], compressed[i], divisor)`` for every i,
+        the device tensors as one cast-plan launch per (device, dtype);
+        returns ``outs``."""
+        if len(outs) != len(compressed):
+            raise ValueError("decompress_many_into: as many outputs as compressed tensors")
+        _cast_many(list(zip(outs, compressed)), False, divisor, plans)
+        return outs
+
+
 class Compression:
     """Optional gradient compression used during push_pull."""
 
@@ -161,4 +276,4 @@ class Compression:
     fp16 = FP16Compressor
 
 
-__all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "Compression"]
+__all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "Compression", "CastPlanCache"]

@@ -472,6 +472,68 @@ int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int 
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "decompress kernel launch");
 }
 
+struct byteps_reduce_cast_plan {
+  int device;
+  int dtype;
+  void* dev_table;
+  CastTableInfo ti;
+};
+
+int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
+                                   byteps_reduce_cast_plan** out) {
+  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
+  *out = nullptr;
+  std::vector<char> host;
+  CastTableInfo ti;
+  const int rc = build_cast_table(segs, nsegs, wide_dtype, tuning().copy_vpt, host, &ti);
+  if (rc) return rc;
+  auto* p = new byteps_reduce_cast_plan();
+  p->dtype = wide_dtype;
+  p->ti = ti;
+  p->dev_table = nullptr;
+  hipError_t e = hipGetDevice(&p->device);
+  if (e == hipSuccess && ti.records > 0) {
+    e = hipMalloc(&p->dev_table, ti.bytes);
+    if (e == hipSuccess)
+      e = hipMemcpy(p->dev_table, host.data(), ti.bytes, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    if (p->dev_table) (void)hipFree(p->dev_table);
+    delete p;
+    return hip_fail(e, "cast plan table upload");
+  }
+  *out = p;
+  return BYTEPS_REDUCE_OK;
+}
+
+static int cast_plan_launch(byteps_reduce_cast_plan* p, bool compress, int divisor,
+                            void* stream) {
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
+  const uint64_t out_bytes = p->ti.nelem * (compress ? 2 : (uint64_t)elem_size(p->dtype));
+  hipError_t e = launch_cast_plan(compress, static_cast<const CastRec*>(p->dev_table),
+                                  p->ti.records, p->dtype, divisor, p->ti.u, out_bytes, tuning(),
+                                  to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan kernel launch");
+}
+
+int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* p, void* stream) {
+  return cast_plan_launch(p, true, 1, stream);
+}
+
+int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* p, int divisor, void* stream) {
+  return cast_plan_launch(p, false, divisor, stream);
+}
+
+int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* p) {
+  if (!p) return BYTEPS_REDUCE_OK;
+  hipError_t e = hipSuccess;
+  if (p->dev_table) e = hipFree(p->dev_table);
+  delete p;
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan free");
+}
+
 int byteps_reduce_sync(void* stream) {
   hipError_t e = hipStreamSynchronize(to_stream(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "hipStreamSynchronize");

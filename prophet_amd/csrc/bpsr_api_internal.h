@@ -1,5 +1,6 @@
 // What the units of the fold C ABI share: bpsr_api.cpp (errors, tuning, the
-// fold calls), bpsr_table.cpp (batch tables), bpsr_queues.cpp (the devices'
+// fold calls), bpsr_table.cpp (batch tables), bpsr_cast_table.cpp (cast plan
+// tables), bpsr_queues.cpp (the devices'
 // library queues and dispatch sequence), bpsr_blockq.cpp (block queue) and
 // bpsr_keyq.cpp (keyed queue).
 #pragma once
@@ -80,6 +81,24 @@ int build_table(const byteps_bucket_desc* buckets, int nbuckets, int dtype, std:
 // host pages are not cached in L2, so the touch would only add a PCIe round
 // trip that every workgroup waits for before it retires.
 BatchLaunch batch_launch(const void* dev_table, const TableInfo& ti, bool in_hbm = true);
+
+// ------------------------------------ cast tables (bpsr_cast_table.cpp) --
+struct CastTableInfo {
+  int u = 1;             // tile size: kBlock * u 8-element units (1, 2 or 4)
+  int live = 0;          // segments with nelem > 0
+  uint32_t records = 0;  // workgroups (guarded tiles and element ranges, then full tiles)
+  uint64_t nelem = 0;    // elements of all segments (store policy: the launch's output bytes)
+  size_t bytes = 0;      // bytes to upload
+};
+
+// Validate the segments (null pointers, pairwise disjoint byte ranges, grid
+// size) and write [CastRec x records] into `out` (bpsr_internal.h: CastRec);
+// on an error `out` is left as it was.  Every segment is cut as a single cast
+// is (cast_cut); the tile size is the single cast's rule applied to the whole
+// launch: `copy_vpt` (Tuning::copy_vpt), halved while the launch would have
+// fewer than kMinTiles vector tiles.  No HIP call.
+int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                     std::vector<char>& out, CastTableInfo* ti);
 
 // ------------------------------------- library queues (bpsr_queues.cpp) --
 // Per device, created on first use, never destroyed: the four library queues

@@ -1,0 +1,277 @@
+// Per-tile device code of the fp16 casts, shared by the single cast
+// (bpsr_k_cast.hip) and the cast plan (bpsr_k_cast_plan.hip): the wide-side
+// element types, one element's arithmetic, the full tile, the guarded partial
+// tile and the element loop.  What the arithmetic is and why the full tile
+// re-deals its lanes: bpsr_k_cast.hip.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bpsr_kernels_impl.h"
+
+namespace bpsr {
+
+// Wide-side element: its 16-B vectors per unit, and the exact steps to and
+// from f32 bits.  get/put address element e (0..7) of a unit's vectors.
+template <int DT>
+struct Wide;
+
+template <>
+struct Wide<kFloat32> {
+  using E = uint32_t;
+  static constexpr int kVecs = 2;
+  __device__ static uint32_t to_f32(E x) { return x; }
+  __device__ static E from_f32(float f) { return bitcast<uint32_t>(f); }
+  __device__ static E get(const vec16* x, int e) { return x[e >> 2].w[e & 3]; }
+  __device__ static void put(vec16* x, int e, E v) { x[e >> 2].w[e & 3] = v; }
+};
+
+template <>
+struct Wide<kFloat64> {
+  using E = uint64_t;
+  static constexpr int kVecs = 4;
+  // round to f32 first (RNE), as the host conversion does
+  __device__ static uint32_t to_f32(E x) { return bitcast<uint32_t>((float)bitcast<double>(x)); }
+  __device__ static E from_f32(float f) { return bitcast<uint64_t>((double)f); }
+  __device__ static E get(const vec16* x, int e) {
+    return ((uint64_t)x[e >> 1].w[(e & 1) * 2 + 1] << 32) | x[e >> 1].w[(e & 1) * 2];
+  }
+  __device__ static void put(vec16* x, int e, E v) {
+    x[e >> 1].w[(e & 1) * 2] = (uint32_t)v;
+    x[e >> 1].w[(e & 1) * 2 + 1] = (uint32_t)(v >> 32);
+  }
+};
+
+template <>
+struct Wide<kBFloat16> {
+  using E = uint16_t;
+  static constexpr int kVecs = 1;
+  __device__ static uint32_t to_f32(E x) { return (uint32_t)x << 16; }  // exact
+  __device__ static E from_f32(float f) { return (E)f32_to_bf16_rne(bitcast<uint32_t>(f)); }
+  __device__ static E get(const vec16* x, int e) {
+    return (E)(x[0].w[e >> 1] >> ((e & 1) * 16));
+  }
+  __device__ static void put(vec16* x, int e, E v) {
+    if (e & 1) x[0].w[e >> 1] |= (uint32_t)v << 16;
+    else x[0].w[e >> 1] = v;
+  }
+};
+
+struct CastArgs {
+  const unsigned char* src;
+  unsigned char* dst;
+  uint64_t n_elems;
+  uint64_t head;        // elements before the vector range
+  uint64_t nunits;      // 8-element units in the vector range
+  uint64_t tail_begin;  // head + 8 * nunits
+  uint64_t grid;        // launched workgroups
+  int divisor;          // decompress: >= 1
+  int aligned;          // both operands element-aligned
+};
+
+template <class W>
+__device__ __forceinline__ uint16_t compress_elem(typename W::E x) {
+  return (uint16_t)f2h_bits(W::to_f32(x));
+}
+
+// div: the quotient is rounded to fp16 BEFORE it is widened.
+template <class W>
+__device__ __forceinline__ typename W::E decompress_elem(uint16_t h, bool div, float fd) {
+  if (div) h = (uint16_t)f2h_bits(bitcast<uint32_t>((float)bitcast<_Float16>(h) / fd));
+  return W::from_f32((float)bitcast<_Float16>(h));
+}
+
+template <class W>
+__device__ __forceinline__ vec16 compress_unit(const vec16* x) {
+  vec16 o;
+#pragma unroll
+  for (int e = 0; e < 8; e += 2)
+    o.w[e >> 1] = (uint32_t)compress_elem<W>(W::get(x, e)) |
+                  ((uint32_t)compress_elem<W>(W::get(x, e + 1)) << 16);
+  return o;
+}
+
+template <class W>
+__device__ __forceinline__ void decompress_unit(const vec16& h, bool div, float fd, vec16* o) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    W::put(o, e, decompress_elem<W>((uint16_t)(h.w[e >> 1] >> ((e & 1) * 16)), div, fd));
+}
+
+// Full tile: units [0, kBlock * U) of the tile whose first bytes are h0 (fp16
+// side) and w0 (wide side); lane handles units lane + j * kBlock.  One buffer
+// descriptor per operand sized to the tile, 32-bit lane offsets.
+template <class W, bool COMPRESS, int U, int POL>
+__device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigned char* dst,
+                                               bool div, float fd, int lane) {
+  constexpr int kAux = 2;                            // loads: nt
+  constexpr int kStAux = POL == kPolWt ? 16 : kAux;  // stores: sc1 (write-through) or nt
+  constexpr int KV = W::kVecs;
+  constexpr int kHBytes = kBlock * U * 16, kWBytes = kHBytes * KV;
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(src), 0,
+                                                    COMPRESS ? kWBytes : kHBytes, 0x00020000);
+  const auto rd = __builtin_amdgcn_make_buffer_rsrc(dst, 0, COMPRESS ? kHBytes : kWBytes,
+                                                    0x00020000);
+  if constexpr (COMPRESS && KV > 1) {
+    // The mirror image of the decompress below: load instruction v reads the
+    // wave's input vectors v * 64 + l (1 KiB contiguous), each lane rounds the
+    // elements it loaded, and lane l collects the fp16 values of ITS unit
+    // (vectors l * KV + s, all in load l / (64 / KV)) from the lanes that
+    // hold them.  Every element is rounded exactly once, by the lane that
+    // loaded it.
+    constexpr int EPV = 8 / KV, DW = EPV / 2;  // elements / fp16 dwords per input vector
+    const int l = lane & 63, wave0 = lane & ~63;
+    vec16 x[U][KV];
+#pragma unroll
+    for (int j = 0; j < U; ++j)
+#pragma unroll
+      for (int v = 0; v < KV; ++v)
+        x[j][v] = bitcast<vec16>(__builtin_amdgcn_raw_buffer_load_b128(
+            rs, ((j * kBlock + wave0) * KV + v * 64 + l) * 16, 0, kAux));
+    const int vi = l / (64 / KV);
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      uint32_t c[KV][DW];
+#pragma unroll
+      for (int v = 0; v < KV; ++v)
+#pragma unroll
+        for (int k = 0; k < DW; ++k)
+          c[v][k] = (uint32_t)compress_elem<W>(W::get(&x[j][v], 2 * k)) |
+                    ((uint32_t)compress_elem<W>(W::get(&x[j][v], 2 * k + 1)) << 16);
+      vec16 o;
+#pragma unroll
+      for (int s = 0; s < KV; ++s) {
+        const int from = ((l * KV + s) & 63) * 4;
+#pragma unroll
+        for (int k = 0; k < DW; ++k) {
+          uint32_t r = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)c[0][k]);
+#pragma unroll
+          for (int v = 1; v < KV; ++v) {
+            const uint32_t t = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)c[v][k]);
+            r = vi == v ? t : r;
+          }
+          o.w[s * DW + k] = r;
+        }
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(o), rd, (j * kBlock + lane) * 16, 0,
+                                             kStAux);
+    }
+  } else if constexpr (COMPRESS) {
+    vec16 x[U][KV];
+#pragma unroll
+    for (int j = 0; j < U; ++j)
+#pragma unroll
+      for (int v = 0; v < KV; ++v)
+        x[j][v] = bitcast<vec16>(__builtin_amdgcn_raw_buffer_load_b128(
+            rs, ((j * kBlock + lane) * KV + v) * 16, 0, kAux));
+#pragma unroll
+    for (int j = 0; j < U; ++j)
+      __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(compress_unit<W>(x[j])), rd,
+                                             (j * kBlock + lane) * 16, 0, kStAux);
+  } else {
+    vec16 h[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j)
+      h[j] = bitcast<vec16>(
+          __builtin_amdgcn_raw_buffer_load_b128(rs, (j * kBlock + lane) * 16, 0, kAux));
+    if constexpr (KV > 1) {
+      // Lane-private stores would leave each store instruction writing 16 of
+      // every 16 * KV bytes — a fraction of each 128-B line per instruction,
+      // measured 0.53 (no divide) to 0.59 of the roofline for f32, so it was
+      // the store pattern and not the divide that bound it; re-dealt, 0.75
+      // with or without the divide.  So the wave's 64 units are
+      // re-dealt before the widen: store instruction v writes the wave's
+      // output vectors v * 64 + l, 1 KiB contiguous, and lane l fetches the
+      // fp16 values of that vector from the lane that loaded them (unit
+      // (v * 64 + l) / KV, its sub-vector (v * 64 + l) % KV) by ds_bpermute —
+      // the halves travel, 2 bytes an element, and each element is still
+      // divided and widened exactly once.  Full tiles only: every lane is
+      // active.
+      constexpr int EPV = 8 / KV;  // elements per output vector
+      const int l = lane & 63, wave0 = lane & ~63;
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+#pragma unroll
+        for (int v = 0; v < KV; ++v) {
+          const int g = v * 64 + l;
+          const int from = (g / KV) * 4, sub = g % KV;
+          uint32_t w[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            w[k] = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)h[j].w[k]);
+          // the EPV halves of sub-vector `sub`: dwords [sub * EPV / 2, + EPV / 2)
+          uint32_t d[EPV / 2];
+#pragma unroll
+          for (int k = 0; k < EPV / 2; ++k) {
+            d[k] = w[k];
+#pragma unroll
+            for (int s = 1; s < KV; ++s) d[k] = sub == s ? w[s * (EPV / 2) + k] : d[k];
+          }
+          vec16 o{};
+#pragma unroll
+          for (int e = 0; e < EPV; ++e)  // e < EPV: all within the one vector
+            W::put(&o, e, decompress_elem<W>((uint16_t)(d[e >> 1] >> ((e & 1) * 16)), div, fd));
+          __builtin_amdgcn_raw_buffer_store_b128(
+              bitcast<u4>(o), rd, ((j * kBlock + wave0) * KV + g) * 16, 0, kStAux);
+        }
+      }
+      return;
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      vec16 o[KV];
+      decompress_unit<W>(h[j], div, fd, o);
+#pragma unroll
+      for (int v = 0; v < KV; ++v)
+        __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(o[v]), rd,
+                                               ((j * kBlock + lane) * KV + v) * 16, 0, kStAux);
+    }
+  }
+}
+
+// The partial last tile: units [u0, nunits) of the vector range (src / dst
+// already advanced to the range); a unit past nunits is neither read nor
+// written.
+template <class W, bool COMPRESS, int U>
+__device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsigned char* dst,
+                                                  uint64_t u0, uint64_t nunits, bool div,
+                                                  float fd, int lane) {
+  constexpr int KV = W::kVecs;
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+    const uint64_t u = u0 + (uint64_t)j * kBlock + lane;
+    if (u >= nunits) continue;
+    if constexpr (COMPRESS) {
+      vec16 x[KV];
+#pragma unroll
+      for (int v = 0; v < KV; ++v) x[v] = ld16<true>(src + (u * KV + v) * 16);
+      st16<true>(dst + u * 16, compress_unit<W>(x));
+    } else {
+      vec16 o[KV];
+      decompress_unit<W>(ld16<true>(src + u * 16), div, fd, o);
+#pragma unroll
+      for (int v = 0; v < KV; ++v) st16<true>(dst + (u * KV + v) * 16, o[v]);
+    }
+  }
+}
+
+// Elements [0, head) and [tail_begin, n_elems), one per thread.
+template <class W, bool COMPRESS>
+__device__ __forceinline__ void cast_elements(const CastArgs& a, bool div, float fd, uint64_t t,
+                                              uint64_t stride) {
+  using E = typename W::E;
+  const bool al = a.aligned != 0;
+  const uint64_t n_scalar = a.head + (a.n_elems - a.tail_begin);
+  for (uint64_t s = t; s < n_scalar; s += stride) {
+    const uint64_t e = s < a.head ? s : a.tail_begin + (s - a.head);
+    if constexpr (COMPRESS)
+      st_e<uint16_t>(a.dst + e * 2, compress_elem<W>(ld_e<E>(a.src + e * sizeof(E), al)), al);
+    else
+      st_e<E>(a.dst + e * sizeof(E), decompress_elem<W>(ld_e<uint16_t>(a.src + e * 2, al), div, fd),
+              al);
+  }
+}
+
+}  // namespace bpsr

@@ -351,6 +351,53 @@ hipError_t launch_compress_fp16(void* dst, const void* src, size_t nelem, int sr
                                 const Tuning& tu, hipStream_t s);
 hipError_t launch_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
                                   int divisor, const Tuning& tu, hipStream_t s);
+// How one cast is cut: h = the fp16 operand, w = the wide one (es bytes per
+// element).  The vector range starts at the first element index where both
+// are 16-byte aligned: the fp16 side every 8 elements from hh, the wide side
+// every 16 / es from hw, so they meet iff hh = hw mod (16 / es), first at hh.
+// Without a vector range (never co-aligned, element-misaligned, or shorter
+// than head + one unit) head and nunits are 0 and every element goes through
+// the element path.
+struct CastCut {
+  uint64_t head;    // elements before the vector range
+  uint64_t nunits;  // 8-element units in the vector range
+  int aligned;      // both operands element-aligned
+};
+inline CastCut cast_cut(const void* h, const void* w, size_t nelem, int es) {
+  const uintptr_t ph = (uintptr_t)h, pw = (uintptr_t)w;
+  CastCut c{0, 0, (ph % 2 == 0 && pw % (uintptr_t)es == 0) ? 1 : 0};
+  if (!c.aligned) return c;
+  const uint64_t hh = ((16 - (ph & 15)) & 15) / 2;
+  const uint64_t hw = ((16 - (pw & 15)) & 15) / (uint64_t)es;
+  if (hh % (16 / (uint64_t)es) != hw || hh >= nelem) return c;
+  c.nunits = (nelem - hh) / 8;
+  if (c.nunits) c.head = hh;
+  return c;
+}
+
+// Cast plan (byteps_reduce_cast_plan_*, bpsr_cast_table.cpp builds the table,
+// bpsr_k_cast_plan.hip runs it): one record per workgroup.  Both pointers are
+// already advanced to the record's first element, so a workgroup reaches its
+// data after one scalar round trip, and the same table serves both
+// directions.  Guarded tiles and element ranges come first (latency-bound,
+// they start with the launch), the full tiles follow in address order.
+struct CastRec {
+  unsigned char* wide;
+  unsigned char* half;
+  uint32_t kind;     // kTileFull, kTilePartial or kTileElem
+  uint32_t count;    // partial: valid 8-element units; element: elements
+  uint32_t aligned;  // element: both operands element-aligned
+  uint32_t pad;
+};
+static_assert(sizeof(CastRec) == 32, "CastRec layout");
+// Elements of one element record: a long range that never co-aligns is split
+// so that it does not serialise on one workgroup (build_table's kElemPart).
+constexpr uint64_t kCastElemPart = (uint64_t)kBlock * 16;
+// `u`: the tile size the table was cut for (kBlock * u units per tile);
+// `out_bytes`: what the whole launch writes (store policy).
+hipError_t launch_cast_plan(bool compress, const CastRec* table, uint32_t nrecords,
+                            int wide_dtype, int divisor, int u, uint64_t out_bytes,
+                            const Tuning& tu, hipStream_t s);
 
 // Pull copy service (bpsr_copy_service.cpp, kernel in bpsr_k_service.hip):
 // a persistent kernel of a few workgroups serving copies that host threads

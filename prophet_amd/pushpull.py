@@ -33,6 +33,11 @@ per-context fp16 staging buffer, pushes and pulls that, and one fused launch
 widens the result into the output — dividing the fp16 value first when
 ``average=True``, as the reference's callback does on the compressed tensor
 (byteps/torch/ops.cc:77-81).  DESIGN.md §11 has the stream-ordering argument.
+
+``push_pull_iteration`` casts all its compressed device tensors at once: one
+cast-plan launch before the first push and one after the last pull
+(``FP16Compressor.compress_many_into`` / ``decompress_many_into``), with the
+plans kept on the worker between iterations.
 """
 from __future__ import annotations
 
@@ -41,7 +46,7 @@ from dataclasses import dataclass, field
 
 from .buckets import (DEFAULT_PARTITION_BYTES, cantor_command, depair_command,
                       local_size_from_env, partition_bound, partition_bytes_from_env)
-from .compression import Compression
+from .compression import CastPlanCache, Compression
 from .dtypes import DType, elem_size
 
 K_DEFAULT_PUSH_PULL = 0     # RequestType::kDefaultPushPull (common.h:68-71)
@@ -112,6 +117,10 @@ class Worker:
         self._pool = None
         self._handles: dict[int, tuple] = {}
         self._next_handle = 0
+        # push_pull_iteration's cast plans: found again by every segment's
+        # (tensor address, staging address, element count), at most 4, the
+        # least recently used destroyed first
+        self._cast_plans = CastPlanCache(4)
 
     # ------------------------------------------------------------ declare/init
     def declare(self, name: str) -> int:
@@ -250,6 +259,7 @@ class Worker:
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
+        self._cast_plans.close()
 
     def broadcast(self, name: str, tensor, root_rank: int, output=None):
         """Broadcast as BytePS does it (byteps/torch/__init__.py:264-272: "push +
@@ -266,14 +276,25 @@ class Worker:
         self.push_pull(name, src, output=out)
         return out
 
-    def push_pull_iteration(self, tensors: dict, scheduler=None) -> list:
+    def push_pull_iteration(self, tensors: dict, scheduler=None, average: bool = False) -> list:
         """One training iteration: every declared tensor, gradients arriving in
         backward order (highest declared index first).  With a Prophet
         ``scheduler`` (``ProphetPushQueue``) the partitions are pushed in the
         groups it releases; then every partition is pulled back in place.
+        Compressed contexts are cast together: one ``compress_many_into``
+        before the first push and one ``decompress_many_into`` after the last
+        pull (device tensors: one cast-plan launch each, the plans cached on
+        this worker).  ``average``: divide by the number of workers as
+        ``push_pull(average=True)`` does — compressed contexts on the fp16
+        value inside the decompress, the others in place afterwards.
         Returns the release groups as lists of (declared key, partition)."""
         from .prophet import PushTask, release_groups
         ctxs = [self.contexts[n] for n in self._declared if n in tensors]
+        divisor = 1
+        if average:
+            divisor = getattr(self.frontend, "size", None)
+            if not divisor:
+                raise ValueError("average: the frontend does not know the worker count")
         arrivals = []
         for c in sorted(ctxs, key=lambda c: -c.declared_key):
             for i, (key, off, ln) in enumerate(c.parts):
@@ -285,22 +306,33 @@ class Worker:
             groups = release_groups(scheduler, arrivals)
         by_key = {c.declared_key: c for c in ctxs}
         # what travels: the tensor itself, or a compressed context's staging
-        # buffer (cast once, before its first partition is pushed)
-        wire = {}
+        # buffer — all of them cast before the first partition is pushed
+        wire = {c.name: tensors[c.name] if c.compressor is None else c.staging for c in ctxs}
+        casts = {}
+        for c in ctxs:
+            if c.compressor is not None:
+                casts.setdefault(c.compressor, []).append(c)
+        for comp, cs in casts.items():
+            comp.compress_many_into([c.staging for c in cs],
+                                    [_contiguous(tensors[c.name]) for c in cs],
+                                    plans=self._cast_plans)
         for g in groups:
             for t in g:
                 c = by_key[t.grad]
-                if c.name not in wire:
-                    wire[c.name] = tensors[c.name] if c.compressor is None else \
-                        c.compressor.compress_into(c.staging, _contiguous(tensors[c.name]))
                 key, off, ln = c.parts[t.part]
                 self.frontend.push(cantor_command(K_DEFAULT_PUSH_PULL, c.dtype), key, self.rank,
                                    _slice(wire[c.name], off, ln), ln)
         for c in ctxs:
             for key, off, ln in c.parts:
                 self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
-            if c.compressor is not None:
-                c.compressor.decompress_into(_contiguous(tensors[c.name]), wire[c.name])
+        for comp, cs in casts.items():
+            comp.decompress_many_into([_contiguous(tensors[c.name]) for c in cs],
+                                      [c.staging for c in cs], divisor,
+                                      plans=self._cast_plans)
+        if average:
+            for c in ctxs:
+                if c.compressor is None:
+                    _divide_(tensors[c.name], divisor)
         return [[(t.grad, t.part) for t in g] for g in groups]
 
 

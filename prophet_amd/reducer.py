@@ -57,6 +57,8 @@ EXPORTS = (
     "byteps_reduce_blockq_join", "byteps_reduce_blockq_release_stream",
     "byteps_reduce_blockq_queue_ids",
     "byteps_reduce_compress_fp16", "byteps_reduce_decompress_fp16",
+    "byteps_reduce_cast_plan_create", "byteps_reduce_cast_plan_compress",
+    "byteps_reduce_cast_plan_decompress", "byteps_reduce_cast_plan_destroy",
 )
 
 
@@ -64,6 +66,11 @@ class BucketDesc(ctypes.Structure):
     """``byteps_bucket_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("dst", _vp), ("srcs", _vp * MAX_SRCS), ("len", _sz), ("n", _int),
                 ("reserved", _int)]
+
+
+class CastDesc(ctypes.Structure):
+    """``byteps_cast_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("wide", _vp), ("half", _vp), ("nelem", _sz)]
 
 
 class ReduceError(RuntimeError):
@@ -120,6 +127,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_blockq_queue_ids.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64), _int]
     L.byteps_reduce_compress_fp16.argtypes = [_vp, _vp, _sz, _int, _vp]
     L.byteps_reduce_decompress_fp16.argtypes = [_vp, _vp, _sz, _int, _int, _vp]
+    L.byteps_reduce_cast_plan_create.argtypes = [ctypes.POINTER(CastDesc), _int, _int,
+                                                 ctypes.POINTER(_vp)]
+    L.byteps_reduce_cast_plan_compress.argtypes = [_vp, _vp]
+    L.byteps_reduce_cast_plan_decompress.argtypes = [_vp, _int, _vp]
+    L.byteps_reduce_cast_plan_destroy.argtypes = [_vp]
     _LIB = L
     return L
 
@@ -223,6 +235,13 @@ class GpuReducer:
                                                       _stream_of(dst, stream)))
         return 0
 
+    def cast_plan(self, segments: Sequence[tuple], wide_dtype: int) -> "CastPlan":
+        """A whole iteration's fp16 casts as one launch each way
+        (byteps_reduce_cast_plan_*): ``segments`` are ``(wide, half, nelem)``
+        triples of tensors or raw pointers, all of ``wide_dtype``.  The plan
+        keeps the tensors it was built from alive."""
+        return CastPlan(self.lib, segments, wide_dtype)
+
     def sum_n(self, dst, srcs: Sequence, length: int, dtype: int,
               mode: int = MODE_REFERENCE, stream=None) -> int:
         """Left fold ``dst = ((srcs[0] + srcs[1]) + ...)`` in the given order."""
@@ -304,6 +323,56 @@ class Plan:
         if self.handle:
             self.lib.byteps_reduce_plan_destroy(self.handle)
             self.handle = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CastPlan:
+    """``byteps_reduce_cast_plan``: the segments' tile table resident on the
+    device.  ``compress`` writes every fp16 side from its wide side,
+    ``decompress`` the other way (dividing by ``divisor`` on the fp16 value),
+    each as ONE launch; per segment the bytes are those of
+    ``GpuReducer.compress_fp16`` / ``decompress_fp16``.
+
+    Tensor operands are bounds-checked before the library sees them, and the
+    plan holds a reference to every one: the device table carries raw
+    addresses, and a write through a freed one would be a GPU fault rather
+    than an exception.  Raw pointers carry no size and stay the caller's."""
+
+    def __init__(self, lib, segments, wide_dtype):
+        self.lib = lib
+        self.handle = _vp()
+        segments = [tuple(s) for s in segments]
+        for wide, half, nelem in segments:
+            _fits_cast(nelem, half, wide, wide_dtype)
+        self._keep = segments         # keep the tensors alive
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (CastDesc * max(1, len(segments)))()
+        for i, (wide, half, nelem) in enumerate(segments):
+            descs[i].wide = _ptr(wide)
+            descs[i].half = _ptr(half)
+            descs[i].nelem = int(nelem)
+        _check(lib.byteps_reduce_cast_plan_create(descs, len(segments), int(wide_dtype),
+                                                  ctypes.byref(self.handle)))
+
+    def compress(self, stream=None) -> None:
+        _check(self.lib.byteps_reduce_cast_plan_compress(self.handle,
+                                                         _stream_of(self.first, stream)))
+
+    def decompress(self, divisor: int = 1, stream=None) -> None:
+        _check(self.lib.byteps_reduce_cast_plan_decompress(self.handle, int(divisor),
+                                                           _stream_of(self.first, stream)))
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.byteps_reduce_cast_plan_destroy(self.handle)
+            self.handle = _vp()
+        self._keep = []
 
     def __del__(self):
         try:

@@ -27,6 +27,26 @@ with Compression.fp16, host-resident (where the casts are the host's) and
 device-resident.  One process; every GPU step runs under a
 time limit of its own (a step that overruns ends the process with status
 124).  Prints one JSON line.
+
+``--iteration`` measures what a whole iteration's casts cost instead: the 165
+entries of tools/cfg3_resnet50_table.txt (ResNet-50's gradients as fp16 byte
+ranges), each one f32 segment of len / 2 elements at its own offset in one
+arena per side, compressed and then decompressed (divisor 8) by
+
+  loop    one compress_fp16_out and one decompress_fp16_out per segment — what
+          push_pull_iteration queued before cast plans: 2 x 165 launches;
+  plan    one cast-plan launch each way (byteps_reduce_cast_plan_*);
+  single  for scale, one one-tensor call each way over the same element count.
+
+Same method: rotated buffer sets, candidates alternated round by round,
+medians of rounds, device events.  Then one 64 Mi-element segment, each
+direction on its own, as a plan launch and as the one-tensor call.  Gates:
+
+  iteration  plan faster than loop by more than the larger of the two spreads;
+  big        per direction, the plan's median within the larger of the two
+             spreads of the one-tensor call's.
+
+One JSON line, also appended to ``--out`` when given.
 """
 import argparse
 import json
@@ -73,7 +93,13 @@ def main() -> int:
     p.add_argument("--e2e-elems", type=int, default=16 << 20)
     p.add_argument("--e2e-iters", type=int, default=6)
     p.add_argument("--no-e2e", action="store_true")
+    p.add_argument("--iteration", action="store_true",
+                   help="a whole iteration's casts: per-segment loop, cast plan, one tensor")
+    p.add_argument("--table", default=os.path.join(ROOT, "tools", "cfg3_resnet50_table.txt"))
+    p.add_argument("--out", default=None, help="append the JSON line to this file too")
     args = p.parse_args()
+    if args.iteration:
+        return iteration_mode(args)
 
     import torch
 
@@ -176,6 +202,166 @@ def main() -> int:
             out["push_pull_device_2workers_1gpu"] = end_to_end(args.e2e_elems, args.e2e_iters,
                                                                "device")
     print(json.dumps(out), flush=True)
+    return 0 if all(gates.values()) else 1
+
+
+def read_table(path: str):
+    """(offset, len) in fp16 bytes of every entry of a cfg3 table file."""
+    with open(path) as f:
+        total, count, _ = (int(v) for v in f.readline().split())
+        rows = [tuple(int(v) for v in line.split()) for line in f if line.strip()]
+    rows = rows[:count]
+    if len(rows) != count or max(o + ln for o, ln in rows) > total:
+        raise ValueError(f"{path}: {len(rows)} entries, header says {count} in {total} bytes")
+    return total, rows
+
+
+def timed_rounds(torch, cands, nsets, args):
+    """Per candidate the per-call device-event times of every timed round:
+    ``cands[name] = (fn(set index), calls per round)``."""
+    times = {k: [] for k in cands}
+    for r in range(args.warmup + args.rounds):
+        for name, (fn, inner) in cands.items():
+            with step(f"{name} round {r}", 60):
+                e0 = torch.cuda.Event(enable_timing=True)
+                e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for i in range(inner):
+                    fn(i % nsets)
+                e1.record()
+                e1.synchronize()
+                if r >= args.warmup:
+                    times[name].append(e0.elapsed_time(e1) / inner)
+    return {name: {"ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5),
+                   "max_ms": round(max(ts), 5), "spread_ms": round(max(ts) - min(ts), 5),
+                   "calls_per_round": cands[name][1]}
+            for name, ts in times.items()}
+
+
+def iteration_mode(args) -> int:
+    import torch
+
+    from prophet_amd import torch_ops  # noqa: F401  (registers torch.ops.bpsr.*)
+    from prophet_amd.dtypes import DType
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    total_bytes, rows = read_table(args.table)
+    dev = torch.device("cuda:0")
+    comp, decomp = torch.ops.bpsr.compress_fp16_out, torch.ops.bpsr.decompress_fp16_out
+    with step("setup", 120):
+        red = GpuReducer(device=0)
+        g = torch.Generator(device=dev).manual_seed(2)
+        nelem = sum(ln // 2 for _, ln in rows)
+        sets = []
+        for _ in range(args.sets):
+            wide = torch.randn(total_bytes // 2, device=dev, generator=g) * 64
+            half = torch.empty(total_bytes // 2, dtype=torch.float16, device=dev)
+            segs = [(wide[o // 2:(o + ln) // 2], half[o // 2:(o + ln) // 2]) for o, ln in rows]
+            sets.append({"wide": wide, "half": half, "segs": segs,
+                         "plan": red.cast_plan([(w, h, w.numel()) for w, h in segs],
+                                               DType.FLOAT32),
+                         "one_w": wide[:nelem], "one_h": half[:nelem]})
+        torch.cuda.synchronize()
+
+    with step("check", 120):
+        s = sets[0]
+        s["plan"].compress()
+        ref = torch.full_like(s["half"], 7.0)
+        for w, h in s["segs"]:
+            o = h.data_ptr() - s["half"].data_ptr()
+            comp(ref[o // 2:o // 2 + h.numel()], w)
+        same_c = all(bool(torch.equal(h.view(torch.int16),
+                                      ref[(h.data_ptr() - s["half"].data_ptr()) // 2:][:h.numel()]
+                                      .view(torch.int16))) for _, h in s["segs"])
+        s["plan"].decompress(8)
+        same_d = True
+        for w, h in s["segs"]:
+            one = torch.empty_like(w)
+            decomp(one, h, 8)
+            same_d = same_d and bool(torch.equal(w.view(torch.int32), one.view(torch.int32)))
+        del ref
+        torch.cuda.synchronize()
+
+    def loop(k):
+        for w, h in sets[k]["segs"]:
+            comp(h, w)
+        for w, h in sets[k]["segs"]:
+            decomp(w, h, 8)
+
+    def plan(k):
+        sets[k]["plan"].compress()
+        sets[k]["plan"].decompress(8)
+
+    def single(k):
+        red.compress_fp16(sets[k]["one_h"], sets[k]["one_w"], nelem, DType.FLOAT32)
+        red.decompress_fp16(sets[k]["one_w"], sets[k]["one_h"], nelem, DType.FLOAT32, 8)
+
+    few = max(1, args.inner // 8)            # 330 launches a call: fewer calls a round
+    res = timed_rounds(torch, {"loop": (loop, few), "plan": (plan, args.inner),
+                               "single": (single, args.inner)}, len(sets), args)
+    sp = max(res["loop"]["spread_ms"], res["plan"]["spread_ms"])
+    gates = {"iteration_plan_beats_loop": res["loop"]["ms"] - res["plan"]["ms"] > sp}
+    out = {"tool": "bench_compress", "mode": "iteration", "table": os.path.basename(args.table),
+           "segments": len(rows), "elems": nelem, "bytes_moved_per_iteration": 12 * nelem,
+           "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0),
+           "bit_equal_to_per_segment_calls": {"compress": same_c, "decompress_div8": same_d},
+           "iteration": res, "iteration_gate_spread_ms": sp,
+           "loop_over_plan": round(res["loop"]["ms"] / res["plan"]["ms"], 2),
+           "plan_over_single": round(res["plan"]["ms"] / res["single"]["ms"], 3)}
+    for s in sets:
+        s["plan"].close()
+    del sets
+    torch.cuda.empty_cache()
+
+    n = args.elems
+    with step("setup, one segment", 120):
+        big = []
+        for _ in range(args.sets):
+            x = torch.randn(n, device=dev, generator=g) * 64
+            h = x.to(torch.float16)
+            big.append({"x": x, "h": h, "h_out": torch.empty_like(h),
+                        "pc": red.cast_plan([(x, torch.empty_like(h), n)], DType.FLOAT32)})
+        for b in big:                        # decompress plans write x from the fixed h
+            b["pd"] = red.cast_plan([(torch.empty_like(b["x"]), b["h"], n)], DType.FLOAT32)
+            b["out"] = b["pd"]._keep[0][0]
+            b["pc_h"] = b["pc"]._keep[0][1]
+        torch.cuda.synchronize()
+    bres = timed_rounds(torch, {
+        "plan_compress": (lambda k: big[k]["pc"].compress(), args.inner),
+        "single_compress": (lambda k: red.compress_fp16(big[k]["h_out"], big[k]["x"], n,
+                                                        DType.FLOAT32), args.inner),
+        "plan_decompress": (lambda k: big[k]["pd"].decompress(8), args.inner),
+        "single_decompress": (lambda k: red.decompress_fp16(big[k]["out"], big[k]["h"], n,
+                                                            DType.FLOAT32, 8), args.inner),
+    }, len(big), args)
+    for v in bres.values():
+        v["roofline_frac"] = round(6 * n / (v["ms"] * 1e-3) / HBM_BYTES_PER_S, 4)
+    big_sp = {}
+    for d in ("compress", "decompress"):
+        sp = max(bres[f"plan_{d}"]["spread_ms"], bres[f"single_{d}"]["spread_ms"])
+        big_sp[d] = sp
+        gates[f"big_plan_{d}_within_spread_of_single"] = \
+            bres[f"plan_{d}"]["ms"] - bres[f"single_{d}"]["ms"] <= sp
+    with step("check, one segment", 60):
+        b = big[0]
+        b["pc"].compress()
+        out["bit_equal_one_segment"] = bool(torch.equal(b["pc_h"].view(torch.int16),
+                                                        b["h"].view(torch.int16)))
+        torch.cuda.synchronize()
+    out.update({"big_elems": n, "big": bres, "big_gate_spread_ms": big_sp, "gates": gates})
+    for b in big:
+        b["pc"].close()
+        b["pd"].close()
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
     return 0 if all(gates.values()) else 1
 
 
