@@ -59,7 +59,9 @@ extern "C" {
  * 5: byteps_server_create_sized (a caller states its config's size)
  *    additive, still 5: byteps_reduce_compress_fp16 / _decompress_fp16
  *    additive, still 5: byteps_reduce_cast_plan_create / _compress /
- *                       _decompress / _destroy (byteps_cast_desc) */
+ *                       _decompress / _destroy (byteps_cast_desc)
+ *    additive, still 5: byteps_reduce_compress_to / _decompress_from /
+ *                       byteps_reduce_cast_plan_create_wire (bf16 wire) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -315,6 +317,29 @@ int byteps_reduce_compress_fp16(void* dst, const void* src, size_t nelem, int sr
 int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
                                   int divisor, void* stream);
 
+/* The same casts with the 2-byte wire format named: `wire_dtype` FLOAT16 is
+ * exactly the two calls above (same kernels, same checks), BFLOAT16 is bf16
+ * gradient compression, whose T is FLOAT32, FLOAT64 or FLOAT16.  Any other
+ * pair, T equal to the wire format included, is EDTYPE.  bf16 has f32's
+ * exponent range, so a sum of workers' gradients does not overflow where
+ * fp16's does at 65,520.
+ *   compress:    dst[i] = bf16(src[i]), round to nearest even on f32's upper
+ *                16 bits: f32 subnormals are kept, not flushed (0x00008001 ->
+ *                0x0001), finite values from 0x7f7f8000 up give +-inf, signed
+ *                zeros are kept; f64 is rounded to f32 first (f32 subnormals
+ *                produced), f16 is widened exactly.  A NaN gives a NaN
+ *                (payload unspecified).
+ *   decompress:  dst[i] = T(src[i]) for divisor 1 (exact for f32 / f64; RNE
+ *                with overflow to +-inf and fp16 subnormals for f16); for
+ *                divisor d > 1, dst[i] = T(bf16(float(src[i]) / float(d))),
+ *                the quotient rounded to bf16 BEFORE it is widened.  The
+ *                quotient may be an f32 subnormal; it is not flushed.
+ * Lengths, overlap, divisor and nelem == 0 as above. */
+int byteps_reduce_compress_to(void* dst, const void* src, size_t nelem, int src_dtype,
+                              int wire_dtype, void* stream);
+int byteps_reduce_decompress_from(void* dst, const void* src, size_t nelem, int dst_dtype,
+                                  int wire_dtype, int divisor, void* stream);
+
 /* Cast plan: the casts of a whole push_pull iteration — every gradient to
  * fp16 before the pushes, every result back after the pulls — as ONE launch
  * each way.  Segment i pairs `nelem` elements of the plan's wide type
@@ -332,6 +357,12 @@ int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int 
  *            segment is valid and its launches succeed without a launch.
  *   compress / decompress: asynchronous on `stream`; divisor < 1 is EARGS.
  *   destroy: frees the table with hipFree, which waits for launches in flight.
+ *   create_wire: a plan whose 2-byte side is `wire_dtype`: FLOAT16 is create
+ *            itself, BFLOAT16 pairs FLOAT32, FLOAT64 or FLOAT16 at `wide` with
+ *            bf16 values at `half`, per segment the bytes of
+ *            byteps_reduce_compress_to / _decompress_from; other pairs are
+ *            EDTYPE.  A plan remembers its wire format: compress, decompress
+ *            and destroy serve both kinds.
  * The plan holds raw pointers: the caller keeps the segments' memory alive
  * and in place for as long as the plan is launched. */
 typedef struct byteps_cast_desc {
@@ -342,6 +373,8 @@ typedef struct byteps_cast_desc {
 typedef struct byteps_reduce_cast_plan byteps_reduce_cast_plan;
 int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
                                    byteps_reduce_cast_plan** out);
+int byteps_reduce_cast_plan_create_wire(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
+                                        int wire_dtype, byteps_reduce_cast_plan** out);
 int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* plan, void* stream);
 int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* plan, int divisor, void* stream);
 int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* plan);

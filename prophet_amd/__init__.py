@@ -9,8 +9,9 @@ Python surface:
   * :class:`prophet_amd.reducer.GpuReducer` — mirrors ``CpuReducer``
     (``sum``/``copy``/``GetDataType``) on device pointers, through the C ABI.
   * :mod:`prophet_amd.torch_ops` — the same ops as ``torch.ops.bpsr.*``.
-  * :mod:`prophet_amd.compression` — ``Compression.none`` / ``Compression.fp16``
-    for ``pushpull.Worker.init_tensor`` (fused HIP casts on device tensors).
+  * :mod:`prophet_amd.compression` — ``Compression.none`` / ``Compression.fp16`` /
+    ``Compression.bf16`` for ``pushpull.Worker.init_tensor`` (fused HIP casts
+    on device tensors).
   * :mod:`prophet_amd.dtypes` — the reference DataType ids.
   * :mod:`prophet_amd.synth` — deterministic synthetic buckets.
 """

@@ -7,6 +7,15 @@ compressor casts floating tensors to fp16 before the push and back after the
 pull; everything else (integers, tensors that are fp16 already) passes
 through as the same object.
 
+``Compression.bf16`` is the build's own second wire format with the same
+surface: floating tensors travel as bf16, which has f32's exponent range — a
+sum of gradients that fp16 turns into inf (from 65,520 up) stays finite.  The
+casts are pinned to torch's CPU casts (round to nearest even, f32 subnormals
+kept, f64 through f32); on the device they are
+``torch.ops.bpsr.compress_bf16*`` / ``decompress_bf16_out``
+(``prophet_amd/csrc/bpsr_k_cast_bf16.hip``).  A numpy bf16 buffer is raw
+``uint16`` bits (``dtypes.numpy_dtype``).
+
 Where the casts run:
 
 * CUDA tensors: the HIP kernels of ``prophet_amd/csrc/bpsr_k_cast.hip``
@@ -57,6 +66,15 @@ def _is_half(x) -> bool:
     return x.dtype == np.float16
 
 
+def _is_bf16(x) -> bool:
+    """torch bf16; numpy has no bf16 (its raw uint16 bits are integers and are
+    not compressed either)."""
+    if _is_torch(x):
+        import torch
+        return x.dtype == torch.bfloat16
+    return False
+
+
 def _on_device(x) -> bool:
     return _is_torch(x) and x.device.type == "cuda"
 
@@ -67,10 +85,16 @@ def _as_host_tensor(x):
     return x if _is_torch(x) else torch.from_numpy(x)
 
 
+def _as_host_bf16(x):
+    """The same for a bf16 buffer: a numpy one carries raw uint16 bits."""
+    import torch
+    return x if _is_torch(x) else torch.from_numpy(x.view(np.int16)).view(torch.bfloat16)
+
+
 class CastPlanCache:
     """The cast plans of the last few iterations, least recently used out
-    first.  A plan is found again by its wide dtype and the (wide address,
-    fp16 address, element count) of every segment, so a tensor that moved
+    first.  A plan is found again by its wide dtype, its wire dtype and the
+    (wide address, 2-byte address, element count) of every segment, so a tensor that moved
     misses and gets a new plan.  A cached plan holds its tensors: their
     memory cannot be freed, so no other tensor can appear at a cached
     address while the plan that names it is alive."""
@@ -83,16 +107,17 @@ class CastPlanCache:
     def __len__(self) -> int:
         return len(self._plans)
 
-    def get(self, wide_dtype: int, pairs):
+    def get(self, wide_dtype: int, pairs, wire_dtype: int = 2):
         """The plan over ``pairs`` of flat ``(wide, half)`` device tensors on
-        the current device, built on a miss."""
-        key = (int(wide_dtype),) + tuple(
+        the current device, built on a miss.  ``wire_dtype``: the dtype of
+        the ``half`` side (``DType.FLOAT16`` unless named)."""
+        key = (int(wide_dtype), int(wire_dtype)) + tuple(
             (int(w.data_ptr()), int(h.data_ptr()), int(w.numel())) for w, h in pairs)
         plan = self._plans.get(key)
         if plan is not None:
             self._plans.move_to_end(key)
             return plan
-        plan = _new_plan(wide_dtype, pairs)
+        plan = _new_plan(wide_dtype, pairs, wire_dtype)
         self.built += 1
         self._plans[key] = plan
         while len(self._plans) > self.capacity:
@@ -106,36 +131,38 @@ class CastPlanCache:
             plan.close()
 
 
-def _new_plan(wide_dtype: int, pairs):
+def _new_plan(wide_dtype: int, pairs, wire_dtype: int = 2):
     from .torch_ops import _red
-    return _red().cast_plan([(w, h, int(w.numel())) for w, h in pairs], wide_dtype)
+    return _red().cast_plan([(w, h, int(w.numel())) for w, h in pairs], wide_dtype, wire_dtype)
 
 
-def _cast_many(pairs, compress: bool, divisor: int, plans) -> None:
-    """``pairs`` of ``(wide, half)`` tensors or arrays: the device ones as one
-    plan launch per (device, wide dtype), the host ones one by one."""
+def _cast_many(comp, pairs, compress: bool, divisor: int, plans) -> None:
+    """``pairs`` of ``(wide, half)`` tensors or arrays cast by compressor
+    ``comp``: the device ones as one plan launch per (device, wide dtype, wire
+    dtype), the host ones one by one."""
     if int(divisor) < 1:
         raise ValueError(f"divisor {divisor} < 1")
     groups: dict = {}
     for wide, half in pairs:
         if not _on_device(wide) and not _on_device(half):
             if compress:
-                FP16Compressor.compress_into(half, wide)
+                comp.compress_into(half, wide)
             else:
-                FP16Compressor.decompress_into(wide, half, divisor)
+                comp.decompress_into(wide, half, divisor)
             continue
         from .torch_ops import _check_cast
-        _check_cast(half, wide)
-        groups.setdefault((wide.device, wide.dtype), []).append(
+        wire = comp.wire_torch_dtype()
+        _check_cast(half, wide, wire)
+        groups.setdefault((wide.device, wide.dtype, wire), []).append(
             (wide.reshape(-1), half.reshape(-1)))
     if not groups:
         return
     import torch
     from .dtypes import from_torch
-    for (device, dtype), segs in groups.items():
+    for (device, dtype, wire), segs in groups.items():
         with torch.cuda.device(device):
-            plan = plans.get(from_torch(dtype), segs) if plans is not None \
-                else _new_plan(from_torch(dtype), segs)
+            plan = plans.get(from_torch(dtype), segs, from_torch(wire)) if plans is not None \
+                else _new_plan(from_torch(dtype), segs, from_torch(wire))
             stream = torch.cuda.current_stream(device)
             try:
                 if compress:
@@ -176,42 +203,75 @@ class NoneCompressor(Compressor):
         return tensor
 
 
-class FP16Compressor(Compressor):
-    """Floating tensors travel as fp16."""
+class _CastCompressor(Compressor):
+    """Floating tensors travel in a 2-byte wire format; the two formats differ
+    in the names below only.  Tensors already of the wire dtype, and integers,
+    pass through as the same object."""
 
-    @staticmethod
-    def compresses(tensor) -> bool:
-        return _is_floating(tensor) and not _is_half(tensor)
+    WIRE_DTYPE = None                     # DType id a compressed context carries
+    WIRE = None                           # "float16" / "bfloat16": the torch dtype's name
+    NAME = None                           # "fp16" / "bf16": torch.ops.bpsr.compress_<NAME>*
+    NUMPY = None                          # numpy dtype of a host wire buffer
 
-    @staticmethod
-    def compress(tensor):
+    @classmethod
+    def wire_torch_dtype(cls):
+        import torch
+        return getattr(torch, cls.WIRE)
+
+    @classmethod
+    def wire_like(cls, x):
+        """A wire-format buffer of x's kind, device and element count (a
+        compressed context's staging buffer)."""
+        if _is_torch(x):
+            import torch
+            return torch.empty(x.numel(), dtype=cls.wire_torch_dtype(), device=x.device)
+        return np.empty(x.size, dtype=cls.NUMPY)
+
+    @classmethod
+    def _host_wire(cls, x):
+        """A CPU torch view, of the wire dtype, of a host wire buffer."""
+        return _as_host_tensor(x)
+
+    @classmethod
+    def _is_wire(cls, x) -> bool:
+        raise NotImplementedError
+
+    @classmethod
+    def compresses(cls, tensor) -> bool:
+        return _is_floating(tensor) and not cls._is_wire(tensor)
+
+    @classmethod
+    def compress(cls, tensor):
         ctx = tensor.dtype
-        if not FP16Compressor.compresses(tensor):
+        if not cls.compresses(tensor):
             return tensor, ctx
         import torch
         if _on_device(tensor):
             from . import torch_ops  # noqa: F401  (registers torch.ops.bpsr.*)
             with torch.cuda.device(tensor.device):
-                return torch.ops.bpsr.compress_fp16(tensor.contiguous()), ctx
+                return getattr(torch.ops.bpsr, f"compress_{cls.NAME}")(tensor.contiguous()), ctx
         if _is_torch(tensor):
-            return tensor.to(torch.float16), ctx
-        return torch.from_numpy(np.ascontiguousarray(tensor)).to(torch.float16).numpy(), ctx
+            return tensor.to(cls.wire_torch_dtype()), ctx
+        out = np.empty(tensor.shape, dtype=cls.NUMPY)
+        return cls.compress_into(out, np.ascontiguousarray(tensor)), ctx
 
-    @staticmethod
-    def compress_into(out, tensor):
-        """``compress`` into a preallocated fp16 buffer of the same kind and
+    @classmethod
+    def compress_into(cls, out, tensor):
+        """``compress`` into a preallocated wire buffer of the same kind and
         element count (push_pull's staging buffer); returns ``out``."""
         import torch
         if _on_device(tensor):
             from . import torch_ops  # noqa: F401
             with torch.cuda.device(tensor.device):
-                torch.ops.bpsr.compress_fp16_out(out.reshape(-1), tensor.reshape(-1))
+                getattr(torch.ops.bpsr, f"compress_{cls.NAME}_out")(out.reshape(-1),
+                                                                    tensor.reshape(-1))
             return out
-        _as_host_tensor(out).reshape(-1).copy_(_as_host_tensor(tensor).reshape(-1))
+        cls._host_wire(out).reshape(-1).copy_(_as_host_tensor(tensor).reshape(-1))
         return out
 
-    @staticmethod
-    def decompress(tensor, ctx):
+    @classmethod
+    def decompress(cls, tensor, ctx):
+        """``ctx``: the dtype ``compress`` returned."""
         if ctx is None or tensor.dtype == ctx:
             return tensor
         if _is_torch(tensor):
@@ -219,16 +279,16 @@ class FP16Compressor(Compressor):
                 return tensor
             import torch
             out = torch.empty(tensor.shape, dtype=ctx, device=tensor.device)
-            return FP16Compressor.decompress_into(out, tensor.contiguous())
+            return cls.decompress_into(out, tensor.contiguous())
         if not np.issubdtype(ctx, np.floating):
             return tensor
         out = np.empty(tensor.shape, dtype=ctx)
-        return FP16Compressor.decompress_into(out, np.ascontiguousarray(tensor))
+        return cls.decompress_into(out, np.ascontiguousarray(tensor))
 
-    @staticmethod
-    def decompress_into(out, compressed, divisor: int = 1):
-        """``out[i] = T(compressed[i])``, or ``T(fp16(compressed[i] / divisor))``
-        for a divisor above 1 (divide on the fp16 value, then widen), in one
+    @classmethod
+    def decompress_into(cls, out, compressed, divisor: int = 1):
+        """``out[i] = T(compressed[i])``, or ``T(wire(compressed[i] / divisor))``
+        for a divisor above 1 (divide on the 2-byte value, then widen), in one
         pass; returns ``out``."""
         if int(divisor) < 1:
             raise ValueError(f"divisor {divisor} < 1")
@@ -236,37 +296,62 @@ class FP16Compressor(Compressor):
         if _on_device(out):
             from . import torch_ops  # noqa: F401
             with torch.cuda.device(out.device):
-                torch.ops.bpsr.decompress_fp16_out(out.reshape(-1), compressed.reshape(-1),
-                                                   int(divisor))
+                getattr(torch.ops.bpsr, f"decompress_{cls.NAME}_out")(
+                    out.reshape(-1), compressed.reshape(-1), int(divisor))
             return out
-        q = _as_host_tensor(compressed).reshape(-1)
+        q = cls._host_wire(compressed).reshape(-1)
         if int(divisor) > 1:
             q = q.clone().div_(int(divisor))
         _as_host_tensor(out).reshape(-1).copy_(q)
         return out
 
-
-    @staticmethod
-    def compress_many_into(outs, tensors, plans: CastPlanCache | None = None):
+    @classmethod
+    def compress_many_into(cls, outs, tensors, plans: CastPlanCache | None = None):
         """``compress_into(outs[i], tensors[i])`` for every i, the device
         tensors as one cast-plan launch per (device, dtype); returns ``outs``.
         ``plans`` keeps the plans for the next call over the same tensors;
         without it a plan is built and destroyed here."""
         if len(outs) != len(tensors):
             raise ValueError("compress_many_into: as many outputs as tensors")
-        _cast_many(list(zip(tensors, outs)), True, 1, plans)
+        _cast_many(cls, list(zip(tensors, outs)), True, 1, plans)
         return outs
 
-    @staticmethod
-    def decompress_many_into(outs, compressed, divisor: int = 1,
+    @classmethod
+    def decompress_many_into(cls, outs, compressed, divisor: int = 1,
                              plans: CastPlanCache | None = None):
         """``decompress_into(outs[i], compressed[i], divisor)`` for every i,
         the device tensors as one cast-plan launch per (device, dtype);
         returns ``outs``."""
         if len(outs) != len(compressed):
             raise ValueError("decompress_many_into: as many outputs as compressed tensors")
-        _cast_many(list(zip(outs, compressed)), False, divisor, plans)
+        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans)
         return outs
+
+
+class FP16Compressor(_CastCompressor):
+    """Floating tensors travel as fp16."""
+
+    WIRE_DTYPE, WIRE, NAME, NUMPY = 2, "float16", "fp16", np.float16    # DType.FLOAT16
+
+    @classmethod
+    def _is_wire(cls, x) -> bool:
+        return _is_half(x)
+
+
+class BF16Compressor(_CastCompressor):
+    """Floating tensors travel as bf16 (f32's exponent range: a sum that fp16
+    turns into inf stays finite).  A numpy wire buffer holds raw uint16 bits,
+    so for numpy ``decompress`` goes by ``ctx`` alone."""
+
+    WIRE_DTYPE, WIRE, NAME, NUMPY = 11, "bfloat16", "bf16", np.uint16   # DType.BFLOAT16
+
+    @classmethod
+    def _is_wire(cls, x) -> bool:
+        return _is_bf16(x)
+
+    @classmethod
+    def _host_wire(cls, x):
+        return _as_host_bf16(x)
 
 
 class Compression:
@@ -274,6 +359,8 @@ class Compression:
 
     none = NoneCompressor
     fp16 = FP16Compressor
+    bf16 = BF16Compressor
 
 
-__all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "Compression", "CastPlanCache"]
+__all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor", "Compression",
+           "CastPlanCache"]

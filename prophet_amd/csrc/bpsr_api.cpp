@@ -437,11 +437,25 @@ int byteps_reduce_copy(void* dst, const void* src, size_t len, void* stream) {
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "copy kernel launch");
 }
 
-// Shared checks of the two fp16 casts, all before any HIP call: h = the fp16
-// operand, w = the wide one.  Returns 1 when there is nothing to do.
-static int cast_check(const void* h, const void* w, size_t nelem, int dtype, int divisor) {
-  if (dtype != kFloat32 && dtype != kFloat64 && dtype != kBFloat16)
-    return fail(BYTEPS_REDUCE_EDTYPE, "fp16 compression of data type %d", dtype);
+// Which wide dtypes travel in which 2-byte wire format: fp16 carries f32, f64
+// and bf16, bf16 carries f32, f64 and fp16.  Anything else, wide == wire
+// included, is the dtype error.
+static int cast_pair_check(int dtype, int wire) {
+  if (wire != kFloat16 && wire != kBFloat16)
+    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire);
+  const int other = wire == kFloat16 ? kBFloat16 : kFloat16;
+  if (dtype != kFloat32 && dtype != kFloat64 && dtype != other)
+    return fail(BYTEPS_REDUCE_EDTYPE, "%s compression of data type %d",
+                wire == kFloat16 ? "fp16" : "bf16", dtype);
+  return BYTEPS_REDUCE_OK;
+}
+
+// Shared checks of the casts, all before any HIP call: h = the 2-byte operand
+// (of `wire`), w = the wide one.  Returns 1 when there is nothing to do.
+static int cast_check(const void* h, const void* w, size_t nelem, int dtype, int divisor,
+                      int wire = kFloat16) {
+  const int pair = cast_pair_check(dtype, wire);
+  if (pair != BYTEPS_REDUCE_OK) return pair;
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
   if (nelem == 0) return 1;
   if (!h || !w) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
@@ -472,23 +486,47 @@ int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int 
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "decompress kernel launch");
 }
 
+int byteps_reduce_compress_to(void* dst, const void* src, size_t nelem, int src_dtype,
+                              int wire_dtype, void* stream) {
+  if (wire_dtype == kFloat16)
+    return byteps_reduce_compress_fp16(dst, src, nelem, src_dtype, stream);
+  const int rc = cast_check(dst, src, nelem, src_dtype, 1, wire_dtype);
+  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
+  hipError_t e = launch_compress_bf16(dst, src, nelem, src_dtype, tuning(), to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "compress kernel launch");
+}
+
+int byteps_reduce_decompress_from(void* dst, const void* src, size_t nelem, int dst_dtype,
+                                  int wire_dtype, int divisor, void* stream) {
+  if (wire_dtype == kFloat16)
+    return byteps_reduce_decompress_fp16(dst, src, nelem, dst_dtype, divisor, stream);
+  const int rc = cast_check(src, dst, nelem, dst_dtype, divisor, wire_dtype);
+  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
+  hipError_t e = launch_decompress_bf16(dst, src, nelem, dst_dtype, divisor, tuning(),
+                                        to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "decompress kernel launch");
+}
+
 struct byteps_reduce_cast_plan {
   int device;
   int dtype;
+  int wire;
   void* dev_table;
   CastTableInfo ti;
 };
 
-int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
-                                   byteps_reduce_cast_plan** out) {
-  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
-  *out = nullptr;
+// table_dtype: what the table builder is given.  It cuts by element size alone
+// and knows the fp16 wire's three wide types, so a wide fp16 (bf16 wire) is
+// cut as its 2-byte peer.
+static int cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int wire,
+                            int table_dtype, byteps_reduce_cast_plan** out) {
   std::vector<char> host;
   CastTableInfo ti;
-  const int rc = build_cast_table(segs, nsegs, wide_dtype, tuning().copy_vpt, host, &ti);
+  const int rc = build_cast_table(segs, nsegs, table_dtype, tuning().copy_vpt, host, &ti);
   if (rc) return rc;
   auto* p = new byteps_reduce_cast_plan();
   p->dtype = wide_dtype;
+  p->wire = wire;
   p->ti = ti;
   p->dev_table = nullptr;
   hipError_t e = hipGetDevice(&p->device);
@@ -506,15 +544,33 @@ int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int 
   return BYTEPS_REDUCE_OK;
 }
 
+int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
+                                   byteps_reduce_cast_plan** out) {
+  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
+  *out = nullptr;
+  return cast_plan_create(segs, nsegs, wide_dtype, kFloat16, wide_dtype, out);
+}
+
+int byteps_reduce_cast_plan_create_wire(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
+                                        int wire_dtype, byteps_reduce_cast_plan** out) {
+  if (wire_dtype == kFloat16) return byteps_reduce_cast_plan_create(segs, nsegs, wide_dtype, out);
+  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
+  *out = nullptr;
+  const int pair = cast_pair_check(wide_dtype, wire_dtype);
+  if (pair != BYTEPS_REDUCE_OK) return pair;
+  return cast_plan_create(segs, nsegs, wide_dtype, wire_dtype,
+                          wide_dtype == kFloat16 ? kBFloat16 : wide_dtype, out);
+}
+
 static int cast_plan_launch(byteps_reduce_cast_plan* p, bool compress, int divisor,
                             void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
   if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
   const uint64_t out_bytes = p->ti.nelem * (compress ? 2 : (uint64_t)elem_size(p->dtype));
-  hipError_t e = launch_cast_plan(compress, static_cast<const CastRec*>(p->dev_table),
-                                  p->ti.records, p->dtype, divisor, p->ti.u, out_bytes, tuning(),
-                                  to_stream(stream));
+  const auto launch = p->wire == kBFloat16 ? launch_cast_plan_bf16 : launch_cast_plan;
+  hipError_t e = launch(compress, static_cast<const CastRec*>(p->dev_table), p->ti.records,
+                        p->dtype, divisor, p->ti.u, out_bytes, tuning(), to_stream(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan kernel launch");
 }
 

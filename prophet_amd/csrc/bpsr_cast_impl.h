@@ -1,8 +1,10 @@
-// Per-tile device code of the fp16 casts, shared by the single cast
-// (bpsr_k_cast.hip) and the cast plan (bpsr_k_cast_plan.hip): the wide-side
-// element types, one element's arithmetic, the full tile, the guarded partial
-// tile and the element loop.  What the arithmetic is and why the full tile
-// re-deals its lanes: bpsr_k_cast.hip.
+// Per-tile device code of the 2-byte casts, shared by the single cast
+// (bpsr_cast_single.h; bpsr_k_cast.hip for the fp16 wire, bpsr_k_cast_bf16.hip
+// for the bf16 wire) and the cast plan (bpsr_cast_plan.h; bpsr_k_cast_plan.hip,
+// bpsr_k_cast_plan_bf16.hip): the wide-side element types, the narrow (wire)
+// side's two formats, one element's arithmetic, the full tile, the guarded
+// partial tile and the element loop.  What the arithmetic is and why the full
+// tile re-deals its lanes: bpsr_k_cast.hip, bpsr_k_cast_bf16.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -58,6 +60,38 @@ struct Wide<kBFloat16> {
   }
 };
 
+// Wide fp16 under the bf16 wire: widened exactly, narrowed as the fp16 wire's
+// compress narrows (RNE, overflow to inf, fp16 subnormals produced).
+template <>
+struct Wide<kFloat16> {
+  using E = uint16_t;
+  static constexpr int kVecs = 1;
+  __device__ static uint32_t to_f32(E x) { return bitcast<uint32_t>((float)bitcast<_Float16>(x)); }
+  __device__ static E from_f32(float f) { return (E)f2h_bits(bitcast<uint32_t>(f)); }
+  __device__ static E get(const vec16* x, int e) {
+    return (E)(x[0].w[e >> 1] >> ((e & 1) * 16));
+  }
+  // ORs into the upper half: elements are put in order, the even one first
+  __device__ static void put(vec16* x, int e, E v) {
+    if (e & 1) x[0].w[e >> 1] |= (uint32_t)v << 16;
+    else x[0].w[e >> 1] = v;
+  }
+};
+
+// Narrow (wire) side: f32 bits to the 2-byte format, round to nearest even,
+// and the exact way back.
+struct NarrowF16 {
+  __device__ static uint16_t from_f32(uint32_t x) { return (uint16_t)f2h_bits(x); }
+  __device__ static float to_float(uint16_t h) { return (float)bitcast<_Float16>(h); }
+};
+
+// bf16: the integer RNE of the folds (f32_to_bf16_rne) — it rounds the bits,
+// so f32 subnormals are kept whatever the wave's denormal mode — and a shift.
+struct NarrowBF16 {
+  __device__ static uint16_t from_f32(uint32_t x) { return (uint16_t)f32_to_bf16_rne(x); }
+  __device__ static float to_float(uint16_t b) { return bitcast<float>((uint32_t)b << 16); }
+};
+
 struct CastArgs {
   const unsigned char* src;
   unsigned char* dst;
@@ -70,39 +104,41 @@ struct CastArgs {
   int aligned;          // both operands element-aligned
 };
 
-template <class W>
+template <class W, class N>
 __device__ __forceinline__ uint16_t compress_elem(typename W::E x) {
-  return (uint16_t)f2h_bits(W::to_f32(x));
+  return N::from_f32(W::to_f32(x));
 }
 
-// div: the quotient is rounded to fp16 BEFORE it is widened.
-template <class W>
+// div: the quotient is rounded to the narrow format BEFORE it is widened.  A
+// bf16 quotient can be an f32 subnormal (fp16's never is): the divide is the
+// plain IEEE `/` with f32 denormals on, the build's default.
+template <class W, class N>
 __device__ __forceinline__ typename W::E decompress_elem(uint16_t h, bool div, float fd) {
-  if (div) h = (uint16_t)f2h_bits(bitcast<uint32_t>((float)bitcast<_Float16>(h) / fd));
-  return W::from_f32((float)bitcast<_Float16>(h));
+  if (div) h = N::from_f32(bitcast<uint32_t>(N::to_float(h) / fd));
+  return W::from_f32(N::to_float(h));
 }
 
-template <class W>
+template <class W, class N>
 __device__ __forceinline__ vec16 compress_unit(const vec16* x) {
   vec16 o;
 #pragma unroll
   for (int e = 0; e < 8; e += 2)
-    o.w[e >> 1] = (uint32_t)compress_elem<W>(W::get(x, e)) |
-                  ((uint32_t)compress_elem<W>(W::get(x, e + 1)) << 16);
+    o.w[e >> 1] = (uint32_t)compress_elem<W, N>(W::get(x, e)) |
+                  ((uint32_t)compress_elem<W, N>(W::get(x, e + 1)) << 16);
   return o;
 }
 
-template <class W>
+template <class W, class N>
 __device__ __forceinline__ void decompress_unit(const vec16& h, bool div, float fd, vec16* o) {
 #pragma unroll
   for (int e = 0; e < 8; ++e)
-    W::put(o, e, decompress_elem<W>((uint16_t)(h.w[e >> 1] >> ((e & 1) * 16)), div, fd));
+    W::put(o, e, decompress_elem<W, N>((uint16_t)(h.w[e >> 1] >> ((e & 1) * 16)), div, fd));
 }
 
-// Full tile: units [0, kBlock * U) of the tile whose first bytes are h0 (fp16
+// Full tile: units [0, kBlock * U) of the tile whose first bytes are h0 (narrow
 // side) and w0 (wide side); lane handles units lane + j * kBlock.  One buffer
 // descriptor per operand sized to the tile, 32-bit lane offsets.
-template <class W, bool COMPRESS, int U, int POL>
+template <class W, class N, bool COMPRESS, int U, int POL>
 __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigned char* dst,
                                                bool div, float fd, int lane) {
   constexpr int kAux = 2;                            // loads: nt
@@ -138,8 +174,8 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
       for (int v = 0; v < KV; ++v)
 #pragma unroll
         for (int k = 0; k < DW; ++k)
-          c[v][k] = (uint32_t)compress_elem<W>(W::get(&x[j][v], 2 * k)) |
-                    ((uint32_t)compress_elem<W>(W::get(&x[j][v], 2 * k + 1)) << 16);
+          c[v][k] = (uint32_t)compress_elem<W, N>(W::get(&x[j][v], 2 * k)) |
+                    ((uint32_t)compress_elem<W, N>(W::get(&x[j][v], 2 * k + 1)) << 16);
       vec16 o;
 #pragma unroll
       for (int s = 0; s < KV; ++s) {
@@ -168,7 +204,7 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
             rs, ((j * kBlock + lane) * KV + v) * 16, 0, kAux));
 #pragma unroll
     for (int j = 0; j < U; ++j)
-      __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(compress_unit<W>(x[j])), rd,
+      __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(compress_unit<W, N>(x[j])), rd,
                                              (j * kBlock + lane) * 16, 0, kStAux);
   } else {
     vec16 h[U];
@@ -212,7 +248,7 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
           vec16 o{};
 #pragma unroll
           for (int e = 0; e < EPV; ++e)  // e < EPV: all within the one vector
-            W::put(&o, e, decompress_elem<W>((uint16_t)(d[e >> 1] >> ((e & 1) * 16)), div, fd));
+            W::put(&o, e, decompress_elem<W, N>((uint16_t)(d[e >> 1] >> ((e & 1) * 16)), div, fd));
           __builtin_amdgcn_raw_buffer_store_b128(
               bitcast<u4>(o), rd, ((j * kBlock + wave0) * KV + g) * 16, 0, kStAux);
         }
@@ -222,7 +258,7 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
 #pragma unroll
     for (int j = 0; j < U; ++j) {
       vec16 o[KV];
-      decompress_unit<W>(h[j], div, fd, o);
+      decompress_unit<W, N>(h[j], div, fd, o);
 #pragma unroll
       for (int v = 0; v < KV; ++v)
         __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(o[v]), rd,
@@ -234,7 +270,7 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
 // The partial last tile: units [u0, nunits) of the vector range (src / dst
 // already advanced to the range); a unit past nunits is neither read nor
 // written.
-template <class W, bool COMPRESS, int U>
+template <class W, class N, bool COMPRESS, int U>
 __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsigned char* dst,
                                                   uint64_t u0, uint64_t nunits, bool div,
                                                   float fd, int lane) {
@@ -247,10 +283,10 @@ __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsi
       vec16 x[KV];
 #pragma unroll
       for (int v = 0; v < KV; ++v) x[v] = ld16<true>(src + (u * KV + v) * 16);
-      st16<true>(dst + u * 16, compress_unit<W>(x));
+      st16<true>(dst + u * 16, compress_unit<W, N>(x));
     } else {
       vec16 o[KV];
-      decompress_unit<W>(ld16<true>(src + u * 16), div, fd, o);
+      decompress_unit<W, N>(ld16<true>(src + u * 16), div, fd, o);
 #pragma unroll
       for (int v = 0; v < KV; ++v) st16<true>(dst + (u * KV + v) * 16, o[v]);
     }
@@ -258,7 +294,7 @@ __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsi
 }
 
 // Elements [0, head) and [tail_begin, n_elems), one per thread.
-template <class W, bool COMPRESS>
+template <class W, class N, bool COMPRESS>
 __device__ __forceinline__ void cast_elements(const CastArgs& a, bool div, float fd, uint64_t t,
                                               uint64_t stride) {
   using E = typename W::E;
@@ -267,10 +303,10 @@ __device__ __forceinline__ void cast_elements(const CastArgs& a, bool div, float
   for (uint64_t s = t; s < n_scalar; s += stride) {
     const uint64_t e = s < a.head ? s : a.tail_begin + (s - a.head);
     if constexpr (COMPRESS)
-      st_e<uint16_t>(a.dst + e * 2, compress_elem<W>(ld_e<E>(a.src + e * sizeof(E), al)), al);
+      st_e<uint16_t>(a.dst + e * 2, compress_elem<W, N>(ld_e<E>(a.src + e * sizeof(E), al)), al);
     else
-      st_e<E>(a.dst + e * sizeof(E), decompress_elem<W>(ld_e<uint16_t>(a.src + e * 2, al), div, fd),
-              al);
+      st_e<E>(a.dst + e * sizeof(E),
+              decompress_elem<W, N>(ld_e<uint16_t>(a.src + e * 2, al), div, fd), al);
   }
 }
 

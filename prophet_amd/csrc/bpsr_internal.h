@@ -351,7 +351,13 @@ hipError_t launch_compress_fp16(void* dst, const void* src, size_t nelem, int sr
                                 const Tuning& tu, hipStream_t s);
 hipError_t launch_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
                                   int divisor, const Tuning& tu, hipStream_t s);
-// How one cast is cut: h = the fp16 operand, w = the wide one (es bytes per
+// The same over the bf16 wire (bpsr_k_cast_bf16.hip): f32, f64 or fp16 to bf16
+// and back (byteps_reduce_compress_to / _decompress_from with BFLOAT16).
+hipError_t launch_compress_bf16(void* dst, const void* src, size_t nelem, int src_dtype,
+                                const Tuning& tu, hipStream_t s);
+hipError_t launch_decompress_bf16(void* dst, const void* src, size_t nelem, int dst_dtype,
+                                  int divisor, const Tuning& tu, hipStream_t s);
+// How one cast is cut: h = the 2-byte (wire) operand, w = the wide one (es bytes per
 // element).  The vector range starts at the first element index where both
 // are 16-byte aligned: the fp16 side every 8 elements from hh, the wide side
 // every 16 / es from hw, so they meet iff hh = hw mod (16 / es), first at hh.
@@ -398,6 +404,11 @@ constexpr uint64_t kCastElemPart = (uint64_t)kBlock * 16;
 hipError_t launch_cast_plan(bool compress, const CastRec* table, uint32_t nrecords,
                             int wide_dtype, int divisor, int u, uint64_t out_bytes,
                             const Tuning& tu, hipStream_t s);
+// A plan whose wire format is bf16 (bpsr_k_cast_plan_bf16.hip); the table is
+// the same.
+hipError_t launch_cast_plan_bf16(bool compress, const CastRec* table, uint32_t nrecords,
+                                 int wide_dtype, int divisor, int u, uint64_t out_bytes,
+                                 const Tuning& tu, hipStream_t s);
 
 // Pull copy service (bpsr_copy_service.cpp, kernel in bpsr_k_service.hip):
 // a persistent kernel of a few workgroups serving copies that host threads

@@ -26,7 +26,8 @@ byteps/server/server.cc, with an in-process transport:
 Buffers may be host (numpy / CPU tensors) or device tensors; every byte of
 arithmetic is the server's HIP fold.
 
-``init_tensor(..., compression=Compression.fp16)`` makes a floating tensor
+``init_tensor(..., compression=Compression.fp16)`` (or ``Compression.bf16``,
+read bf16 for fp16 below) makes a floating tensor
 travel as fp16 (byteps/torch/__init__.py:133-170): the context's size, dtype
 and partitions are those of the COMPRESSED tensor, every call casts into a
 per-context fp16 staging buffer, pushes and pulls that, and one fused launch
@@ -81,9 +82,9 @@ class Context:
     key_list: list = field(default_factory=list)
     parts: list = field(default_factory=list)      # (key, offset, len) in bytes
     initialized: bool = False
-    # fp16 compression (None: the tensor travels as it is): the compressor,
-    # the caller's dtype and byte size, and the fp16 buffer that is pushed
-    # from and pulled into; size / dtype / parts above are the compressed ones
+    # compression (None: the tensor travels as it is): the compressor, the
+    # caller's dtype and byte size, and the buffer of the compressor's wire
+    # dtype (fp16 or bf16) that is pushed from and pulled into; size / dtype / parts above are the compressed ones
     compressor: object = None
     orig_dtype: int = 0
     orig_size: int = 0
@@ -143,9 +144,10 @@ class Worker:
         """InitTensor (operations.cc:219-316): keys, then one blocking init push
         per partition (every worker's init push of a key returns only once all
         of them arrived: the global barrier).  ``compression``: how the tensor
-        travels from now on (``Compression.fp16``: floating tensors as fp16 —
-        the keys, partitions and request dtype are the compressed tensor's;
-        integers and fp16 tensors pass through as with ``Compression.none``)."""
+        travels from now on (``Compression.fp16``: floating tensors as fp16,
+        ``Compression.bf16``: as bf16 — the keys, partitions and request dtype
+        are the compressed tensor's; integers and tensors already of the wire
+        dtype pass through as with ``Compression.none``)."""
         self.declare(name)
         ctx = self.contexts[name]
         size = _nbytes(data)
@@ -157,9 +159,9 @@ class Worker:
             if compression.compresses(data):
                 ctx.compressor = compression
                 ctx.orig_dtype, ctx.orig_size = int(dtype), size
-                ctx.staging = _half_like(data)
+                ctx.staging = compression.wire_like(data)
                 data = compression.compress_into(ctx.staging, data)
-                size, dtype = _nbytes(data), DType.FLOAT16
+                size, dtype = _nbytes(data), DType(compression.WIRE_DTYPE)
             ctx.size, ctx.dtype = size, int(dtype)
             start = ctx.declared_key << 16
             ctx.parts = [(start + i, off, ln) for i, (off, ln) in enumerate(self._partition(size))]
@@ -205,9 +207,10 @@ class Worker:
 
     def _push_pull_compressed(self, ctx: Context, tensor, output, order, average: bool) -> None:
         """push_pull of a context initialised with a compressor: cast into the
-        context's staging buffer, push and pull THAT (its partitions, FLOAT16
-        in the request word), then one launch widens it into the output,
-        dividing the fp16 value by the worker count first for ``average``.
+        context's staging buffer, push and pull THAT (its partitions, the wire
+        dtype — FLOAT16 or BFLOAT16 — in the request word), then one launch
+        widens it into the output, dividing the 2-byte value by the worker
+        count first for ``average``.
         Device tensors: both casts run on the calling thread's current stream;
         the output is complete in that stream's order."""
         out = tensor if output is None else output
@@ -285,7 +288,7 @@ class Worker:
         before the first push and one ``decompress_many_into`` after the last
         pull (device tensors: one cast-plan launch each, the plans cached on
         this worker).  ``average``: divide by the number of workers as
-        ``push_pull(average=True)`` does — compressed contexts on the fp16
+        ``push_pull(average=True)`` does — compressed contexts on the 2-byte
         value inside the decompress, the others in place afterwards.
         Returns the release groups as lists of (declared key, partition)."""
         from .prophet import PushTask, release_groups
@@ -353,16 +356,6 @@ def _divide_(x, size: int) -> None:
     if not np.issubdtype(x.dtype, np.floating):
         raise ValueError("average needs a floating dtype")
     x /= size
-
-
-def _half_like(x):
-    """An fp16 buffer of x's kind, device and element count (a compressed
-    context's staging buffer, allocated once at init_tensor)."""
-    if hasattr(x, "data_ptr"):                             # torch
-        import torch
-        return torch.empty(x.numel(), dtype=torch.float16, device=x.device)
-    import numpy as np
-    return np.empty(x.size, dtype=np.float16)
 
 
 def _contiguous(x):

@@ -10,6 +10,7 @@ reference                              here
 ``sum(dst, src1, src2, len, dtype)``   ``GpuReducer.sum3`` -> ``byteps_reduce_sum3``
 ``copy(dst, src, len)``                ``GpuReducer.copy`` -> ``byteps_reduce_copy``
 ``FP16Compressor`` (torch front end)   ``GpuReducer.compress_fp16`` / ``decompress_fp16``
+``BF16Compressor`` (build extension)   ``GpuReducer.compress`` / ``decompress`` with a wire dtype
 ``GetDataType(int)``                   ``GpuReducer.GetDataType``
 server fold, server.cc:216-273         ``GpuReducer.sum_n`` -> ``byteps_reduce_sum_n``
 one Prophet block                      ``GpuReducer.sum_batched``
@@ -59,6 +60,8 @@ EXPORTS = (
     "byteps_reduce_compress_fp16", "byteps_reduce_decompress_fp16",
     "byteps_reduce_cast_plan_create", "byteps_reduce_cast_plan_compress",
     "byteps_reduce_cast_plan_decompress", "byteps_reduce_cast_plan_destroy",
+    "byteps_reduce_compress_to", "byteps_reduce_decompress_from",
+    "byteps_reduce_cast_plan_create_wire",
 )
 
 
@@ -132,6 +135,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_cast_plan_compress.argtypes = [_vp, _vp]
     L.byteps_reduce_cast_plan_decompress.argtypes = [_vp, _int, _vp]
     L.byteps_reduce_cast_plan_destroy.argtypes = [_vp]
+    L.byteps_reduce_compress_to.argtypes = [_vp, _vp, _sz, _int, _int, _vp]
+    L.byteps_reduce_decompress_from.argtypes = [_vp, _vp, _sz, _int, _int, _int, _vp]
+    L.byteps_reduce_cast_plan_create_wire.argtypes = [ctypes.POINTER(CastDesc), _int, _int, _int,
+                                                      ctypes.POINTER(_vp)]
     _LIB = L
     return L
 
@@ -163,13 +170,14 @@ def _fits(length: int, *xs) -> None:
 
 
 def _fits_cast(nelem: int, half, wide, wide_dtype: int) -> None:
-    """``_fits`` for the fp16 casts, whose operands differ in element size:
-    ``half`` holds ``nelem`` fp16 values, ``wide`` as many of ``wide_dtype``
-    (an unsupported dtype is left to the library: EDTYPE)."""
+    """``_fits`` for the casts, whose operands differ in element size:
+    ``half`` holds ``nelem`` 2-byte values (fp16 or bf16, the wire format),
+    ``wide`` as many of ``wide_dtype`` (an unsupported dtype is left to the
+    library: EDTYPE)."""
     if int(nelem) < 0:
         raise ValueError(f"negative element count {nelem}")
     _fits(int(nelem) * 2, half)
-    if int(wide_dtype) in (DType.FLOAT32, DType.FLOAT64, DType.BFLOAT16):
+    if int(wide_dtype) in (DType.FLOAT32, DType.FLOAT64, DType.BFLOAT16, DType.FLOAT16):
         _fits(int(nelem) * elem_size(wide_dtype), wide)
 
 
@@ -235,12 +243,37 @@ class GpuReducer:
                                                       _stream_of(dst, stream)))
         return 0
 
-    def cast_plan(self, segments: Sequence[tuple], wide_dtype: int) -> "CastPlan":
-        """A whole iteration's fp16 casts as one launch each way
+    def compress(self, dst, src, nelem: int, src_dtype: int, wire_dtype: int,
+                 stream=None) -> int:
+        """``dst[i] = wire(src[i])`` for ``nelem`` ELEMENTS, the 2-byte wire
+        format named (byteps_reduce_compress_to): FLOAT16 is ``compress_fp16``,
+        BFLOAT16 takes f32, f64 or fp16 (round to nearest even, f64 through
+        f32, f32 subnormals kept)."""
+        _fits_cast(nelem, dst, src, src_dtype)
+        _check(self.lib.byteps_reduce_compress_to(_ptr(dst), _ptr(src), int(nelem),
+                                                  int(src_dtype), int(wire_dtype),
+                                                  _stream_of(dst, stream)))
+        return 0
+
+    def decompress(self, dst, src, nelem: int, dst_dtype: int, wire_dtype: int,
+                   divisor: int = 1, stream=None) -> int:
+        """``dst[i] = T(src[i])``, or ``T(wire(src[i] / divisor))`` for a
+        divisor above 1, ``src`` in the named wire format
+        (byteps_reduce_decompress_from)."""
+        _fits_cast(nelem, src, dst, dst_dtype)
+        _check(self.lib.byteps_reduce_decompress_from(_ptr(dst), _ptr(src), int(nelem),
+                                                      int(dst_dtype), int(wire_dtype),
+                                                      int(divisor), _stream_of(dst, stream)))
+        return 0
+
+    def cast_plan(self, segments: Sequence[tuple], wide_dtype: int,
+                  wire_dtype: int = DType.FLOAT16) -> "CastPlan":
+        """A whole iteration's casts as one launch each way
         (byteps_reduce_cast_plan_*): ``segments`` are ``(wide, half, nelem)``
-        triples of tensors or raw pointers, all of ``wide_dtype``.  The plan
-        keeps the tensors it was built from alive."""
-        return CastPlan(self.lib, segments, wide_dtype)
+        triples of tensors or raw pointers, all of ``wide_dtype`` with their
+        2-byte sides of ``wire_dtype`` (fp16 unless named).  The plan keeps
+        the tensors it was built from alive."""
+        return CastPlan(self.lib, segments, wide_dtype, wire_dtype)
 
     def sum_n(self, dst, srcs: Sequence, length: int, dtype: int,
               mode: int = MODE_REFERENCE, stream=None) -> int:
@@ -336,15 +369,17 @@ class CastPlan:
     device.  ``compress`` writes every fp16 side from its wide side,
     ``decompress`` the other way (dividing by ``divisor`` on the fp16 value),
     each as ONE launch; per segment the bytes are those of
-    ``GpuReducer.compress_fp16`` / ``decompress_fp16``.
+    ``GpuReducer.compress_fp16`` / ``decompress_fp16`` — or, for a plan whose
+    ``wire_dtype`` is BFLOAT16, of ``GpuReducer.compress`` / ``decompress``.
 
     Tensor operands are bounds-checked before the library sees them, and the
     plan holds a reference to every one: the device table carries raw
     addresses, and a write through a freed one would be a GPU fault rather
     than an exception.  Raw pointers carry no size and stay the caller's."""
 
-    def __init__(self, lib, segments, wide_dtype):
+    def __init__(self, lib, segments, wide_dtype, wire_dtype=DType.FLOAT16):
         self.lib = lib
+        self.wire_dtype = int(wire_dtype)
         self.handle = _vp()
         segments = [tuple(s) for s in segments]
         for wide, half, nelem in segments:
@@ -357,8 +392,13 @@ class CastPlan:
             descs[i].wide = _ptr(wide)
             descs[i].half = _ptr(half)
             descs[i].nelem = int(nelem)
-        _check(lib.byteps_reduce_cast_plan_create(descs, len(segments), int(wide_dtype),
-                                                  ctypes.byref(self.handle)))
+        if self.wire_dtype == DType.FLOAT16:
+            _check(lib.byteps_reduce_cast_plan_create(descs, len(segments), int(wide_dtype),
+                                                      ctypes.byref(self.handle)))
+        else:
+            _check(lib.byteps_reduce_cast_plan_create_wire(descs, len(segments), int(wide_dtype),
+                                                           self.wire_dtype,
+                                                           ctypes.byref(self.handle)))
 
     def compress(self, stream=None) -> None:
         _check(self.lib.byteps_reduce_cast_plan_compress(self.handle,

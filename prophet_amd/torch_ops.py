@@ -26,6 +26,13 @@ op                                    reference / C ABI
 ``bpsr::decompress_fp16_out(dst,      ``FP16Compressor.decompress`` fused with
 src, divisor)``                       average's divide on the fp16 value
                                       -> byteps_reduce_decompress_fp16
+``bpsr::compress_bf16(src) -> out``   ``BF16Compressor.compress`` (build
+                                      extension: f32 / f64 / fp16 as bf16)
+                                      -> byteps_reduce_compress_to
+``bpsr::compress_bf16_out(dst, src)`` the same into a preallocated bf16 ``dst``
+``bpsr::decompress_bf16_out(dst,      ``BF16Compressor.decompress`` fused with
+src, divisor)``                       average's divide on the bf16 value
+                                      -> byteps_reduce_decompress_from
 ====================================  ===========================================
 
 Tensors must be contiguous, on one CUDA (HIP) device, of one dtype among the
@@ -38,7 +45,7 @@ from typing import List
 
 import torch
 
-from .dtypes import from_torch
+from .dtypes import DType, from_torch
 from .reducer import MODE_REFERENCE, GpuReducer, ReduceError, EARGS, EDTYPE
 
 _RED = None
@@ -102,18 +109,25 @@ def sum_n(srcs: List[torch.Tensor], mode: int = MODE_REFERENCE) -> torch.Tensor:
     return out
 
 
-def _check_cast(half: torch.Tensor, wide: torch.Tensor) -> int:
-    """Operands of an fp16 cast: ``half`` fp16, ``wide`` f32 / f64 / bf16, as
-    many elements, one device, contiguous.  Returns the element count."""
+_WIDE_OF = {torch.float16: (torch.float32, torch.float64, torch.bfloat16),
+            torch.bfloat16: (torch.float32, torch.float64, torch.float16)}
+_WIRE_NAME = {torch.float16: "fp16", torch.bfloat16: "bf16"}
+
+
+def _check_cast(half: torch.Tensor, wide: torch.Tensor, wire=torch.float16) -> int:
+    """Operands of a cast: ``half`` of the wire dtype (fp16 unless named),
+    ``wide`` f32 / f64 / the other 2-byte float, as many elements, one device,
+    contiguous.  Returns the element count."""
     for t in (half, wide):
         if t.device.type != "cuda":
             raise ReduceError(EARGS, f"bpsr ops need device tensors, got {t.device}")
         if not t.is_contiguous():
             raise ReduceError(EARGS, "bpsr ops need contiguous tensors")
-    if half.dtype != torch.float16:
-        raise ReduceError(EDTYPE, f"the compressed tensor must be float16, got {half.dtype}")
-    if wide.dtype not in (torch.float32, torch.float64, torch.bfloat16):
-        raise ReduceError(EDTYPE, f"fp16 compression of {wide.dtype}")
+    if half.dtype != wire:
+        raise ReduceError(EDTYPE, f"the compressed tensor must be {str(wire)[len('torch.'):]}, "
+                                  f"got {half.dtype}")
+    if wide.dtype not in _WIDE_OF[wire]:
+        raise ReduceError(EDTYPE, f"{_WIRE_NAME[wire]} compression of {wide.dtype}")
     if half.numel() != wide.numel() or half.device != wide.device:
         raise ReduceError(EARGS, "bpsr ops need tensors of one size and device")
     return wide.numel()
@@ -140,6 +154,45 @@ def decompress_fp16_out(dst: torch.Tensor, src: torch.Tensor, divisor: int = 1) 
     if divisor < 1:
         raise ReduceError(EARGS, f"divisor {divisor} < 1")
     _red().decompress_fp16(dst, src, n, from_torch(dst.dtype), divisor, stream=_stream(dst))
+
+
+@torch.library.custom_op("bpsr::compress_bf16_out", mutates_args=("dst",), device_types="cuda")
+def compress_bf16_out(dst: torch.Tensor, src: torch.Tensor) -> None:
+    n = _check_cast(dst, src, torch.bfloat16)
+    _red().compress(dst, src, n, from_torch(src.dtype), DType.BFLOAT16, stream=_stream(dst))
+
+
+@torch.library.custom_op("bpsr::compress_bf16", mutates_args=(), device_types="cuda")
+def compress_bf16(src: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
+    n = _check_cast(out, src, torch.bfloat16)
+    _red().compress(out, src, n, from_torch(src.dtype), DType.BFLOAT16, stream=_stream(out))
+    return out
+
+
+@torch.library.custom_op("bpsr::decompress_bf16_out", mutates_args=("dst",),
+                         device_types="cuda")
+def decompress_bf16_out(dst: torch.Tensor, src: torch.Tensor, divisor: int = 1) -> None:
+    n = _check_cast(src, dst, torch.bfloat16)
+    if divisor < 1:
+        raise ReduceError(EARGS, f"divisor {divisor} < 1")
+    _red().decompress(dst, src, n, from_torch(dst.dtype), DType.BFLOAT16, divisor,
+                      stream=_stream(dst))
+
+
+@compress_bf16_out.register_fake
+def _(dst, src):
+    return None
+
+
+@compress_bf16.register_fake
+def _(src):
+    return torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
+
+
+@decompress_bf16_out.register_fake
+def _(dst, src, divisor=1):
+    return None
 
 
 @compress_fp16_out.register_fake
@@ -183,7 +236,9 @@ def _(srcs, mode=MODE_REFERENCE):
 
 
 OPS = ("sum_", "sum3_", "copy_", "sum_n_out", "sum_n",
-       "compress_fp16", "compress_fp16_out", "decompress_fp16_out")
+       "compress_fp16", "compress_fp16_out", "decompress_fp16_out",
+       "compress_bf16", "compress_bf16_out", "decompress_bf16_out")
 
 __all__ = ["sum_", "sum3_", "copy_", "sum_n_out", "sum_n", "compress_fp16",
-           "compress_fp16_out", "decompress_fp16_out", "OPS"]
+           "compress_fp16_out", "decompress_fp16_out", "compress_bf16",
+           "compress_bf16_out", "decompress_bf16_out", "OPS"]

@@ -47,6 +47,18 @@ direction on its own, as a plan launch and as the one-tensor call.  Gates:
              spreads of the one-tensor call's.
 
 One JSON line, also appended to ``--out`` when given.
+
+``--wire bf16`` measures the bf16 wire (byteps_reduce_compress_to /
+_decompress_from / _cast_plan_create_wire with BFLOAT16) against the fp16 wire
+in the same run, by the same method, the two alternated round by round: at
+``--elems`` the one-tensor compress and decompress / 8 of f32, with
+``--iteration`` the plan over the ResNet-50 table, each direction timed on its
+own.  Both wires move the same 6 bytes per f32 element.  Gates, per direction:
+
+  the bf16 median is not slower than the fp16 median by more than the larger
+  of the two candidates' spreads (max - min of the rounds).
+
+``--wire fp16`` (the default) is everything above, unchanged.
 """
 import argparse
 import json
@@ -97,7 +109,11 @@ def main() -> int:
                    help="a whole iteration's casts: per-segment loop, cast plan, one tensor")
     p.add_argument("--table", default=os.path.join(ROOT, "tools", "cfg3_resnet50_table.txt"))
     p.add_argument("--out", default=None, help="append the JSON line to this file too")
+    p.add_argument("--wire", choices=("fp16", "bf16"), default="fp16",
+                   help="bf16: the bf16 casts alternated with the fp16 casts")
     args = p.parse_args()
+    if args.wire == "bf16":
+        return wire_mode(args)
     if args.iteration:
         return iteration_mode(args)
 
@@ -363,6 +379,121 @@ def iteration_mode(args) -> int:
         with open(args.out, "a") as f:
             f.write(line + "\n")
     return 0 if all(gates.values()) else 1
+
+
+def wire_mode(args) -> int:
+    """The bf16 wire against the fp16 wire, alternated in one run."""
+    import torch
+
+    from prophet_amd.dtypes import DType
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    F32, WIRES = DType.FLOAT32, {"fp16": (DType.FLOAT16, torch.float16),
+                                 "bf16": (DType.BFLOAT16, torch.bfloat16)}
+    out = {"tool": "bench_compress", "wire": "bf16", "sets": args.sets, "rounds": args.rounds,
+           "inner": args.inner, "device": torch.cuda.get_device_name(0)}
+    with step("setup", 120):
+        red = GpuReducer(device=0)
+        g = torch.Generator(device=dev).manual_seed(3)
+        sets = []
+        if args.iteration:
+            total_bytes, rows = read_table(args.table)
+            n = sum(ln // 2 for _, ln in rows)
+            for _ in range(args.sets):
+                s = {}
+                for w, (wd, tdt) in WIRES.items():
+                    # a wide arena per wire: each plan writes the one it was built over
+                    wide = torch.randn(total_bytes // 2, device=dev, generator=g) * 64
+                    half = wide.to(tdt)
+                    s[w] = {"wide": wide, "half": half,
+                            "plan": red.cast_plan([(wide[o // 2:(o + ln) // 2],
+                                                    half[o // 2:(o + ln) // 2], ln // 2)
+                                                   for o, ln in rows], F32, wd)}
+                sets.append(s)
+            out.update({"mode": "iteration", "table": os.path.basename(args.table),
+                        "segments": len(rows), "elems": n})
+        else:
+            n = args.elems
+            for _ in range(args.sets):
+                x = torch.randn(n, device=dev, generator=g) * 64
+                s = {"x": x, "out": torch.empty(n, device=dev)}
+                for w, (_, tdt) in WIRES.items():
+                    s[w] = {"h": torch.empty(n, dtype=tdt, device=dev), "h2": x.to(tdt)}
+                sets.append(s)
+            out.update({"mode": "one tensor", "elems": n})
+        torch.cuda.synchronize()
+
+    same = {}
+    with step("check", 120):
+        s = sets[0]
+        for w, (wd, tdt) in WIRES.items():
+            bits = torch.int16
+            if args.iteration:
+                a = s[w]
+                want = a["wide"].to(tdt)
+                a["half"].fill_(7.0)
+                a["plan"].compress()
+                # the table's segments need not cover the arena: compare where they do
+                cover = torch.zeros(a["half"].numel(), dtype=torch.bool, device=dev)
+                for o, ln in rows:
+                    cover[o // 2:(o + ln) // 2] = True
+                same[f"compress_{w}"] = bool(torch.equal(a["half"].view(bits)[cover],
+                                                         want.view(bits)[cover]))
+                ref = a["half"].clone().div_(8).float()
+                a["plan"].decompress(8)
+                same[f"decompress_div8_{w}"] = bool(torch.equal(
+                    a["wide"].view(torch.int32)[cover], ref.view(torch.int32)[cover]))
+                del ref, want, cover
+            else:
+                red.compress(s[w]["h"], s["x"], n, F32, wd)
+                same[f"compress_{w}"] = bool(torch.equal(s[w]["h"].view(bits),
+                                                         s["x"].to(tdt).view(bits)))
+                red.decompress(s["out"], s[w]["h"], n, F32, wd, 8)
+                ref = s[w]["h"].clone().div_(8).float()
+                same[f"decompress_div8_{w}"] = bool(torch.equal(s["out"].view(torch.int32),
+                                                                ref.view(torch.int32)))
+                del ref
+        torch.cuda.synchronize()
+    out["bit_equal_to_torch_device_cast"] = same
+
+    cands = {}
+    for w, (wd, _) in WIRES.items():
+        if args.iteration:
+            cands[f"compress_{w}"] = (lambda k, w=w: sets[k][w]["plan"].compress(), args.inner)
+            cands[f"decompress_{w}"] = (lambda k, w=w: sets[k][w]["plan"].decompress(8),
+                                        args.inner)
+        else:
+            cands[f"compress_{w}"] = (lambda k, w=w, wd=wd: red.compress(
+                sets[k][w]["h"], sets[k]["x"], n, F32, wd), args.inner)
+            cands[f"decompress_{w}"] = (lambda k, w=w, wd=wd: red.decompress(
+                sets[k]["out"], sets[k][w]["h2"], n, F32, wd, 8), args.inner)
+    # alternated: compress fp16, compress bf16, decompress fp16, decompress bf16
+    order = ["compress_fp16", "compress_bf16", "decompress_fp16", "decompress_bf16"]
+    res = timed_rounds(torch, {k: cands[k] for k in order}, len(sets), args)
+    for v in res.values():
+        v["roofline_frac"] = round(6 * n / (v["ms"] * 1e-3) / HBM_BYTES_PER_S, 4)
+    gates, spreads = {}, {}
+    for d in ("compress", "decompress"):
+        sp = max(res[f"{d}_fp16"]["spread_ms"], res[f"{d}_bf16"]["spread_ms"])
+        spreads[d] = sp
+        gates[f"{d}_bf16_not_slower_than_fp16"] = \
+            res[f"{d}_bf16"]["ms"] - res[f"{d}_fp16"]["ms"] <= sp
+    out.update({"results": res, "gate_spread_ms": spreads, "gates": gates})
+    if args.iteration:
+        for s in sets:
+            for w in WIRES:
+                s[w]["plan"].close()
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    return 0 if all(gates.values()) and all(same.values()) else 1
 
 
 def end_to_end(nelem: int, iters: int, where: str) -> dict:
