@@ -82,8 +82,24 @@ enum byteps_reduce_mode {
   /* Round to the storage type after every pairwise add: bit-exact with the
    * reference CpuReducer fold.  Default. */
   BYTEPS_REDUCE_MODE_REFERENCE = 0,
-  /* Accumulate all N inputs in fp32 and round once at the end (more accurate,
-   * not bit-exact; documented tolerance <= 1 ulp of the exact sum for N <= 32). */
+  /* Widen every input to fp32 once, fold in fp32, narrow once.  Not the
+   * reference's arithmetic, but just as deterministic, per element:
+   *  - a strict left fold in source order, each add an IEEE fp32 add (round to
+   *    nearest even, subnormals kept), then ONE round-to-nearest-even narrowing
+   *    to the storage type (overflow gives Inf, subnormals kept);
+   *  - NaN: an add whose result is NaN yields the accumulator's NaN if it is
+   *    one, else the source's, quieted, sign and payload kept (an fp16 payload
+   *    sits in the top 10 fraction bits of the fp32 one); inf + -inf yields the
+   *    default NaN with the sign set (fp16 0xfe00, bf16 0xffc0).  The fp16
+   *    tail rule of reference mode (0x7fff) does not apply;
+   *  - n = 1 is a byte copy (a signalling NaN stays as it is), in
+   *    byteps_reduce_sum_n and in every table;
+   *  - n > BYTEPS_REDUCE_MAX_SRCS (byteps_reduce_sum_n only): the first 32
+   *    sources fold and narrow; each further launch folds the running result
+   *    with the next 31 and narrows again.
+   * The result is within 1/2 ulp of the fp32 fold.  It is close to the exact
+   * sum only where the fp32 partial sums do not cancel: fp16 65504, 1e-4,
+   * -65504 folds to 0, although the exact sum 1e-4 is representable. */
   BYTEPS_REDUCE_MODE_ACCUM_F32 = 1
 };
 

@@ -88,6 +88,9 @@ __device__ __forceinline__ vec16 fold_vector_exact(const XS& srcs, int n, uint64
     asm volatile("" : "+v"(p));
     return p;
   };
+  if constexpr (!one_source_is_identity<Op>::value) {
+    if (n == 1) return ld16<NT>(opaque(srcs[0] + off));  // one source: a byte copy
+  }
   typename Op::Acc acc = Op::init(ld16<NT>(opaque(srcs[0] + off)));
   for (int k = 1; k < n; ++k) Op::accum(acc, ld16<NT>(opaque(srcs[k] + off)));
   return Op::finish(acc);
@@ -263,6 +266,12 @@ __device__ __forceinline__ void fold_elements(const XS& srcs, int n,
     const uint64_t e = s < n_head ? s : g.tail_begin + (s - n_head);
     const bool tail = e >= g.tail_sem_from;
     const uint64_t off = e * sizeof(E);
+    if constexpr (!one_source_is_identity<Op>::value) {
+      if (n == 1) {  // one source: a byte copy (a signalling NaN stays as it is)
+        st_e<E>(dst + off, ld_e<E>(srcs[0] + off, aligned), aligned);
+        continue;
+      }
+    }
     typename Op::EAcc acc{};
     for (int k0 = 0; k0 < n; k0 += 8) {
       E x[8];

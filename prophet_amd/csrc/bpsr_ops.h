@@ -324,6 +324,15 @@ struct OpAcc16 {
   __device__ static E finish_e(EAcc a, bool) { return (E)down(a); }
 };
 
+// A bucket with ONE source is a byte copy in every mode.  For the reference
+// operators init -> finish is the identity already; OpAcc16 widens and narrows,
+// which is exact for every value except a signalling NaN (it comes back
+// quieted), so the exact replay and the element path copy instead.
+template <class Op>
+struct one_source_is_identity { static constexpr bool value = true; };
+template <bool BF>
+struct one_source_is_identity<OpAcc16<BF>> { static constexpr bool value = false; };
+
 // ------------------------------------------------------------- integers ----
 struct OpI8 {  // uint8 and int8: identical two's-complement bits
   static constexpr int kSize = 1;
