@@ -61,7 +61,9 @@ extern "C" {
  *    additive, still 5: byteps_reduce_cast_plan_create / _compress /
  *                       _decompress / _destroy (byteps_cast_desc)
  *    additive, still 5: byteps_reduce_compress_to / _decompress_from /
- *                       byteps_reduce_cast_plan_create_wire (bf16 wire) */
+ *                       byteps_reduce_cast_plan_create_wire (bf16 wire)
+ *    additive, still 5: byteps_reduce_compress_ef / _cast_plan_create_ef
+ *                       (byteps_cast_ef_desc: error-feedback compression) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -394,6 +396,46 @@ int byteps_reduce_cast_plan_create_wire(const byteps_cast_desc* segs, int nsegs,
 int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* plan, void* stream);
 int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* plan, int divisor, void* stream);
 int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* plan);
+
+/* Error-feedback compression: the compress of the two wire formats with a
+ * per-tensor FLOAT32 residual that holds what the 2-byte wire could not carry
+ * and is added back before the next cast.  For src of FLOAT32, wire format N
+ * (`wire_dtype`: FLOAT16 or BFLOAT16) and the residual r at `resid`, per
+ * element and in one pass:
+ *   c  = src[i] + r[i]                  IEEE f32 add, RNE, subnormals kept
+ *   w  = N(c)                           the arithmetic of byteps_reduce_compress_to
+ *   b  = f32(w)                         exact
+ *   r' = isfinite(b) ? c - b : +0.0     f32 subtract (exact: b is c in fewer bits)
+ *   dst[i] = w, r[i] = r'
+ * With r == 0 the bytes at dst are those of byteps_reduce_compress_to (but
+ * for src -0.0, which the add turns into +0.0: -0 + +0 = +0); where b
+ * is finite f32(w) + r' == c exactly; overflow of the wire format, +-inf and
+ * NaN leave r' = +0.0 (bits 0), so a residual never holds a non-finite value.
+ * Pinned bit for bit to the same four lines in torch's CPU ops.
+ *   Scope: FLOAT32 wide tensors only — the residual is f32, and only an f32
+ *   wide side shares its vector layout; any other src_dtype / wide_dtype is
+ *   EDTYPE, as is a wire other than FLOAT16 or BFLOAT16.
+ *   compress_ef: the three byte ranges (2 * nelem at dst, 4 * nelem at resid
+ *            and at src) are pairwise disjoint (EARGS); a null pointer with
+ *            nelem > 0 is EARGS; nelem == 0 succeeds without a launch.
+ *            Asynchronous on `stream`.
+ *   cast_plan_create_ef: a cast plan (above) whose segments carry a residual.
+ *            All 3 * nsegs byte ranges are pairwise disjoint (EARGS).  The
+ *            plan is the same opaque type: _compress on it runs the
+ *            error-feedback compress (per segment the bytes of one
+ *            compress_ef, wire and residual), _decompress on it is the plain
+ *            decompress of `wire_dtype` and leaves the residuals untouched,
+ *            _destroy frees the record table and the residual-pointer table. */
+int byteps_reduce_compress_ef(void* dst, void* resid, const void* src, size_t nelem,
+                              int src_dtype, int wire_dtype, void* stream);
+typedef struct byteps_cast_ef_desc {
+  void* wide;
+  void* half;
+  void* resid;
+  size_t nelem; /* ELEMENTS */
+} byteps_cast_ef_desc;
+int byteps_reduce_cast_plan_create_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype,
+                                      int wire_dtype, byteps_reduce_cast_plan** out);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

@@ -41,6 +41,30 @@ those of ``compress_into`` / ``decompress_into``.  A :class:`CastPlanCache`
 keeps the plans between iterations.  There is no ``torch.library`` op for
 plans: a plan owns raw device pointers, which a traced graph cannot — the
 one-tensor ops stay the traceable form.
+
+``Compression.fp16_ef`` / ``Compression.bf16_ef`` add error feedback to the
+two wire formats, which are memoryless otherwise: whatever the 2-byte
+rounding drops in an iteration is gone (on the fp16 wire an f32 gradient
+below 2^-25 is sent as zero forever; bf16 keeps 8 significant bits a step).
+A per-tensor f32 residual ``r`` holds what the wire could not carry and is
+added back before the next cast.  Per element, float32 tensors only::
+
+    c  = g + r                                    # f32 add
+    w  = wire(c)                                  # the plain compress
+    b  = w.float()                                # exact
+    r' = torch.where(torch.isfinite(b), c - b, 0) # exact where finite; never non-finite
+
+``compress_ef_into(out, residual, tensor)`` writes ``w`` and replaces ``r``
+in place — device tensors in one pass of
+``torch.ops.bpsr.compress_<wire>_ef_out``
+(``prophet_amd/csrc/bpsr_cast_ef.h``), CPU tensors and numpy arrays through
+the four torch lines above, which is the semantics the kernels are pinned to
+bit for bit.  ``compress_many_ef_into`` is the cast-plan form.  The wire
+carries ordinary fp16 / bf16, so the server, the folds and ``decompress*``
+are those of the plain compressors.  The stateless ``compress(tensor)`` stays
+the plain cast: it has no residual to read or to leave the error in.
+Tensors other than float32 (f64 and the 2-byte floats included) pass through
+uncompressed, as integers do.
 """
 from __future__ import annotations
 
@@ -95,7 +119,9 @@ class CastPlanCache:
     """The cast plans of the last few iterations, least recently used out
     first.  A plan is found again by its wide dtype, its wire dtype and the
     (wide address, 2-byte address, element count) of every segment, so a tensor that moved
-    misses and gets a new plan.  A cached plan holds its tensors: their
+    misses and gets a new plan.  An error-feedback plan's segments carry
+    their residual's address as well: a moved residual misses too, and the
+    plan over the same tensors without residuals is another plan.  A cached plan holds its tensors: their
     memory cannot be freed, so no other tensor can appear at a cached
     address while the plan that names it is alive."""
 
@@ -110,9 +136,11 @@ class CastPlanCache:
     def get(self, wide_dtype: int, pairs, wire_dtype: int = 2):
         """The plan over ``pairs`` of flat ``(wide, half)`` device tensors on
         the current device, built on a miss.  ``wire_dtype``: the dtype of
-        the ``half`` side (``DType.FLOAT16`` unless named)."""
+        the ``half`` side (``DType.FLOAT16`` unless named).  Items of three,
+        ``(wide, half, residual)``, ask for the error-feedback plan."""
         key = (int(wide_dtype), int(wire_dtype)) + tuple(
-            (int(w.data_ptr()), int(h.data_ptr()), int(w.numel())) for w, h in pairs)
+            (int(p[0].data_ptr()), int(p[1].data_ptr()), int(p[0].numel()))
+            + tuple(int(r.data_ptr()) for r in p[2:]) for p in pairs)
         plan = self._plans.get(key)
         if plan is not None:
             self._plans.move_to_end(key)
@@ -133,28 +161,38 @@ class CastPlanCache:
 
 def _new_plan(wide_dtype: int, pairs, wire_dtype: int = 2):
     from .torch_ops import _red
-    return _red().cast_plan([(w, h, int(w.numel())) for w, h in pairs], wide_dtype, wire_dtype)
+    return _red().cast_plan([(p[0], p[1], int(p[0].numel())) + tuple(p[2:]) for p in pairs],
+                            wide_dtype, wire_dtype)
 
 
-def _cast_many(comp, pairs, compress: bool, divisor: int, plans) -> None:
+def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None) -> None:
     """``pairs`` of ``(wide, half)`` tensors or arrays cast by compressor
     ``comp``: the device ones as one plan launch per (device, wide dtype, wire
-    dtype), the host ones one by one."""
+    dtype), the host ones one by one.  With ``residuals`` (one per pair) the
+    plans are error-feedback plans: the compress is ``compress_ef_into``'s,
+    the decompress the plain one through the same plan."""
     if int(divisor) < 1:
         raise ValueError(f"divisor {divisor} < 1")
     groups: dict = {}
-    for wide, half in pairs:
+    for i, (wide, half) in enumerate(pairs):
+        resid = None if residuals is None else residuals[i]
         if not _on_device(wide) and not _on_device(half):
-            if compress:
+            if not compress:
+                comp.decompress_into(wide, half, divisor)
+            elif resid is None:
                 comp.compress_into(half, wide)
             else:
-                comp.decompress_into(wide, half, divisor)
+                comp.compress_ef_into(half, resid, wide)
             continue
-        from .torch_ops import _check_cast
+        from .torch_ops import _check_cast, _check_cast_ef
         wire = comp.wire_torch_dtype()
-        _check_cast(half, wide, wire)
-        groups.setdefault((wide.device, wide.dtype, wire), []).append(
-            (wide.reshape(-1), half.reshape(-1)))
+        if resid is None:
+            _check_cast(half, wide, wire)
+            seg = (wide.reshape(-1), half.reshape(-1))
+        else:
+            _check_cast_ef(half, resid, wide, wire)
+            seg = (wide.reshape(-1), half.reshape(-1), resid.reshape(-1))
+        groups.setdefault((wide.device, wide.dtype, wire), []).append(seg)
     if not groups:
         return
     import torch
@@ -184,6 +222,8 @@ class Compressor:
     @staticmethod
     def decompress(tensor, ctx):
         raise NotImplementedError
+
+    ERROR_FEEDBACK = False                # compress_ef_into and a residual per tensor
 
     @staticmethod
     def compresses(tensor) -> bool:
@@ -354,13 +394,104 @@ class BF16Compressor(_CastCompressor):
         return _as_host_bf16(x)
 
 
+def _is_f32(x) -> bool:
+    if _is_torch(x):
+        import torch
+        return x.dtype == torch.float32
+    return x.dtype == np.float32
+
+
+class _ErrorFeedback:
+    """Error feedback over a cast compressor (mixed in ahead of it): a
+    per-tensor f32 residual takes what the wire format could not carry and
+    gives it back before the next cast.  float32 tensors only — everything
+    else, f64 and the 2-byte floats included, passes through uncompressed.
+    ``compress(tensor)`` is inherited and stays the plain, stateless cast (no
+    residual to read or write); ``decompress*`` is inherited unchanged."""
+
+    ERROR_FEEDBACK = True
+
+    @classmethod
+    def compresses(cls, tensor) -> bool:
+        return _is_f32(tensor)
+
+    @classmethod
+    def residual_like(cls, x):
+        """A zeroed f32 residual of x's kind, device and element count."""
+        if _is_torch(x):
+            import torch
+            return torch.zeros(x.numel(), dtype=torch.float32, device=x.device)
+        return np.zeros(x.size, dtype=np.float32)
+
+    @classmethod
+    def compress_ef_into(cls, out, residual, tensor):
+        """``c = tensor + residual``; ``out = wire(c)``; ``residual = c -
+        out.float()`` where that is finite, +0.0 elsewhere — in place, one
+        pass on the device; returns ``out``."""
+        import torch
+        if not cls.compresses(tensor) or not _is_f32(residual):
+            raise ValueError("error feedback needs a float32 tensor and a float32 residual")
+        if _on_device(tensor):
+            from . import torch_ops  # noqa: F401
+            with torch.cuda.device(tensor.device):
+                getattr(torch.ops.bpsr, f"compress_{cls.NAME}_ef_out")(
+                    out.reshape(-1), residual.reshape(-1), tensor.reshape(-1))
+            return out
+        g = _as_host_tensor(tensor).reshape(-1)
+        r = _as_host_tensor(residual).reshape(-1)
+        if r.numel() != g.numel():
+            raise ValueError("error feedback: residual and tensor differ in size")
+        c = g + r
+        w = c.to(cls.wire_torch_dtype())
+        b = w.to(torch.float32)
+        r.copy_(torch.where(torch.isfinite(b), c - b, torch.zeros_like(c)))
+        cls._host_wire(out).reshape(-1).copy_(w)
+        return out
+
+    @classmethod
+    def compress_many_ef_into(cls, outs, residuals, tensors, plans: CastPlanCache | None = None):
+        """``compress_ef_into(outs[i], residuals[i], tensors[i])`` for every
+        i, the device tensors as one error-feedback cast-plan launch per
+        device; returns ``outs``."""
+        if len(outs) != len(tensors) or len(residuals) != len(tensors):
+            raise ValueError("compress_many_ef_into: as many outputs and residuals as tensors")
+        for t, r in zip(tensors, residuals):
+            if not cls.compresses(t) or not _is_f32(r):
+                raise ValueError("error feedback needs float32 tensors and float32 residuals")
+        _cast_many(cls, list(zip(tensors, outs)), True, 1, plans, residuals=list(residuals))
+        return outs
+
+    @classmethod
+    def decompress_many_into(cls, outs, compressed, divisor: int = 1,
+                             plans: CastPlanCache | None = None, residuals=None):
+        """The inherited decompress.  ``residuals`` (those given to
+        ``compress_many_ef_into`` over the same tensors) only names the plan:
+        the error-feedback plan's own decompress is the plain one, so one
+        cached plan serves both directions; the residuals are not touched."""
+        if len(outs) != len(compressed):
+            raise ValueError("decompress_many_into: as many outputs as compressed tensors")
+        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans,
+                   residuals=None if residuals is None else list(residuals))
+        return outs
+
+
+class FP16EFCompressor(_ErrorFeedback, FP16Compressor):
+    """float32 tensors travel as fp16 with error feedback."""
+
+
+class BF16EFCompressor(_ErrorFeedback, BF16Compressor):
+    """float32 tensors travel as bf16 with error feedback."""
+
+
 class Compression:
     """Optional gradient compression used during push_pull."""
 
     none = NoneCompressor
     fp16 = FP16Compressor
     bf16 = BF16Compressor
+    fp16_ef = FP16EFCompressor
+    bf16_ef = BF16EFCompressor
 
 
-__all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor", "Compression",
-           "CastPlanCache"]
+__all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
+           "FP16EFCompressor", "BF16EFCompressor", "Compression", "CastPlanCache"]

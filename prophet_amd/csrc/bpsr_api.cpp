@@ -507,41 +507,107 @@ int byteps_reduce_decompress_from(void* dst, const void* src, size_t nelem, int 
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "decompress kernel launch");
 }
 
+// The three byte ranges of an error-feedback compress are pairwise disjoint:
+// dst and resid are written, src is read.  All checks before any HIP call;
+// returns 1 when there is nothing to do.
+static int cast_ef_check(const void* dst, const void* resid, const void* src, size_t nelem,
+                         int src_dtype, int wire) {
+  if (wire != kFloat16 && wire != kBFloat16)
+    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire);
+  if (src_dtype != kFloat32)
+    return fail(BYTEPS_REDUCE_EDTYPE, "error-feedback compression of data type %d (FLOAT32 only)",
+                src_dtype);
+  if (nelem == 0) return 1;
+  if (!dst || !resid || !src) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
+  if (nelem > SIZE_MAX / 4) return fail(BYTEPS_REDUCE_EARGS, "element count overflows");
+  const uintptr_t b[3] = {(uintptr_t)dst, (uintptr_t)resid, (uintptr_t)src};
+  const size_t n[3] = {nelem * 2, nelem * 4, nelem * 4};
+  for (int i = 0; i < 3; ++i)
+    if (b[i] > UINTPTR_MAX - n[i])
+      return fail(BYTEPS_REDUCE_EARGS, "operand wraps the address space");
+  static const char* const name[3] = {"dst", "resid", "src"};
+  for (int i = 0; i < 3; ++i)
+    for (int j = i + 1; j < 3; ++j)
+      if (b[i] < b[j] + n[j] && b[j] < b[i] + n[i])
+        return fail(BYTEPS_REDUCE_EARGS, "%s and %s overlap", name[i], name[j]);
+  return BYTEPS_REDUCE_OK;
+}
+
+int byteps_reduce_compress_ef(void* dst, void* resid, const void* src, size_t nelem,
+                              int src_dtype, int wire_dtype, void* stream) {
+  const int rc = cast_ef_check(dst, resid, src, nelem, src_dtype, wire_dtype);
+  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
+  const auto launch = wire_dtype == kBFloat16 ? launch_compress_ef_bf16 : launch_compress_ef;
+  hipError_t e = launch(dst, resid, src, nelem, tuning(), to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "error-feedback compress kernel launch");
+}
+
 struct byteps_reduce_cast_plan {
   int device;
   int dtype;
   int wire;
   void* dev_table;
+  void* dev_resid;  // error-feedback plans: one residual pointer per record
   CastTableInfo ti;
 };
 
 // table_dtype: what the table builder is given.  It cuts by element size alone
 // and knows the fp16 wire's three wide types, so a wide fp16 (bf16 wire) is
 // cut as its 2-byte peer.
+// Upload a built table (and, for an error-feedback plan, its residual
+// pointers: `resid` non-null) into a new plan.
+static int cast_plan_upload(const std::vector<char>& host,
+                            const std::vector<unsigned char*>* resid, const CastTableInfo& ti,
+                            int wide_dtype, int wire, byteps_reduce_cast_plan** out) {
+  auto* p = new byteps_reduce_cast_plan();
+  p->dtype = wide_dtype;
+  p->wire = wire;
+  p->ti = ti;
+  p->dev_table = nullptr;
+  p->dev_resid = nullptr;
+  hipError_t e = hipGetDevice(&p->device);
+  if (e == hipSuccess && ti.records > 0) {
+    e = hipMalloc(&p->dev_table, ti.bytes);
+    if (e == hipSuccess)
+      e = hipMemcpy(p->dev_table, host.data(), ti.bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && resid) {
+      const size_t rb = resid->size() * sizeof(unsigned char*);
+      e = hipMalloc(&p->dev_resid, rb);
+      if (e == hipSuccess) e = hipMemcpy(p->dev_resid, resid->data(), rb, hipMemcpyHostToDevice);
+    }
+  }
+  if (e != hipSuccess) {
+    if (p->dev_table) (void)hipFree(p->dev_table);
+    if (p->dev_resid) (void)hipFree(p->dev_resid);
+    delete p;
+    return hip_fail(e, "cast plan table upload");
+  }
+  *out = p;
+  return BYTEPS_REDUCE_OK;
+}
+
 static int cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int wire,
                             int table_dtype, byteps_reduce_cast_plan** out) {
   std::vector<char> host;
   CastTableInfo ti;
   const int rc = build_cast_table(segs, nsegs, table_dtype, tuning().copy_vpt, host, &ti);
   if (rc) return rc;
-  auto* p = new byteps_reduce_cast_plan();
-  p->dtype = wide_dtype;
-  p->wire = wire;
-  p->ti = ti;
-  p->dev_table = nullptr;
-  hipError_t e = hipGetDevice(&p->device);
-  if (e == hipSuccess && ti.records > 0) {
-    e = hipMalloc(&p->dev_table, ti.bytes);
-    if (e == hipSuccess)
-      e = hipMemcpy(p->dev_table, host.data(), ti.bytes, hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    if (p->dev_table) (void)hipFree(p->dev_table);
-    delete p;
-    return hip_fail(e, "cast plan table upload");
-  }
-  *out = p;
-  return BYTEPS_REDUCE_OK;
+  return cast_plan_upload(host, nullptr, ti, wide_dtype, wire, out);
+}
+
+int byteps_reduce_cast_plan_create_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype,
+                                      int wire_dtype, byteps_reduce_cast_plan** out) {
+  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
+  *out = nullptr;
+  if (wire_dtype != kFloat16 && wire_dtype != kBFloat16)
+    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire_dtype);
+  std::vector<char> host;
+  std::vector<unsigned char*> resid;
+  CastTableInfo ti;
+  const int rc =
+      build_cast_table_ef(segs, nsegs, wide_dtype, tuning().copy_vpt, host, resid, &ti);
+  if (rc) return rc;
+  return cast_plan_upload(host, &resid, ti, wide_dtype, wire_dtype, out);
 }
 
 int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
@@ -567,6 +633,13 @@ static int cast_plan_launch(byteps_reduce_cast_plan* p, bool compress, int divis
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
   if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
+  if (compress && p->dev_resid) {  // error-feedback plan: 2 + 4 bytes written an element
+    const auto ef = p->wire == kBFloat16 ? launch_cast_plan_ef_bf16 : launch_cast_plan_ef;
+    hipError_t e = ef(static_cast<const CastRec*>(p->dev_table),
+                      static_cast<unsigned char* const*>(p->dev_resid), p->ti.records, p->ti.u,
+                      p->ti.nelem * 6, tuning(), to_stream(stream));
+    return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan kernel launch");
+  }
   const uint64_t out_bytes = p->ti.nelem * (compress ? 2 : (uint64_t)elem_size(p->dtype));
   const auto launch = p->wire == kBFloat16 ? launch_cast_plan_bf16 : launch_cast_plan;
   hipError_t e = launch(compress, static_cast<const CastRec*>(p->dev_table), p->ti.records,
@@ -586,6 +659,10 @@ int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* p) {
   if (!p) return BYTEPS_REDUCE_OK;
   hipError_t e = hipSuccess;
   if (p->dev_table) e = hipFree(p->dev_table);
+  if (p->dev_resid) {
+    const hipError_t e2 = hipFree(p->dev_resid);
+    if (e == hipSuccess) e = e2;
+  }
   delete p;
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan free");
 }

@@ -99,6 +99,15 @@ struct CastTableInfo {
 // fewer than kMinTiles vector tiles.  No HIP call.
 int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                      std::vector<char>& out, CastTableInfo* ti);
+// The same for an error-feedback plan (wide_dtype FLOAT32, else EDTYPE): the
+// cut also asks the residual to co-align (cast_cut_ef), all 3 * nsegs byte
+// ranges must be pairwise disjoint, a null residual with nelem > 0 is EARGS,
+// and `resid_out` receives one pointer per record: the segment's residual
+// plus (the record's wide pointer - the segment's wide pointer).  On an error
+// both outputs are left as they were.  No HIP call.
+int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                        std::vector<char>& out, std::vector<unsigned char*>& resid_out,
+                        CastTableInfo* ti);
 
 // ------------------------------------- library queues (bpsr_queues.cpp) --
 // Per device, created on first use, never destroyed: the four library queues

@@ -1,6 +1,8 @@
 // Host arithmetic of the cast plan (byteps_reduce_cast_plan_*): the table of
-// tile records one plan launch reads, compress or decompress.  No HIP runtime
-// call (tests/test_cast_table.py builds this file with g++).
+// tile records one plan launch reads, compress or decompress, and for an
+// error-feedback plan the parallel array of one residual pointer per record.
+// No HIP runtime call (tests/test_cast_table.py and tests/test_cast_table_ef.py
+// build this file with g++).
 #include <algorithm>
 #include <cstring>
 
@@ -13,8 +15,18 @@ namespace {
 struct Seg {
   unsigned char* wide;
   unsigned char* half;
+  unsigned char* resid;  // error-feedback plans, else null
   uint64_t nelem;
   CastCut cut;
+};
+
+// byteps_cast_desc and byteps_cast_ef_desc as one: resid is null without
+// error feedback
+struct Desc {
+  void* wide;
+  void* half;
+  void* resid;
+  size_t nelem;
 };
 
 struct Range {
@@ -24,36 +36,44 @@ struct Range {
 
 }  // namespace
 
-int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
-                     std::vector<char>& out, CastTableInfo* ti) {
-  if (wide_dtype != kFloat32 && wide_dtype != kFloat64 && wide_dtype != kBFloat16)
-    return fail(BYTEPS_REDUCE_EDTYPE, "fp16 compression of data type %d", wide_dtype);
-  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
+// rout: null for a plain plan; for an error-feedback plan (f32 wide side) it
+// receives one residual pointer per record, the segment's residual base plus
+// the record's distance into the wide operand — wide and residual are both
+// f32, so the byte offsets agree.
+static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
+                 std::vector<char>& out, std::vector<unsigned char*>* rout, CastTableInfo* ti) {
+  const int nsegs = (int)segs.size();
+  const bool ef = rout != nullptr;
   const uint64_t es = (uint64_t)elem_size(wide_dtype);
   std::vector<Seg> live;
   std::vector<Range> ranges;
   live.reserve((size_t)nsegs);
-  ranges.reserve(2 * (size_t)nsegs);
+  ranges.reserve((ef ? 3 : 2) * (size_t)nsegs);
   uint64_t total = 0;
   for (int i = 0; i < nsegs; ++i) {
-    const byteps_cast_desc& d = segs[i];
+    const Desc& d = segs[i];
     if (d.nelem == 0) continue;
-    if (!d.wide || !d.half) return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
+    if (!d.wide || !d.half || (ef && !d.resid))
+      return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
     if (d.nelem > SIZE_MAX / es)
       return fail(BYTEPS_REDUCE_EARGS, "segment %d: element count overflows", i);
     const uintptr_t w = (uintptr_t)d.wide, h = (uintptr_t)d.half;
     const size_t wb = d.nelem * es, hb = d.nelem * 2;
-    if (w > UINTPTR_MAX - wb || h > UINTPTR_MAX - hb)
+    if (w > UINTPTR_MAX - wb || h > UINTPTR_MAX - hb || (ef && (uintptr_t)d.resid > UINTPTR_MAX - wb))
       return fail(BYTEPS_REDUCE_EARGS, "segment %d: operand wraps the address space", i);
     if (total > UINT64_MAX - d.nelem) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
     total += d.nelem;
     ranges.push_back({w, w + wb, i});
     ranges.push_back({h, h + hb, i});
+    if (ef) ranges.push_back({(uintptr_t)d.resid, (uintptr_t)d.resid + wb, i});
     live.push_back({static_cast<unsigned char*>(d.wide), static_cast<unsigned char*>(d.half),
-                    (uint64_t)d.nelem, cast_cut(d.half, d.wide, d.nelem, (int)es)});
+                    static_cast<unsigned char*>(d.resid), (uint64_t)d.nelem,
+                    ef ? cast_cut_ef(d.half, d.wide, d.resid, d.nelem)
+                       : cast_cut(d.half, d.wide, d.nelem, (int)es)});
   }
   // The plan serves both directions, so every range is written in one of
-  // them: all 2 * live ranges must be pairwise disjoint.  Sorted by their
+  // them (the residual by the compress): all 2 * live ranges (3 * live with
+  // residuals) must be pairwise disjoint.  Sorted by their
   // first byte, two ranges overlap iff some range starts before the furthest
   // end seen so far.
   std::sort(ranges.begin(), ranges.end(),
@@ -87,6 +107,8 @@ int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, in
   if (records >= (1ull << 31)) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
   std::vector<char> tab((size_t)records * sizeof(CastRec), 0);
   char* rec = tab.data();
+  std::vector<unsigned char*> rtab;
+  if (ef) rtab.reserve((size_t)records);
   // `first` elements into the segment, `count` units (vector tiles) or
   // elements (element ranges)
   auto put = [&](const Seg& s, uint32_t kind, uint64_t first, uint64_t count) {
@@ -99,6 +121,7 @@ int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, in
     r.aligned = (uint32_t)s.cut.aligned;
     std::memcpy(rec, &r, sizeof(r));
     rec += sizeof(r);
+    if (ef) rtab.push_back(s.resid + first * es);
   };
   for (const Seg& s : live) {
     if (s.cut.nunits == 0) {
@@ -117,12 +140,36 @@ int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, in
     for (uint64_t t = 0; t < s.cut.nunits / tile_units; ++t)
       put(s, kTileFull, s.cut.head + 8 * t * tile_units, tile_units);
   out.swap(tab);
+  if (ef) rout->swap(rtab);
   ti->u = u;
   ti->live = (int)live.size();
   ti->records = (uint32_t)records;
   ti->nelem = total;
   ti->bytes = out.size();
   return BYTEPS_REDUCE_OK;
+}
+
+int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                     std::vector<char>& out, CastTableInfo* ti) {
+  if (wide_dtype != kFloat32 && wide_dtype != kFloat64 && wide_dtype != kBFloat16)
+    return fail(BYTEPS_REDUCE_EDTYPE, "fp16 compression of data type %d", wide_dtype);
+  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
+  std::vector<Desc> d((size_t)nsegs);
+  for (int i = 0; i < nsegs; ++i) d[i] = {segs[i].wide, segs[i].half, nullptr, segs[i].nelem};
+  return build(d, wide_dtype, copy_vpt, out, nullptr, ti);
+}
+
+int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                        std::vector<char>& out, std::vector<unsigned char*>& resid_out,
+                        CastTableInfo* ti) {
+  if (wide_dtype != kFloat32)
+    return fail(BYTEPS_REDUCE_EDTYPE, "error-feedback compression of data type %d (FLOAT32 only)",
+                wide_dtype);
+  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
+  std::vector<Desc> d((size_t)nsegs);
+  for (int i = 0; i < nsegs; ++i)
+    d[i] = {segs[i].wide, segs[i].half, segs[i].resid, segs[i].nelem};
+  return build(d, wide_dtype, copy_vpt, out, &resid_out, ti);
 }
 
 }  // namespace bpsr

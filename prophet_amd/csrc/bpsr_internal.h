@@ -380,6 +380,17 @@ inline CastCut cast_cut(const void* h, const void* w, size_t nelem, int es) {
   if (c.nunits) c.head = hh;
   return c;
 }
+// The cut of an error-feedback compress (bpsr_cast_ef.h): cast_cut over the
+// wire operand and the f32 wide one, with the f32 residual r beside them.  The
+// vector range exists only where all three co-align: r = w (mod 16) on top of
+// cast_cut's condition; where the residual does not co-align the tensor takes
+// the element path.  A misaligned operand sets aligned = 0 for all three.
+inline CastCut cast_cut_ef(const void* h, const void* w, const void* r, size_t nelem) {
+  CastCut c = cast_cut(h, w, nelem, 4);
+  if (!c.aligned || (uintptr_t)r % 4 != 0) return CastCut{0, 0, 0};
+  if (((uintptr_t)r & 15) != ((uintptr_t)w & 15)) c.head = c.nunits = 0;
+  return c;
+}
 
 // Cast plan (byteps_reduce_cast_plan_*, bpsr_cast_table.cpp builds the table,
 // bpsr_k_cast_plan.hip runs it): one record per workgroup.  Both pointers are
@@ -409,6 +420,23 @@ hipError_t launch_cast_plan(bool compress, const CastRec* table, uint32_t nrecor
 hipError_t launch_cast_plan_bf16(bool compress, const CastRec* table, uint32_t nrecords,
                                  int wide_dtype, int divisor, int u, uint64_t out_bytes,
                                  const Tuning& tu, hipStream_t s);
+// Error-feedback compress (bpsr_cast_ef.h; bpsr_k_cast_ef.hip: fp16 wire,
+// bpsr_k_cast_ef_bf16.hip: bf16 wire): nelem f32 ELEMENTS of src plus the f32
+// residual to the wire format at dst, the residual updated in place.  Operands
+// validated by the caller (byteps_reduce_compress_ef).
+hipError_t launch_compress_ef(void* dst, void* resid, const void* src, size_t nelem,
+                              const Tuning& tu, hipStream_t s);
+hipError_t launch_compress_ef_bf16(void* dst, void* resid, const void* src, size_t nelem,
+                                   const Tuning& tu, hipStream_t s);
+// An EF plan's compress: `rtab[b]` is the residual pointer of record b, already
+// advanced like the record's own two (bpsr_cast_table.cpp); `out_bytes` is
+// what the launch writes, 6 an element.
+hipError_t launch_cast_plan_ef(const CastRec* table, unsigned char* const* rtab,
+                               uint32_t nrecords, int u, uint64_t out_bytes, const Tuning& tu,
+                               hipStream_t s);
+hipError_t launch_cast_plan_ef_bf16(const CastRec* table, unsigned char* const* rtab,
+                                    uint32_t nrecords, int u, uint64_t out_bytes,
+                                    const Tuning& tu, hipStream_t s);
 
 // Pull copy service (bpsr_copy_service.cpp, kernel in bpsr_k_service.hip):
 // a persistent kernel of a few workgroups serving copies that host threads

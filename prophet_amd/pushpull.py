@@ -39,6 +39,14 @@ widens the result into the output — dividing the fp16 value first when
 cast-plan launch before the first push and one after the last pull
 (``FP16Compressor.compress_many_into`` / ``decompress_many_into``), with the
 plans kept on the worker between iterations.
+
+``Compression.fp16_ef`` / ``Compression.bf16_ef`` (float32 tensors) keep a
+zeroed f32 residual beside the staging buffer: every push_pull casts
+``tensor + residual`` and leaves the rounding error in the residual
+(``compress_ef_into``; in ``push_pull_iteration`` one error-feedback plan
+launch).  The init push is the plain cast and leaves the residual zero; the
+decompress, and so ``average=``, is the plain compressor's.
+``Worker.residual`` / ``reset_residual`` read and zero it.
 """
 from __future__ import annotations
 
@@ -89,6 +97,9 @@ class Context:
     orig_dtype: int = 0
     orig_size: int = 0
     staging: object = None
+    # error feedback (Compression.*_ef): the f32 residual, of the tensor's
+    # kind, device and element count; None otherwise
+    residual: object = None
     init_lock: threading.Lock = field(default_factory=threading.Lock)
 
 
@@ -160,6 +171,9 @@ class Worker:
                 ctx.compressor = compression
                 ctx.orig_dtype, ctx.orig_size = int(dtype), size
                 ctx.staging = compression.wire_like(data)
+                if compression.ERROR_FEEDBACK:
+                    ctx.residual = compression.residual_like(data)
+                # the init push is the plain cast: the residual stays zero
                 data = compression.compress_into(ctx.staging, data)
                 size, dtype = _nbytes(data), DType(compression.WIRE_DTYPE)
             ctx.size, ctx.dtype = size, int(dtype)
@@ -226,7 +240,10 @@ class Worker:
             divisor = getattr(self.frontend, "size", None)
             if not divisor:
                 raise ValueError("average: the frontend does not know the worker count")
-        wire = ctx.compressor.compress_into(ctx.staging, _contiguous(tensor))
+        if ctx.residual is not None:
+            wire = ctx.compressor.compress_ef_into(ctx.staging, ctx.residual, _contiguous(tensor))
+        else:
+            wire = ctx.compressor.compress_into(ctx.staging, _contiguous(tensor))
         cmd = cantor_command(K_DEFAULT_PUSH_PULL, ctx.dtype)
         idx = range(len(ctx.parts)) if order is None else order
         for i in idx:
@@ -264,14 +281,31 @@ class Worker:
             self._pool = None
         self._cast_plans.close()
 
+    def residual(self, name: str):
+        """The error-feedback residual of a context initialised with
+        ``Compression.fp16_ef`` / ``bf16_ef`` (flat f32, the live buffer), or
+        ``None`` for any other context."""
+        return self.contexts[name].residual
+
+    def reset_residual(self, name: str) -> None:
+        """Zero the residual (after a learning-rate step or a restored
+        checkpoint, say); nothing to do for a context without one."""
+        r = self.contexts[name].residual
+        if r is None:
+            return
+        if hasattr(r, "data_ptr"):
+            r.zero_()
+        else:
+            r.fill(0)
+
     def broadcast(self, name: str, tensor, root_rank: int, output=None):
         """Broadcast as BytePS does it (byteps/torch/__init__.py:264-272: "push +
         pull ... the non-root tensors all 0", no averaging): the root pushes its
         tensor, every other rank pushes zeros, everyone pulls the sum into
         ``output`` (a new buffer like ``tensor`` if not given; the source is
         left untouched, as test_mxnet.py:116-158 requires).  The tensor must
-        have been through ``init_tensor`` — without compression: parameters
-        are broadcast exactly."""
+        have been through ``init_tensor`` — without compression, error
+        feedback included: parameters are broadcast exactly."""
         if self.contexts[name].compressor is not None:
             raise ValueError(f"{name}: broadcast needs a context without compression")
         src = tensor if self.rank == root_rank else _zeros_like(tensor)
@@ -316,6 +350,11 @@ class Worker:
             if c.compressor is not None:
                 casts.setdefault(c.compressor, []).append(c)
         for comp, cs in casts.items():
+            if comp.ERROR_FEEDBACK:
+                comp.compress_many_ef_into([c.staging for c in cs], [c.residual for c in cs],
+                                           [_contiguous(tensors[c.name]) for c in cs],
+                                           plans=self._cast_plans)
+                continue
             comp.compress_many_into([c.staging for c in cs],
                                     [_contiguous(tensors[c.name]) for c in cs],
                                     plans=self._cast_plans)
@@ -329,9 +368,11 @@ class Worker:
             for key, off, ln in c.parts:
                 self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
         for comp, cs in casts.items():
+            # an error-feedback plan decompresses too: named by its residuals
+            extra = {"residuals": [c.residual for c in cs]} if comp.ERROR_FEEDBACK else {}
             comp.decompress_many_into([_contiguous(tensors[c.name]) for c in cs],
                                       [c.staging for c in cs], divisor,
-                                      plans=self._cast_plans)
+                                      plans=self._cast_plans, **extra)
         if average:
             for c in ctxs:
                 if c.compressor is None:

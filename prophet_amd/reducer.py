@@ -62,6 +62,7 @@ EXPORTS = (
     "byteps_reduce_cast_plan_decompress", "byteps_reduce_cast_plan_destroy",
     "byteps_reduce_compress_to", "byteps_reduce_decompress_from",
     "byteps_reduce_cast_plan_create_wire",
+    "byteps_reduce_compress_ef", "byteps_reduce_cast_plan_create_ef",
 )
 
 
@@ -74,6 +75,11 @@ class BucketDesc(ctypes.Structure):
 class CastDesc(ctypes.Structure):
     """``byteps_cast_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("wide", _vp), ("half", _vp), ("nelem", _sz)]
+
+
+class CastEfDesc(ctypes.Structure):
+    """``byteps_cast_ef_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("wide", _vp), ("half", _vp), ("resid", _vp), ("nelem", _sz)]
 
 
 class ReduceError(RuntimeError):
@@ -139,6 +145,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_decompress_from.argtypes = [_vp, _vp, _sz, _int, _int, _int, _vp]
     L.byteps_reduce_cast_plan_create_wire.argtypes = [ctypes.POINTER(CastDesc), _int, _int, _int,
                                                       ctypes.POINTER(_vp)]
+    L.byteps_reduce_compress_ef.argtypes = [_vp, _vp, _vp, _sz, _int, _int, _vp]
+    L.byteps_reduce_cast_plan_create_ef.argtypes = [ctypes.POINTER(CastEfDesc), _int, _int, _int,
+                                                    ctypes.POINTER(_vp)]
     _LIB = L
     return L
 
@@ -266,13 +275,32 @@ class GpuReducer:
                                                       int(divisor), _stream_of(dst, stream)))
         return 0
 
+    def compress_ef(self, dst, resid, src, nelem: int, src_dtype: int, wire_dtype: int,
+                    stream=None) -> int:
+        """Error-feedback compress (byteps_reduce_compress_ef), one pass over
+        ``nelem`` ELEMENTS of FLOAT32: ``c = src + resid``, ``dst = wire(c)``,
+        ``resid = c - f32(dst)`` where that is finite and +0.0 elsewhere.
+        ``resid`` is f32 and updated in place; any other ``src_dtype`` is
+        EDTYPE."""
+        _fits_cast(nelem, dst, src, src_dtype)
+        _fits(int(nelem) * 4, resid)
+        _check(self.lib.byteps_reduce_compress_ef(_ptr(dst), _ptr(resid), _ptr(src), int(nelem),
+                                                  int(src_dtype), int(wire_dtype),
+                                                  _stream_of(dst, stream)))
+        return 0
+
     def cast_plan(self, segments: Sequence[tuple], wide_dtype: int,
                   wire_dtype: int = DType.FLOAT16) -> "CastPlan":
         """A whole iteration's casts as one launch each way
         (byteps_reduce_cast_plan_*): ``segments`` are ``(wide, half, nelem)``
         triples of tensors or raw pointers, all of ``wide_dtype`` with their
         2-byte sides of ``wire_dtype`` (fp16 unless named).  The plan keeps
-        the tensors it was built from alive."""
+        the tensors it was built from alive.
+
+        With ``(wide, half, nelem, resid)`` segments — all of them, FLOAT32
+        only — it is an error-feedback plan (byteps_reduce_cast_plan_create_ef):
+        ``compress`` adds each f32 residual in and leaves the rounding error
+        there, ``decompress`` is the plain one."""
         return CastPlan(self.lib, segments, wide_dtype, wire_dtype)
 
     def sum_n(self, dst, srcs: Sequence, length: int, dtype: int,
@@ -375,13 +403,39 @@ class CastPlan:
     Tensor operands are bounds-checked before the library sees them, and the
     plan holds a reference to every one: the device table carries raw
     addresses, and a write through a freed one would be a GPU fault rather
-    than an exception.  Raw pointers carry no size and stay the caller's."""
+    than an exception.  Raw pointers carry no size and stay the caller's.
+
+    Segments of four, ``(wide, half, nelem, resid)``, make an error-feedback
+    plan: ``compress`` writes per segment the bytes of
+    ``GpuReducer.compress_ef``, wire and residual; ``decompress`` is the
+    plain one and leaves the residuals alone.  The residual tensors are held
+    like the others."""
 
     def __init__(self, lib, segments, wide_dtype, wire_dtype=DType.FLOAT16):
         self.lib = lib
         self.wire_dtype = int(wire_dtype)
         self.handle = _vp()
         segments = [tuple(s) for s in segments]
+        self.error_feedback = any(len(s) == 4 for s in segments)
+        if self.error_feedback:
+            if not all(len(s) == 4 for s in segments):
+                raise ValueError("cast plan: every segment carries a residual, or none does")
+            for wide, half, nelem, resid in segments:
+                _fits_cast(nelem, half, wide, wide_dtype)
+                _fits(int(nelem) * 4, resid)
+            self._keep = segments     # keep the tensors alive, the residuals too
+            self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+            self.nsegs = len(segments)
+            descs = (CastEfDesc * max(1, len(segments)))()
+            for i, (wide, half, nelem, resid) in enumerate(segments):
+                descs[i].wide = _ptr(wide)
+                descs[i].half = _ptr(half)
+                descs[i].resid = _ptr(resid)
+                descs[i].nelem = int(nelem)
+            _check(lib.byteps_reduce_cast_plan_create_ef(descs, len(segments), int(wide_dtype),
+                                                         self.wire_dtype,
+                                                         ctypes.byref(self.handle)))
+            return
         for wide, half, nelem in segments:
             _fits_cast(nelem, half, wide, wide_dtype)
         self._keep = segments         # keep the tensors alive

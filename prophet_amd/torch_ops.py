@@ -33,6 +33,12 @@ src, divisor)``                       average's divide on the fp16 value
 ``bpsr::decompress_bf16_out(dst,      ``BF16Compressor.decompress`` fused with
 src, divisor)``                       average's divide on the bf16 value
                                       -> byteps_reduce_decompress_from
+``bpsr::compress_fp16_ef_out(dst,     error-feedback compress (``Compression.
+resid, src)``                         fp16_ef``): ``dst = fp16(src + resid)``,
+                                      ``resid`` keeps the rounding error;
+                                      mutates both -> byteps_reduce_compress_ef
+``bpsr::compress_bf16_ef_out(dst,     the same over the bf16 wire
+resid, src)``
 ====================================  ===========================================
 
 Tensors must be contiguous, on one CUDA (HIP) device, of one dtype among the
@@ -180,6 +186,47 @@ def decompress_bf16_out(dst: torch.Tensor, src: torch.Tensor, divisor: int = 1) 
                       stream=_stream(dst))
 
 
+def _check_cast_ef(dst: torch.Tensor, resid: torch.Tensor, src: torch.Tensor, wire) -> int:
+    """Operands of an error-feedback compress: ``_check_cast`` with an f32
+    ``src`` and an f32 ``resid`` of its size and device."""
+    n = _check_cast(dst, src, wire)
+    if src.dtype != torch.float32:
+        raise ReduceError(EDTYPE, f"error-feedback compression of {src.dtype} (float32 only)")
+    if resid.device.type != "cuda":
+        raise ReduceError(EARGS, f"bpsr ops need device tensors, got {resid.device}")
+    if not resid.is_contiguous():
+        raise ReduceError(EARGS, "bpsr ops need contiguous tensors")
+    if resid.dtype != torch.float32:
+        raise ReduceError(EDTYPE, f"the residual must be float32, got {resid.dtype}")
+    if resid.numel() != n or resid.device != src.device:
+        raise ReduceError(EARGS, "bpsr ops need tensors of one size and device")
+    return n
+
+
+@torch.library.custom_op("bpsr::compress_fp16_ef_out", mutates_args=("dst", "resid"),
+                         device_types="cuda")
+def compress_fp16_ef_out(dst: torch.Tensor, resid: torch.Tensor, src: torch.Tensor) -> None:
+    n = _check_cast_ef(dst, resid, src, torch.float16)
+    _red().compress_ef(dst, resid, src, n, DType.FLOAT32, DType.FLOAT16, stream=_stream(dst))
+
+
+@torch.library.custom_op("bpsr::compress_bf16_ef_out", mutates_args=("dst", "resid"),
+                         device_types="cuda")
+def compress_bf16_ef_out(dst: torch.Tensor, resid: torch.Tensor, src: torch.Tensor) -> None:
+    n = _check_cast_ef(dst, resid, src, torch.bfloat16)
+    _red().compress_ef(dst, resid, src, n, DType.FLOAT32, DType.BFLOAT16, stream=_stream(dst))
+
+
+@compress_fp16_ef_out.register_fake
+def _(dst, resid, src):
+    return None
+
+
+@compress_bf16_ef_out.register_fake
+def _(dst, resid, src):
+    return None
+
+
 @compress_bf16_out.register_fake
 def _(dst, src):
     return None
@@ -237,8 +284,10 @@ def _(srcs, mode=MODE_REFERENCE):
 
 OPS = ("sum_", "sum3_", "copy_", "sum_n_out", "sum_n",
        "compress_fp16", "compress_fp16_out", "decompress_fp16_out",
-       "compress_bf16", "compress_bf16_out", "decompress_bf16_out")
+       "compress_bf16", "compress_bf16_out", "decompress_bf16_out",
+       "compress_fp16_ef_out", "compress_bf16_ef_out")
 
 __all__ = ["sum_", "sum3_", "copy_", "sum_n_out", "sum_n", "compress_fp16",
            "compress_fp16_out", "decompress_fp16_out", "compress_bf16",
-           "compress_bf16_out", "decompress_bf16_out", "OPS"]
+           "compress_bf16_out", "decompress_bf16_out", "compress_fp16_ef_out",
+           "compress_bf16_ef_out", "OPS"]

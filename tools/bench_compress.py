@@ -59,6 +59,24 @@ own.  Both wires move the same 6 bytes per f32 element.  Gates, per direction:
   of the two candidates' spreads (max - min of the rounds).
 
 ``--wire fp16`` (the default) is everything above, unchanged.
+
+``--ef`` measures the error-feedback compress (byteps_reduce_compress_ef, wire
+``--wire``) in one run, by the same method, the candidates alternated round by
+round, at ``--elems`` f32 elements:
+
+  ef_hip     the fused pass: reads g and r, writes the wire and r' (14 B an
+             element);
+  ef_torch   torch's four-step composition on the same buffers — add, cast, cast
+             back, sub (at least 36 B an element; it leaves out the isfinite
+             select, which would only add to it);
+  plain_hip  the plain compress (6 B an element), for scale.
+
+and over the ResNet-50 table (165 segments, each with its own residual) one EF
+plan launch against 165 one-tensor launches.  Roofline fractions are on the
+bytes each candidate must move (14, 36 and 6 an element).  Gates:
+
+  ef_hip faster than ef_torch by more than the larger of the two spreads;
+  the EF plan faster than the loop by more than the larger of the two spreads.
 """
 import argparse
 import json
@@ -111,7 +129,12 @@ def main() -> int:
     p.add_argument("--out", default=None, help="append the JSON line to this file too")
     p.add_argument("--wire", choices=("fp16", "bf16"), default="fp16",
                    help="bf16: the bf16 casts alternated with the fp16 casts")
+    p.add_argument("--ef", action="store_true",
+                   help="the error-feedback compress against torch's composition and the "
+                        "plain compress; the ResNet-50 table as one EF plan")
     args = p.parse_args()
+    if args.ef:
+        return ef_mode(args)
     if args.wire == "bf16":
         return wire_mode(args)
     if args.iteration:
@@ -494,6 +517,133 @@ def wire_mode(args) -> int:
         with open(args.out, "a") as f:
             f.write(line + "\n")
     return 0 if all(gates.values()) and all(same.values()) else 1
+
+
+def ef_mode(args) -> int:
+    """The error-feedback compress: fused, torch's composition, the plain one."""
+    import torch
+
+    from prophet_amd.dtypes import DType
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    F32 = DType.FLOAT32
+    wd, tdt = {"fp16": (DType.FLOAT16, torch.float16),
+               "bf16": (DType.BFLOAT16, torch.bfloat16)}[args.wire]
+    n = args.elems
+    out = {"tool": "bench_compress", "mode": "error feedback", "wire": args.wire, "elems": n,
+           "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0),
+           "ef_resid_pol": os.environ.get("BPSR_EF_RESID_POL", "0")}
+    with step("setup", 120):
+        red = GpuReducer(device=0)
+        g = torch.Generator(device=dev).manual_seed(5)
+        sets = []
+        for _ in range(args.sets):
+            x = torch.randn(n, device=dev, generator=g) * 64
+            sets.append({"x": x, "r": x * 2.0 ** -12, "h": torch.empty(n, dtype=tdt, device=dev),
+                         "c": torch.empty(n, device=dev), "b": torch.empty(n, device=dev)})
+        torch.cuda.synchronize()
+
+    def ef_torch(k):
+        s = sets[k]
+        torch.add(s["x"], s["r"], out=s["c"])
+        s["h"].copy_(s["c"])
+        s["b"].copy_(s["h"])
+        torch.sub(s["c"], s["b"], out=s["r"])
+
+    with step("check", 120):
+        s = sets[0]
+        r0 = s["r"].clone()
+        ef_torch(0)
+        want_h, want_r = s["h"].clone(), s["r"].clone()
+        s["r"].copy_(r0)
+        red.compress_ef(s["h"], s["r"], s["x"], n, F32, wd)
+        same = {"wire": bool(torch.equal(s["h"].view(torch.int16), want_h.view(torch.int16))),
+                "residual": bool(torch.equal(s["r"].view(torch.int32), want_r.view(torch.int32)))}
+        del r0, want_h, want_r
+        torch.cuda.synchronize()
+    out["bit_equal_to_torch_composition"] = same
+
+    res = timed_rounds(torch, {
+        "ef_hip": (lambda k: red.compress_ef(sets[k]["h"], sets[k]["r"], sets[k]["x"], n, F32, wd),
+                   args.inner),
+        "ef_torch": (ef_torch, args.inner),
+        "plain_hip": (lambda k: red.compress(sets[k]["h"], sets[k]["x"], n, F32, wd), args.inner),
+    }, len(sets), args)
+    for name, per in (("ef_hip", 14), ("ef_torch", 36), ("plain_hip", 6)):
+        res[name]["bytes_per_elem"] = per
+        res[name]["roofline_frac"] = round(per * n / (res[name]["ms"] * 1e-3) / HBM_BYTES_PER_S, 4)
+    sp = max(res["ef_hip"]["spread_ms"], res["ef_torch"]["spread_ms"])
+    gates = {"ef_hip_beats_torch_composition": res["ef_torch"]["ms"] - res["ef_hip"]["ms"] > sp}
+    out.update({"results": res, "gate_spread_ms": sp,
+                "torch_over_hip": round(res["ef_torch"]["ms"] / res["ef_hip"]["ms"], 2),
+                "ef_over_plain": round(res["ef_hip"]["ms"] / res["plain_hip"]["ms"], 3)})
+    del sets
+    torch.cuda.empty_cache()
+
+    total_bytes, rows = read_table(args.table)
+    with step("setup, table", 120):
+        nelem = sum(ln // 2 for _, ln in rows)
+        tsets = []
+        for _ in range(args.sets):
+            wide = torch.randn(total_bytes // 2, device=dev, generator=g) * 64
+            resid = wide * 2.0 ** -12
+            half = torch.empty(total_bytes // 2, dtype=tdt, device=dev)
+            segs = [(wide[o // 2:(o + ln) // 2], half[o // 2:(o + ln) // 2],
+                     resid[o // 2:(o + ln) // 2]) for o, ln in rows]
+            tsets.append({"segs": segs, "half": half, "resid": resid,
+                          "plan": red.cast_plan([(w, h, w.numel(), q) for w, h, q in segs], F32,
+                                                wd)})
+        torch.cuda.synchronize()
+    with step("check, table", 120):
+        s = tsets[0]
+        r0 = s["resid"].clone()
+        s["plan"].compress()
+        got_h, got_r = s["half"].clone(), s["resid"].clone()
+        s["resid"].copy_(r0)
+        for w, h, q in s["segs"]:
+            red.compress_ef(h, q, w, w.numel(), F32, wd)
+        cover = torch.zeros(s["half"].numel(), dtype=torch.bool, device=dev)
+        for o, ln in rows:
+            cover[o // 2:(o + ln) // 2] = True
+        out["plan_bit_equal_to_per_segment_calls"] = {
+            "wire": bool(torch.equal(got_h.view(torch.int16)[cover],
+                                     s["half"].view(torch.int16)[cover])),
+            "residual": bool(torch.equal(got_r.view(torch.int32), s["resid"].view(torch.int32)))}
+        del r0, got_h, got_r, cover
+        torch.cuda.synchronize()
+
+    def loop(k):
+        for w, h, q in tsets[k]["segs"]:
+            red.compress_ef(h, q, w, w.numel(), F32, wd)
+
+    few = max(1, args.inner // 8)
+    tres = timed_rounds(torch, {"loop": (loop, few),
+                                "plan": (lambda k: tsets[k]["plan"].compress(), args.inner)},
+                        len(tsets), args)
+    tsp = max(tres["loop"]["spread_ms"], tres["plan"]["spread_ms"])
+    gates["table_plan_beats_loop"] = tres["loop"]["ms"] - tres["plan"]["ms"] > tsp
+    tres["plan"]["roofline_frac"] = round(14 * nelem / (tres["plan"]["ms"] * 1e-3)
+                                          / HBM_BYTES_PER_S, 4)
+    out.update({"table": os.path.basename(args.table), "segments": len(rows),
+                "table_elems": nelem, "table_results": tres, "table_gate_spread_ms": tsp,
+                "loop_over_plan": round(tres["loop"]["ms"] / tres["plan"]["ms"], 2),
+                "gates": gates})
+    for s in tsets:
+        s["plan"].close()
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    ok = all(gates.values()) and all(same.values()) and \
+        all(out["plan_bit_equal_to_per_segment_calls"].values())
+    return 0 if ok else 1
 
 
 def end_to_end(nelem: int, iters: int, where: str) -> dict:
