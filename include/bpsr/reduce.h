@@ -63,7 +63,10 @@ extern "C" {
  *    additive, still 5: byteps_reduce_compress_to / _decompress_from /
  *                       byteps_reduce_cast_plan_create_wire (bf16 wire)
  *    additive, still 5: byteps_reduce_compress_ef / _cast_plan_create_ef
- *                       (byteps_cast_ef_desc: error-feedback compression) */
+ *                       (byteps_cast_ef_desc: error-feedback compression)
+ *    additive, still 5: byteps_reduce_compress_sr / _cast_plan_create_sr /
+ *                       _cast_plan_compress_sr (byteps_cast_sr_desc:
+ *                       stochastic-rounding compression) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -436,6 +439,57 @@ typedef struct byteps_cast_ef_desc {
 } byteps_cast_ef_desc;
 int byteps_reduce_cast_plan_create_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype,
                                       int wire_dtype, byteps_reduce_cast_plan** out);
+
+/* Stochastic-rounding compression: the compress of the two wire formats with
+ * round-to-nearest-even replaced by rounding up with a probability equal to
+ * the dropped fraction, so that the wire value is right in expectation.  No
+ * state: dst[i] is a pure function of (the bits of src[i], key, step, i), with
+ * i the element's 0-based index in its tensor (its address plays no part).
+ *   Random bits: Philox2x32-10 with multiplier 0xD256D193 and key increment
+ *   0x9E3779B9 — ten times { hi, lo = mulhilo32(M, c0); c0, c1 = hi ^ k ^ c1,
+ *   lo; k += W } — of the counter (c0 = i >> 2, c1 = step) under k = key;
+ *   element i takes r16 = the low (i & 1 == 0) or high half of x0 (i & 2 == 0)
+ *   or x1.
+ *   BFLOAT16, u the f32 bits: w = (u + r16) >> 16 (no wrap) unless the
+ *   exponent field is 0xff, where w is byteps_reduce_compress_to's value (inf
+ *   stays inf, a NaN a NaN).  A value bf16 holds is sent unchanged; subnormals
+ *   and signed zeros are kept; a finite value above bf16's largest becomes inf
+ *   with the probability its position gives; the mean over r16 is exact.
+ *   FLOAT16: a = u & 0x7fffffff, e = a >> 23.  e == 0xff: compress_to's value.
+ *   a >= 0x47800000 (|x| >= 65536): inf.  Else lo = the fp16 value toward zero
+ *   and f = the dropped fraction to 16 bits — e >= 113: lo = (a >> 13) -
+ *   0x1c000, f = (a & 0x1fff) << 3; below: m = the 24-bit significand (hidden
+ *   bit for e > 0), sh = 126 - max(e, 1), lo = m >> sh, f = ((m << 16) >> sh)
+ *   & 0xffff (both 0 from sh = 40) — and h = min(lo + ((f + r16) >> 16),
+ *   0x7c00), w = sign | h.  The mean over r16 is exact in fp16's normal range;
+ *   in its subnormal range f is a floor, so the mean falls short by at most
+ *   2^-16 of a subnormal step.
+ *   Scope: FLOAT32 wide tensors only (EDTYPE otherwise, as for a wire other
+ *   than FLOAT16 or BFLOAT16); at most 2^34 elements a tensor (EARGS).
+ *   compress_sr: dst and src must not overlap (EARGS); a null pointer with
+ *            nelem > 0 is EARGS; nelem == 0 succeeds without a launch.
+ *            Asynchronous on `stream`.  A caller never reuses (key, step) for
+ *            different data if it wants independent bits.
+ *   cast_plan_create_sr: a cast plan (above) whose segments carry a key.  All
+ *            2 * nsegs byte ranges are pairwise disjoint (EARGS).  The plan is
+ *            the same opaque type: _cast_plan_compress_sr(plan, step) writes
+ *            per segment the bytes of one compress_sr(key of the segment,
+ *            step); _decompress is the plain decompress of `wire_dtype`;
+ *            _destroy frees both tables.  _cast_plan_compress (no step) on
+ *            such a plan is EARGS, as is _cast_plan_compress_sr on a plan
+ *            without keys. */
+int byteps_reduce_compress_sr(void* dst, const void* src, size_t nelem, int src_dtype,
+                              int wire_dtype, uint32_t key, uint32_t step, void* stream);
+typedef struct byteps_cast_sr_desc {
+  void* wide;
+  void* half;
+  size_t nelem; /* ELEMENTS */
+  uint32_t key;
+} byteps_cast_sr_desc;
+int byteps_reduce_cast_plan_create_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype,
+                                      int wire_dtype, byteps_reduce_cast_plan** out);
+int byteps_reduce_cast_plan_compress_sr(byteps_reduce_cast_plan* plan, uint32_t step,
+                                        void* stream);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

@@ -65,12 +65,33 @@ are those of the plain compressors.  The stateless ``compress(tensor)`` stays
 the plain cast: it has no residual to read or to leave the error in.
 Tensors other than float32 (f64 and the 2-byte floats included) pass through
 uncompressed, as integers do.
+
+``Compression.fp16_sr`` / ``Compression.bf16_sr`` remove the same bias without
+any state: stochastic rounding.  A float32 value is rounded up with a
+probability equal to the fraction the wire format drops, so what is delivered
+is right in expectation (a gradient of ``1 + 2^-12`` on the bf16 wire is sent
+as ``1 + 2^-7`` one time in 32, not as ``1.0`` forever).  The wire value is a
+pure function of the value's bits, a ``key``, a ``step`` and the element's
+index — Philox2x32-10 bits, no RNG state — defined by the numpy lines of
+``prophet_amd/sr.py``.  ``compress_sr_into(out, tensor, key, step)`` writes
+it: device tensors in one pass of ``torch.ops.bpsr.compress_<wire>_sr_out``
+(``prophet_amd/csrc/bpsr_cast_sr.h``, 6 bytes an element like the plain
+compress), CPU tensors and numpy arrays through ``sr.py`` itself, bit for bit
+the same.  ``compress_many_sr_into`` is the cast-plan form, one ``step`` for
+the launch and one key per tensor.  A caller never uses a ``(key, step)`` pair
+twice.  ``compress(tensor)`` stays the plain cast, ``decompress*`` is
+inherited, and tensors other than float32 pass through, as for error
+feedback.  Not covered: the server's fold still rounds its sum to the wire
+format to nearest even, so stochastic rounding makes the worker's cast
+unbiased, not the whole round.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
 
 import numpy as np
+
+from .reducer import SrKey
 
 
 def _is_torch(x) -> bool:
@@ -123,7 +144,9 @@ class CastPlanCache:
     their residual's address as well: a moved residual misses too, and the
     plan over the same tensors without residuals is another plan.  A cached plan holds its tensors: their
     memory cannot be freed, so no other tensor can appear at a cached
-    address while the plan that names it is alive."""
+    address while the plan that names it is alive.  A stochastic-rounding
+    plan's segments carry their key (``SrKey``): another key misses, and the
+    plain plan over the same tensors is another plan."""
 
     def __init__(self, capacity: int = 4):
         self.capacity = int(capacity)
@@ -137,10 +160,12 @@ class CastPlanCache:
         """The plan over ``pairs`` of flat ``(wide, half)`` device tensors on
         the current device, built on a miss.  ``wire_dtype``: the dtype of
         the ``half`` side (``DType.FLOAT16`` unless named).  Items of three,
-        ``(wide, half, residual)``, ask for the error-feedback plan."""
+        ``(wide, half, residual)``, ask for the error-feedback plan, and
+        ``(wide, half, SrKey(key))`` for the stochastic-rounding plan."""
         key = (int(wide_dtype), int(wire_dtype)) + tuple(
             (int(p[0].data_ptr()), int(p[1].data_ptr()), int(p[0].numel()))
-            + tuple(int(r.data_ptr()) for r in p[2:]) for p in pairs)
+            + tuple(("sr", int(r)) if isinstance(r, SrKey) else int(r.data_ptr()) for r in p[2:])
+            for p in pairs)
         plan = self._plans.get(key)
         if plan is not None:
             self._plans.move_to_end(key)
@@ -165,12 +190,16 @@ def _new_plan(wide_dtype: int, pairs, wire_dtype: int = 2):
                             wide_dtype, wire_dtype)
 
 
-def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None) -> None:
+def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None, keys=None,
+               step=None) -> None:
     """``pairs`` of ``(wide, half)`` tensors or arrays cast by compressor
     ``comp``: the device ones as one plan launch per (device, wide dtype, wire
     dtype), the host ones one by one.  With ``residuals`` (one per pair) the
     plans are error-feedback plans: the compress is ``compress_ef_into``'s,
-    the decompress the plain one through the same plan."""
+    the decompress the plain one through the same plan.  With ``keys`` (one
+    per pair) they are stochastic-rounding plans: the compress is
+    ``compress_sr_into``'s under ``step``, the decompress again the plain one
+    through the same plan."""
     if int(divisor) < 1:
         raise ValueError(f"divisor {divisor} < 1")
     groups: dict = {}
@@ -179,6 +208,8 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None)
         if not _on_device(wide) and not _on_device(half):
             if not compress:
                 comp.decompress_into(wide, half, divisor)
+            elif keys is not None:
+                comp.compress_sr_into(half, wide, keys[i], step)
             elif resid is None:
                 comp.compress_into(half, wide)
             else:
@@ -186,7 +217,11 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None)
             continue
         from .torch_ops import _check_cast, _check_cast_ef
         wire = comp.wire_torch_dtype()
-        if resid is None:
+        if keys is not None:
+            from .torch_ops import _check_cast_sr
+            _check_cast_sr(half, wide, wire)
+            seg = (wide.reshape(-1), half.reshape(-1), SrKey(int(keys[i]) & 0xffffffff))
+        elif resid is None:
             _check_cast(half, wide, wire)
             seg = (wide.reshape(-1), half.reshape(-1))
         else:
@@ -203,7 +238,9 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None)
                 else _new_plan(from_torch(dtype), segs, from_torch(wire))
             stream = torch.cuda.current_stream(device)
             try:
-                if compress:
+                if compress and keys is not None:
+                    plan.compress(step=step, stream=stream)
+                elif compress:
                     plan.compress(stream=stream)
                 else:
                     plan.decompress(int(divisor), stream=stream)
@@ -224,6 +261,7 @@ class Compressor:
         raise NotImplementedError
 
     ERROR_FEEDBACK = False                # compress_ef_into and a residual per tensor
+    STOCHASTIC = False                    # compress_sr_into under a key and a step
 
     @staticmethod
     def compresses(tensor) -> bool:
@@ -483,6 +521,86 @@ class BF16EFCompressor(_ErrorFeedback, BF16Compressor):
     """float32 tensors travel as bf16 with error feedback."""
 
 
+class _StochasticRounding:
+    """Stochastic rounding over a cast compressor (mixed in ahead of it):
+    round up with a probability equal to the dropped fraction, under bits
+    that are a pure function of ``(key, step, element index)``
+    (``prophet_amd/sr.py``).  float32 tensors only — everything else passes
+    through uncompressed.  ``compress(tensor)`` is inherited and stays the
+    plain, deterministic cast (it has no key or step); ``decompress*`` is
+    inherited unchanged."""
+
+    STOCHASTIC = True
+
+    @classmethod
+    def compresses(cls, tensor) -> bool:
+        return _is_f32(tensor)
+
+    @classmethod
+    def compress_sr_into(cls, out, tensor, key: int, step: int):
+        """``out = sr(tensor; key, step)``: element ``i`` rounded under 16
+        bits of Philox2x32-10(``i >> 2``, ``step``, ``key``); one pass on the
+        device; returns ``out``."""
+        if not cls.compresses(tensor):
+            raise ValueError("stochastic rounding needs a float32 tensor")
+        if _on_device(tensor):
+            import torch
+            from . import torch_ops  # noqa: F401
+            with torch.cuda.device(tensor.device):
+                getattr(torch.ops.bpsr, f"compress_{cls.NAME}_sr_out")(
+                    out.reshape(-1), tensor.reshape(-1), int(key) & 0xffffffff,
+                    int(step) & 0xffffffff)
+            return out
+        from .sr import sr_round
+        g = tensor.detach().numpy() if _is_torch(tensor) else tensor
+        if _is_torch(out):
+            import torch
+            if out.dtype != cls.wire_torch_dtype():
+                raise ValueError(f"the compressed tensor must be {cls.WIRE}, got {out.dtype}")
+            o = out.reshape(-1).view(torch.int16).numpy().view(np.uint16)
+        else:
+            o = out.reshape(-1).view(np.uint16)
+        if o.size != g.size:
+            raise ValueError("stochastic rounding: output and tensor differ in size")
+        o[:] = sr_round(g, key, step, cls.NAME)
+        return out
+
+    @classmethod
+    def compress_many_sr_into(cls, outs, tensors, keys, step: int,
+                              plans: CastPlanCache | None = None):
+        """``compress_sr_into(outs[i], tensors[i], keys[i], step)`` for every
+        i, the device tensors as one stochastic-rounding cast-plan launch per
+        device; returns ``outs``."""
+        if len(outs) != len(tensors) or len(keys) != len(tensors):
+            raise ValueError("compress_many_sr_into: as many outputs and keys as tensors")
+        for t in tensors:
+            if not cls.compresses(t):
+                raise ValueError("stochastic rounding needs float32 tensors")
+        _cast_many(cls, list(zip(tensors, outs)), True, 1, plans, keys=list(keys), step=step)
+        return outs
+
+    @classmethod
+    def decompress_many_into(cls, outs, compressed, divisor: int = 1,
+                             plans: CastPlanCache | None = None, keys=None):
+        """The inherited decompress.  ``keys`` (those given to
+        ``compress_many_sr_into`` over the same tensors) only names the plan:
+        the stochastic-rounding plan's own decompress is the plain one, so one
+        cached plan serves both directions."""
+        if len(outs) != len(compressed):
+            raise ValueError("decompress_many_into: as many outputs as compressed tensors")
+        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans,
+                   keys=None if keys is None else list(keys))
+        return outs
+
+
+class FP16SRCompressor(_StochasticRounding, FP16Compressor):
+    """float32 tensors travel as fp16, stochastically rounded."""
+
+
+class BF16SRCompressor(_StochasticRounding, BF16Compressor):
+    """float32 tensors travel as bf16, stochastically rounded."""
+
+
 class Compression:
     """Optional gradient compression used during push_pull."""
 
@@ -491,7 +609,10 @@ class Compression:
     bf16 = BF16Compressor
     fp16_ef = FP16EFCompressor
     bf16_ef = BF16EFCompressor
+    fp16_sr = FP16SRCompressor
+    bf16_sr = BF16SRCompressor
 
 
 __all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
-           "FP16EFCompressor", "BF16EFCompressor", "Compression", "CastPlanCache"]
+           "FP16EFCompressor", "BF16EFCompressor", "FP16SRCompressor", "BF16SRCompressor",
+           "Compression", "CastPlanCache"]

@@ -542,12 +542,44 @@ int byteps_reduce_compress_ef(void* dst, void* resid, const void* src, size_t ne
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "error-feedback compress kernel launch");
 }
 
+// dst (2 * nelem bytes, written) and src (4 * nelem, read) are disjoint.  All
+// checks before any HIP call; returns 1 when there is nothing to do.
+static int cast_sr_check(const void* dst, const void* src, size_t nelem, int src_dtype,
+                         int wire) {
+  if (wire != kFloat16 && wire != kBFloat16)
+    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire);
+  if (src_dtype != kFloat32)
+    return fail(BYTEPS_REDUCE_EDTYPE,
+                "stochastic-rounding compression of data type %d (FLOAT32 only)", src_dtype);
+  if (nelem == 0) return 1;
+  if (!dst || !src) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
+  if (nelem > kSrMaxElems) return fail(BYTEPS_REDUCE_EARGS, "more than 2^34 elements");
+  const uintptr_t x = (uintptr_t)dst, y = (uintptr_t)src;
+  const size_t hb = nelem * 2, wb = nelem * 4;
+  if (x > UINTPTR_MAX - hb || y > UINTPTR_MAX - wb)
+    return fail(BYTEPS_REDUCE_EARGS, "operand wraps the address space");
+  if (x < y + wb && y < x + hb) return fail(BYTEPS_REDUCE_EARGS, "dst and src overlap");
+  return BYTEPS_REDUCE_OK;
+}
+
+int byteps_reduce_compress_sr(void* dst, const void* src, size_t nelem, int src_dtype,
+                              int wire_dtype, uint32_t key, uint32_t step, void* stream) {
+  const int rc = cast_sr_check(dst, src, nelem, src_dtype, wire_dtype);
+  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
+  const auto launch = wire_dtype == kBFloat16 ? launch_compress_sr_bf16 : launch_compress_sr;
+  hipError_t e = launch(dst, src, nelem, key, step, tuning(), to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK
+                         : hip_fail(e, "stochastic-rounding compress kernel launch");
+}
+
 struct byteps_reduce_cast_plan {
   int device;
   int dtype;
   int wire;
   void* dev_table;
   void* dev_resid;  // error-feedback plans: one residual pointer per record
+  void* dev_sr;     // stochastic-rounding plans: one CastSrRec per record
+  bool sr;          // made by _create_sr (also when it has no records)
   CastTableInfo ti;
 };
 
@@ -555,16 +587,20 @@ struct byteps_reduce_cast_plan {
 // and knows the fp16 wire's three wide types, so a wide fp16 (bf16 wire) is
 // cut as its 2-byte peer.
 // Upload a built table (and, for an error-feedback plan, its residual
-// pointers: `resid` non-null) into a new plan.
+// pointers: `resid` non-null; for a stochastic-rounding plan its parallel
+// array: `sr` non-null) into a new plan.
 static int cast_plan_upload(const std::vector<char>& host,
                             const std::vector<unsigned char*>* resid, const CastTableInfo& ti,
-                            int wide_dtype, int wire, byteps_reduce_cast_plan** out) {
+                            int wide_dtype, int wire, byteps_reduce_cast_plan** out,
+                            const std::vector<CastSrRec>* sr = nullptr) {
   auto* p = new byteps_reduce_cast_plan();
   p->dtype = wide_dtype;
   p->wire = wire;
   p->ti = ti;
   p->dev_table = nullptr;
   p->dev_resid = nullptr;
+  p->dev_sr = nullptr;
+  p->sr = sr != nullptr;
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess && ti.records > 0) {
     e = hipMalloc(&p->dev_table, ti.bytes);
@@ -575,10 +611,16 @@ static int cast_plan_upload(const std::vector<char>& host,
       e = hipMalloc(&p->dev_resid, rb);
       if (e == hipSuccess) e = hipMemcpy(p->dev_resid, resid->data(), rb, hipMemcpyHostToDevice);
     }
+    if (e == hipSuccess && sr) {
+      const size_t sb = sr->size() * sizeof(CastSrRec);
+      e = hipMalloc(&p->dev_sr, sb);
+      if (e == hipSuccess) e = hipMemcpy(p->dev_sr, sr->data(), sb, hipMemcpyHostToDevice);
+    }
   }
   if (e != hipSuccess) {
     if (p->dev_table) (void)hipFree(p->dev_table);
     if (p->dev_resid) (void)hipFree(p->dev_resid);
+    if (p->dev_sr) (void)hipFree(p->dev_sr);
     delete p;
     return hip_fail(e, "cast plan table upload");
   }
@@ -610,6 +652,20 @@ int byteps_reduce_cast_plan_create_ef(const byteps_cast_ef_desc* segs, int nsegs
   return cast_plan_upload(host, &resid, ti, wide_dtype, wire_dtype, out);
 }
 
+int byteps_reduce_cast_plan_create_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype,
+                                      int wire_dtype, byteps_reduce_cast_plan** out) {
+  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
+  *out = nullptr;
+  if (wire_dtype != kFloat16 && wire_dtype != kBFloat16)
+    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire_dtype);
+  std::vector<char> host;
+  std::vector<CastSrRec> sr;
+  CastTableInfo ti;
+  const int rc = build_cast_table_sr(segs, nsegs, wide_dtype, tuning().copy_vpt, host, sr, &ti);
+  if (rc) return rc;
+  return cast_plan_upload(host, nullptr, ti, wide_dtype, wire_dtype, out, &sr);
+}
+
 int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
                                    byteps_reduce_cast_plan** out) {
   if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
@@ -632,6 +688,10 @@ static int cast_plan_launch(byteps_reduce_cast_plan* p, bool compress, int divis
                             void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  if (compress && p->sr)
+    return fail(BYTEPS_REDUCE_EARGS,
+                "a stochastic-rounding plan is compressed with a step "
+                "(byteps_reduce_cast_plan_compress_sr)");
   if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
   if (compress && p->dev_resid) {  // error-feedback plan: 2 + 4 bytes written an element
     const auto ef = p->wire == kBFloat16 ? launch_cast_plan_ef_bf16 : launch_cast_plan_ef;
@@ -651,6 +711,18 @@ int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* p, void* stream) {
   return cast_plan_launch(p, true, 1, stream);
 }
 
+int byteps_reduce_cast_plan_compress_sr(byteps_reduce_cast_plan* p, uint32_t step, void* stream) {
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (!p->sr)
+    return fail(BYTEPS_REDUCE_EARGS, "the plan carries no keys (byteps_reduce_cast_plan_create_sr)");
+  if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
+  const auto launch = p->wire == kBFloat16 ? launch_cast_plan_sr_bf16 : launch_cast_plan_sr;
+  hipError_t e = launch(static_cast<const CastRec*>(p->dev_table),
+                        static_cast<const CastSrRec*>(p->dev_sr), p->ti.records, step, p->ti.u,
+                        p->ti.nelem * 2, tuning(), to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan kernel launch");
+}
+
 int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* p, int divisor, void* stream) {
   return cast_plan_launch(p, false, divisor, stream);
 }
@@ -661,6 +733,10 @@ int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* p) {
   if (p->dev_table) e = hipFree(p->dev_table);
   if (p->dev_resid) {
     const hipError_t e2 = hipFree(p->dev_resid);
+    if (e == hipSuccess) e = e2;
+  }
+  if (p->dev_sr) {
+    const hipError_t e2 = hipFree(p->dev_sr);
     if (e == hipSuccess) e = e2;
   }
   delete p;

@@ -108,6 +108,16 @@ int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, in
 int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                         std::vector<char>& out, std::vector<unsigned char*>& resid_out,
                         CastTableInfo* ti);
+// The same for a stochastic-rounding plan (wide_dtype FLOAT32, else EDTYPE):
+// the cut is the plain one (cast_cut), the 2 * nsegs byte ranges must be
+// pairwise disjoint, a segment of more than 2^34 elements is EARGS, the
+// records are byte for byte build_cast_table's, and `sr_out` receives one
+// entry per record: the index in its segment of the record's first element
+// and the segment's key.  On an error both outputs are left as they were.
+// No HIP call.
+int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                        std::vector<char>& out, std::vector<CastSrRec>& sr_out,
+                        CastTableInfo* ti);
 
 // ------------------------------------- library queues (bpsr_queues.cpp) --
 // Per device, created on first use, never destroyed: the four library queues

@@ -1,8 +1,9 @@
 // Host arithmetic of the cast plan (byteps_reduce_cast_plan_*): the table of
 // tile records one plan launch reads, compress or decompress, and for an
-// error-feedback plan the parallel array of one residual pointer per record.
-// No HIP runtime call (tests/test_cast_table.py and tests/test_cast_table_ef.py
-// build this file with g++).
+// error-feedback plan the parallel array of one residual pointer per record,
+// for a stochastic-rounding plan that of one (first element index, key) per
+// record.  No HIP runtime call (tests/test_cast_table.py, test_cast_table_ef.py
+// and test_cast_table_sr.py build this file with g++).
 #include <algorithm>
 #include <cstring>
 
@@ -12,21 +13,23 @@ namespace bpsr {
 
 namespace {
 
+// byteps_cast_desc, byteps_cast_ef_desc and byteps_cast_sr_desc as one: resid
+// is null without error feedback, key is 0 without stochastic rounding
+struct Desc {
+  void* wide;
+  void* half;
+  void* resid;
+  size_t nelem;
+  uint32_t key;
+};
+
 struct Seg {
   unsigned char* wide;
   unsigned char* half;
   unsigned char* resid;  // error-feedback plans, else null
   uint64_t nelem;
   CastCut cut;
-};
-
-// byteps_cast_desc and byteps_cast_ef_desc as one: resid is null without
-// error feedback
-struct Desc {
-  void* wide;
-  void* half;
-  void* resid;
-  size_t nelem;
+  uint32_t key;          // stochastic-rounding plans, else 0
 };
 
 struct Range {
@@ -40,8 +43,12 @@ struct Range {
 // receives one residual pointer per record, the segment's residual base plus
 // the record's distance into the wide operand — wide and residual are both
 // f32, so the byte offsets agree.
+// sout: null but for a stochastic-rounding plan; it receives per record the
+// index in its segment of the record's first element and the segment's key,
+// and a segment of more than kSrMaxElems elements is an error.
 static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
-                 std::vector<char>& out, std::vector<unsigned char*>* rout, CastTableInfo* ti) {
+                 std::vector<char>& out, std::vector<unsigned char*>* rout,
+                 std::vector<CastSrRec>* sout, CastTableInfo* ti) {
   const int nsegs = (int)segs.size();
   const bool ef = rout != nullptr;
   const uint64_t es = (uint64_t)elem_size(wide_dtype);
@@ -57,6 +64,8 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
       return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
     if (d.nelem > SIZE_MAX / es)
       return fail(BYTEPS_REDUCE_EARGS, "segment %d: element count overflows", i);
+    if (sout && d.nelem > kSrMaxElems)
+      return fail(BYTEPS_REDUCE_EARGS, "segment %d: more than 2^34 elements", i);
     const uintptr_t w = (uintptr_t)d.wide, h = (uintptr_t)d.half;
     const size_t wb = d.nelem * es, hb = d.nelem * 2;
     if (w > UINTPTR_MAX - wb || h > UINTPTR_MAX - hb || (ef && (uintptr_t)d.resid > UINTPTR_MAX - wb))
@@ -69,7 +78,8 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
     live.push_back({static_cast<unsigned char*>(d.wide), static_cast<unsigned char*>(d.half),
                     static_cast<unsigned char*>(d.resid), (uint64_t)d.nelem,
                     ef ? cast_cut_ef(d.half, d.wide, d.resid, d.nelem)
-                       : cast_cut(d.half, d.wide, d.nelem, (int)es)});
+                       : cast_cut(d.half, d.wide, d.nelem, (int)es),
+                    d.key});
   }
   // The plan serves both directions, so every range is written in one of
   // them (the residual by the compress): all 2 * live ranges (3 * live with
@@ -109,6 +119,8 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
   char* rec = tab.data();
   std::vector<unsigned char*> rtab;
   if (ef) rtab.reserve((size_t)records);
+  std::vector<CastSrRec> stab;
+  if (sout) stab.reserve((size_t)records);
   // `first` elements into the segment, `count` units (vector tiles) or
   // elements (element ranges)
   auto put = [&](const Seg& s, uint32_t kind, uint64_t first, uint64_t count) {
@@ -122,6 +134,7 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
     std::memcpy(rec, &r, sizeof(r));
     rec += sizeof(r);
     if (ef) rtab.push_back(s.resid + first * es);
+    if (sout) stab.push_back(CastSrRec{first, s.key, 0});
   };
   for (const Seg& s : live) {
     if (s.cut.nunits == 0) {
@@ -141,6 +154,7 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
       put(s, kTileFull, s.cut.head + 8 * t * tile_units, tile_units);
   out.swap(tab);
   if (ef) rout->swap(rtab);
+  if (sout) sout->swap(stab);
   ti->u = u;
   ti->live = (int)live.size();
   ti->records = (uint32_t)records;
@@ -155,8 +169,8 @@ int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, in
     return fail(BYTEPS_REDUCE_EDTYPE, "fp16 compression of data type %d", wide_dtype);
   if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
   std::vector<Desc> d((size_t)nsegs);
-  for (int i = 0; i < nsegs; ++i) d[i] = {segs[i].wide, segs[i].half, nullptr, segs[i].nelem};
-  return build(d, wide_dtype, copy_vpt, out, nullptr, ti);
+  for (int i = 0; i < nsegs; ++i) d[i] = {segs[i].wide, segs[i].half, nullptr, segs[i].nelem, 0};
+  return build(d, wide_dtype, copy_vpt, out, nullptr, nullptr, ti);
 }
 
 int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
@@ -168,8 +182,21 @@ int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dty
   if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
   std::vector<Desc> d((size_t)nsegs);
   for (int i = 0; i < nsegs; ++i)
-    d[i] = {segs[i].wide, segs[i].half, segs[i].resid, segs[i].nelem};
-  return build(d, wide_dtype, copy_vpt, out, &resid_out, ti);
+    d[i] = {segs[i].wide, segs[i].half, segs[i].resid, segs[i].nelem, 0};
+  return build(d, wide_dtype, copy_vpt, out, &resid_out, nullptr, ti);
+}
+
+int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                        std::vector<char>& out, std::vector<CastSrRec>& sr_out,
+                        CastTableInfo* ti) {
+  if (wide_dtype != kFloat32)
+    return fail(BYTEPS_REDUCE_EDTYPE,
+                "stochastic-rounding compression of data type %d (FLOAT32 only)", wide_dtype);
+  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
+  std::vector<Desc> d((size_t)nsegs);
+  for (int i = 0; i < nsegs; ++i)
+    d[i] = {segs[i].wide, segs[i].half, nullptr, segs[i].nelem, segs[i].key};
+  return build(d, wide_dtype, copy_vpt, out, nullptr, &sr_out, ti);
 }
 
 }  // namespace bpsr

@@ -437,6 +437,30 @@ hipError_t launch_cast_plan_ef(const CastRec* table, unsigned char* const* rtab,
 hipError_t launch_cast_plan_ef_bf16(const CastRec* table, unsigned char* const* rtab,
                                     uint32_t nrecords, int u, uint64_t out_bytes,
                                     const Tuning& tu, hipStream_t s);
+// Stochastic-rounding compress (bpsr_cast_sr.h; bpsr_k_cast_sr.hip: fp16 wire,
+// bpsr_k_cast_sr_bf16.hip: bf16 wire): nelem f32 ELEMENTS of src to the wire
+// format at dst, element i rounded under 16 bits of Philox2x32-10(i >> 2,
+// step, key).  Operands validated by the caller (byteps_reduce_compress_sr).
+constexpr uint64_t kSrMaxElems = 1ull << 34;  // i >> 2 is a 32-bit counter
+hipError_t launch_compress_sr(void* dst, const void* src, size_t nelem, uint32_t key,
+                              uint32_t step, const Tuning& tu, hipStream_t s);
+hipError_t launch_compress_sr_bf16(void* dst, const void* src, size_t nelem, uint32_t key,
+                                   uint32_t step, const Tuning& tu, hipStream_t s);
+// An SR plan's parallel array, one entry per record: the index in its segment
+// of the record's first element, and the segment's key.
+struct CastSrRec {
+  uint64_t first;
+  uint32_t key;
+  uint32_t pad;
+};
+static_assert(sizeof(CastSrRec) == 16, "CastSrRec layout");
+// An SR plan's compress; `out_bytes` is what the launch writes, 2 an element.
+hipError_t launch_cast_plan_sr(const CastRec* table, const CastSrRec* stab, uint32_t nrecords,
+                               uint32_t step, int u, uint64_t out_bytes, const Tuning& tu,
+                               hipStream_t s);
+hipError_t launch_cast_plan_sr_bf16(const CastRec* table, const CastSrRec* stab,
+                                    uint32_t nrecords, uint32_t step, int u, uint64_t out_bytes,
+                                    const Tuning& tu, hipStream_t s);
 
 // Pull copy service (bpsr_copy_service.cpp, kernel in bpsr_k_service.hip):
 // a persistent kernel of a few workgroups serving copies that host threads

@@ -47,6 +47,14 @@ zeroed f32 residual beside the staging buffer: every push_pull casts
 launch).  The init push is the plain cast and leaves the residual zero; the
 decompress, and so ``average=``, is the plain compressor's.
 ``Worker.residual`` / ``reset_residual`` read and zero it.
+
+``Compression.fp16_sr`` / ``Compression.bf16_sr`` (float32 tensors) round
+stochastically and keep no state beside a counter: a context's key is ``x0`` of
+Philox2x32-10(declared key, rank, ``Worker(sr_seed=...)``) — ranks draw
+independent bits — and the step is a per-worker counter (``Worker.sr_step``)
+that advances by one for every stochastic compress call or plan launch, so no
+``(key, step)`` pair is used twice.  The init push is the plain cast; the
+decompress is the plain compressor's.
 """
 from __future__ import annotations
 
@@ -100,6 +108,8 @@ class Context:
     # error feedback (Compression.*_ef): the f32 residual, of the tensor's
     # kind, device and element count; None otherwise
     residual: object = None
+    # stochastic rounding (Compression.*_sr): the context's Philox key
+    sr_key: int = 0
     init_lock: threading.Lock = field(default_factory=threading.Lock)
 
 
@@ -107,11 +117,14 @@ class Worker:
     """One BytePS worker (its root device) talking to the server front end."""
 
     def __init__(self, rank: int, frontend: ServerFrontend,
-                 partition_bytes: int | None = None, local_size: int | None = None):
+                 partition_bytes: int | None = None, local_size: int | None = None, *,
+                 sr_seed: int = 0):
         """``partition_bytes`` / ``local_size`` default to the reference's
         environment: BYTEPS_PARTITION_BYTES (global.cc:128-130, else 4,096,000)
         and BYTEPS_LOCAL_SIZE (communicator.cc:71-77, else 1); the bound is
-        AlignTo(partition_bytes, 8 * local_size), rounded down (global.cc:135)."""
+        AlignTo(partition_bytes, 8 * local_size), rounded down (global.cc:135).
+        ``sr_seed``: the seed of this job's stochastic rounding
+        (``Compression.*_sr``); the same on every worker."""
         self.rank = rank
         self.frontend = frontend
         if partition_bytes is None:
@@ -130,9 +143,28 @@ class Worker:
         self._handles: dict[int, tuple] = {}
         self._next_handle = 0
         # push_pull_iteration's cast plans: found again by every segment's
-        # (tensor address, staging address, element count), at most 4, the
+        # (tensor address, staging address, element count), at most 8 (an
+        # iteration that mixes the six casting compressors uses six), the
         # least recently used destroyed first
-        self._cast_plans = CastPlanCache(4)
+        self._cast_plans = CastPlanCache(8)
+        # stochastic rounding: the seed the contexts' keys derive from, and
+        # the step counter — one per compress call or plan launch, under a
+        # lock (push_pull_async runs on the worker's own thread)
+        self.sr_seed = int(sr_seed) & 0xffffffff
+        self._sr_step = 0
+        self._sr_lock = threading.Lock()
+
+    @property
+    def sr_step(self) -> int:
+        """Stochastic compress calls and plan launches so far: the step the
+        next one rounds under."""
+        return self._sr_step
+
+    def _next_sr_step(self) -> int:
+        with self._sr_lock:
+            step = self._sr_step
+            self._sr_step += 1
+        return step
 
     # ------------------------------------------------------------ declare/init
     def declare(self, name: str) -> int:
@@ -173,6 +205,9 @@ class Worker:
                 ctx.staging = compression.wire_like(data)
                 if compression.ERROR_FEEDBACK:
                     ctx.residual = compression.residual_like(data)
+                if compression.STOCHASTIC:
+                    from .sr import context_key
+                    ctx.sr_key = context_key(ctx.declared_key, self.rank, self.sr_seed)
                 # the init push is the plain cast: the residual stays zero
                 data = compression.compress_into(ctx.staging, data)
                 size, dtype = _nbytes(data), DType(compression.WIRE_DTYPE)
@@ -242,6 +277,9 @@ class Worker:
                 raise ValueError("average: the frontend does not know the worker count")
         if ctx.residual is not None:
             wire = ctx.compressor.compress_ef_into(ctx.staging, ctx.residual, _contiguous(tensor))
+        elif ctx.compressor.STOCHASTIC:
+            wire = ctx.compressor.compress_sr_into(ctx.staging, _contiguous(tensor), ctx.sr_key,
+                                                   self._next_sr_step())
         else:
             wire = ctx.compressor.compress_into(ctx.staging, _contiguous(tensor))
         cmd = cantor_command(K_DEFAULT_PUSH_PULL, ctx.dtype)
@@ -305,7 +343,8 @@ class Worker:
         ``output`` (a new buffer like ``tensor`` if not given; the source is
         left untouched, as test_mxnet.py:116-158 requires).  The tensor must
         have been through ``init_tensor`` — without compression, error
-        feedback included: parameters are broadcast exactly."""
+        feedback and stochastic rounding included: parameters are broadcast
+        exactly."""
         if self.contexts[name].compressor is not None:
             raise ValueError(f"{name}: broadcast needs a context without compression")
         src = tensor if self.rank == root_rank else _zeros_like(tensor)
@@ -355,6 +394,12 @@ class Worker:
                                            [_contiguous(tensors[c.name]) for c in cs],
                                            plans=self._cast_plans)
                 continue
+            if comp.STOCHASTIC:
+                comp.compress_many_sr_into([c.staging for c in cs],
+                                           [_contiguous(tensors[c.name]) for c in cs],
+                                           [c.sr_key for c in cs], self._next_sr_step(),
+                                           plans=self._cast_plans)
+                continue
             comp.compress_many_into([c.staging for c in cs],
                                     [_contiguous(tensors[c.name]) for c in cs],
                                     plans=self._cast_plans)
@@ -369,7 +414,9 @@ class Worker:
                 self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
         for comp, cs in casts.items():
             # an error-feedback plan decompresses too: named by its residuals
-            extra = {"residuals": [c.residual for c in cs]} if comp.ERROR_FEEDBACK else {}
+            # — and a stochastic-rounding plan, named by its keys
+            extra = {"residuals": [c.residual for c in cs]} if comp.ERROR_FEEDBACK else \
+                {"keys": [c.sr_key for c in cs]} if comp.STOCHASTIC else {}
             comp.decompress_many_into([_contiguous(tensors[c.name]) for c in cs],
                                       [c.staging for c in cs], divisor,
                                       plans=self._cast_plans, **extra)

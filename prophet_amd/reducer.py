@@ -63,6 +63,8 @@ EXPORTS = (
     "byteps_reduce_compress_to", "byteps_reduce_decompress_from",
     "byteps_reduce_cast_plan_create_wire",
     "byteps_reduce_compress_ef", "byteps_reduce_cast_plan_create_ef",
+    "byteps_reduce_compress_sr", "byteps_reduce_cast_plan_create_sr",
+    "byteps_reduce_cast_plan_compress_sr",
 )
 
 
@@ -80,6 +82,17 @@ class CastDesc(ctypes.Structure):
 class CastEfDesc(ctypes.Structure):
     """``byteps_cast_ef_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("wide", _vp), ("half", _vp), ("resid", _vp), ("nelem", _sz)]
+
+
+class CastSrDesc(ctypes.Structure):
+    """``byteps_cast_sr_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("wide", _vp), ("half", _vp), ("nelem", _sz), ("key", ctypes.c_uint32)]
+
+
+class SrKey(int):
+    """A cast-plan segment's stochastic-rounding key: ``(wide, half, nelem,
+    SrKey(k))`` asks for an SR plan, where a tensor in that place is an
+    error-feedback residual."""
 
 
 class ReduceError(RuntimeError):
@@ -148,6 +161,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_compress_ef.argtypes = [_vp, _vp, _vp, _sz, _int, _int, _vp]
     L.byteps_reduce_cast_plan_create_ef.argtypes = [ctypes.POINTER(CastEfDesc), _int, _int, _int,
                                                     ctypes.POINTER(_vp)]
+    L.byteps_reduce_compress_sr.argtypes = [_vp, _vp, _sz, _int, _int, ctypes.c_uint32,
+                                            ctypes.c_uint32, _vp]
+    L.byteps_reduce_cast_plan_create_sr.argtypes = [ctypes.POINTER(CastSrDesc), _int, _int, _int,
+                                                    ctypes.POINTER(_vp)]
+    L.byteps_reduce_cast_plan_compress_sr.argtypes = [_vp, ctypes.c_uint32, _vp]
     _LIB = L
     return L
 
@@ -289,6 +307,21 @@ class GpuReducer:
                                                   _stream_of(dst, stream)))
         return 0
 
+    def compress_sr(self, dst, src, nelem: int, key: int, step: int, wire_dtype: int,
+                    src_dtype: int = DType.FLOAT32, stream=None) -> int:
+        """Stochastic-rounding compress (byteps_reduce_compress_sr) of
+        ``nelem`` ELEMENTS of FLOAT32: element ``i`` is rounded up with a
+        probability equal to the fraction the wire format drops, under 16 bits
+        of Philox2x32-10(``i >> 2``, ``step``, ``key``) — the bytes of
+        ``prophet_amd.sr.sr_round``.  ``key`` and ``step`` are taken mod 2^32;
+        any other ``src_dtype`` is EDTYPE."""
+        _fits_cast(nelem, dst, src, src_dtype)
+        _check(self.lib.byteps_reduce_compress_sr(_ptr(dst), _ptr(src), int(nelem),
+                                                  int(src_dtype), int(wire_dtype),
+                                                  int(key) & 0xffffffff, int(step) & 0xffffffff,
+                                                  _stream_of(dst, stream)))
+        return 0
+
     def cast_plan(self, segments: Sequence[tuple], wide_dtype: int,
                   wire_dtype: int = DType.FLOAT16) -> "CastPlan":
         """A whole iteration's casts as one launch each way
@@ -300,7 +333,13 @@ class GpuReducer:
         With ``(wide, half, nelem, resid)`` segments — all of them, FLOAT32
         only — it is an error-feedback plan (byteps_reduce_cast_plan_create_ef):
         ``compress`` adds each f32 residual in and leaves the rounding error
-        there, ``decompress`` is the plain one."""
+        there, ``decompress`` is the plain one.
+
+        With ``(wide, half, nelem, SrKey(key))`` segments — all of them,
+        FLOAT32 only — it is a stochastic-rounding plan
+        (byteps_reduce_cast_plan_create_sr): ``compress(step=...)`` writes per
+        segment the bytes of ``compress_sr`` under the segment's key,
+        ``decompress`` is the plain one."""
         return CastPlan(self.lib, segments, wide_dtype, wire_dtype)
 
     def sum_n(self, dst, srcs: Sequence, length: int, dtype: int,
@@ -409,13 +448,38 @@ class CastPlan:
     plan: ``compress`` writes per segment the bytes of
     ``GpuReducer.compress_ef``, wire and residual; ``decompress`` is the
     plain one and leaves the residuals alone.  The residual tensors are held
-    like the others."""
+    like the others.
+
+    Segments ``(wide, half, nelem, SrKey(key))`` make a stochastic-rounding
+    plan: ``compress(step=s)`` writes per segment the bytes of
+    ``GpuReducer.compress_sr(..., key, s, ...)``, a ``compress`` without a
+    step is refused (EARGS), and ``decompress`` is the plain one."""
 
     def __init__(self, lib, segments, wide_dtype, wire_dtype=DType.FLOAT16):
         self.lib = lib
         self.wire_dtype = int(wire_dtype)
         self.handle = _vp()
         segments = [tuple(s) for s in segments]
+        self.stochastic = any(len(s) == 4 and isinstance(s[3], SrKey) for s in segments)
+        if self.stochastic:
+            self.error_feedback = False
+            if not all(len(s) == 4 and isinstance(s[3], SrKey) for s in segments):
+                raise ValueError("cast plan: every segment carries a key, or none does")
+            for wide, half, nelem, key in segments:
+                _fits_cast(nelem, half, wide, wide_dtype)
+            self._keep = segments     # keep the tensors alive
+            self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+            self.nsegs = len(segments)
+            descs = (CastSrDesc * max(1, len(segments)))()
+            for i, (wide, half, nelem, key) in enumerate(segments):
+                descs[i].wide = _ptr(wide)
+                descs[i].half = _ptr(half)
+                descs[i].nelem = int(nelem)
+                descs[i].key = int(key) & 0xffffffff
+            _check(lib.byteps_reduce_cast_plan_create_sr(descs, len(segments), int(wide_dtype),
+                                                         self.wire_dtype,
+                                                         ctypes.byref(self.handle)))
+            return
         self.error_feedback = any(len(s) == 4 for s in segments)
         if self.error_feedback:
             if not all(len(s) == 4 for s in segments):
@@ -454,7 +518,14 @@ class CastPlan:
                                                            self.wire_dtype,
                                                            ctypes.byref(self.handle)))
 
-    def compress(self, stream=None) -> None:
+    def compress(self, stream=None, *, step: int | None = None) -> None:
+        """One launch; ``step`` (mod 2^32) for a stochastic-rounding plan and
+        for no other."""
+        if step is not None:
+            _check(self.lib.byteps_reduce_cast_plan_compress_sr(self.handle,
+                                                                int(step) & 0xffffffff,
+                                                                _stream_of(self.first, stream)))
+            return
         _check(self.lib.byteps_reduce_cast_plan_compress(self.handle,
                                                          _stream_of(self.first, stream)))
 

@@ -39,6 +39,12 @@ resid, src)``                         fp16_ef``): ``dst = fp16(src + resid)``,
                                       mutates both -> byteps_reduce_compress_ef
 ``bpsr::compress_bf16_ef_out(dst,     the same over the bf16 wire
 resid, src)``
+``bpsr::compress_fp16_sr_out(dst,     stochastic-rounding compress
+src, key, step)``                     (``Compression.fp16_sr``): the bytes of
+                                      ``prophet_amd.sr.sr_round``; mutates
+                                      ``dst`` -> byteps_reduce_compress_sr
+``bpsr::compress_bf16_sr_out(dst,     the same over the bf16 wire
+src, key, step)``
 ====================================  ===========================================
 
 Tensors must be contiguous, on one CUDA (HIP) device, of one dtype among the
@@ -217,6 +223,39 @@ def compress_bf16_ef_out(dst: torch.Tensor, resid: torch.Tensor, src: torch.Tens
     _red().compress_ef(dst, resid, src, n, DType.FLOAT32, DType.BFLOAT16, stream=_stream(dst))
 
 
+def _check_cast_sr(dst: torch.Tensor, src: torch.Tensor, wire) -> int:
+    """Operands of a stochastic-rounding compress: ``_check_cast`` with an
+    f32 ``src``."""
+    n = _check_cast(dst, src, wire)
+    if src.dtype != torch.float32:
+        raise ReduceError(EDTYPE, f"stochastic-rounding compression of {src.dtype} (float32 only)")
+    return n
+
+
+@torch.library.custom_op("bpsr::compress_fp16_sr_out", mutates_args=("dst",),
+                         device_types="cuda")
+def compress_fp16_sr_out(dst: torch.Tensor, src: torch.Tensor, key: int, step: int) -> None:
+    n = _check_cast_sr(dst, src, torch.float16)
+    _red().compress_sr(dst, src, n, key, step, DType.FLOAT16, stream=_stream(dst))
+
+
+@torch.library.custom_op("bpsr::compress_bf16_sr_out", mutates_args=("dst",),
+                         device_types="cuda")
+def compress_bf16_sr_out(dst: torch.Tensor, src: torch.Tensor, key: int, step: int) -> None:
+    n = _check_cast_sr(dst, src, torch.bfloat16)
+    _red().compress_sr(dst, src, n, key, step, DType.BFLOAT16, stream=_stream(dst))
+
+
+@compress_fp16_sr_out.register_fake
+def _(dst, src, key, step):
+    return None
+
+
+@compress_bf16_sr_out.register_fake
+def _(dst, src, key, step):
+    return None
+
+
 @compress_fp16_ef_out.register_fake
 def _(dst, resid, src):
     return None
@@ -285,9 +324,10 @@ def _(srcs, mode=MODE_REFERENCE):
 OPS = ("sum_", "sum3_", "copy_", "sum_n_out", "sum_n",
        "compress_fp16", "compress_fp16_out", "decompress_fp16_out",
        "compress_bf16", "compress_bf16_out", "decompress_bf16_out",
-       "compress_fp16_ef_out", "compress_bf16_ef_out")
+       "compress_fp16_ef_out", "compress_bf16_ef_out",
+       "compress_fp16_sr_out", "compress_bf16_sr_out")
 
 __all__ = ["sum_", "sum3_", "copy_", "sum_n_out", "sum_n", "compress_fp16",
            "compress_fp16_out", "decompress_fp16_out", "compress_bf16",
            "compress_bf16_out", "decompress_bf16_out", "compress_fp16_ef_out",
-           "compress_bf16_ef_out", "OPS"]
+           "compress_bf16_ef_out", "compress_fp16_sr_out", "compress_bf16_sr_out", "OPS"]

@@ -77,6 +77,27 @@ bytes each candidate must move (14, 36 and 6 an element).  Gates:
 
   ef_hip faster than ef_torch by more than the larger of the two spreads;
   the EF plan faster than the loop by more than the larger of the two spreads.
+
+``--sr`` measures the stochastic-rounding compress (byteps_reduce_compress_sr)
+in one run, by the same method, the candidates alternated round by round, at
+``--elems`` f32 elements:
+
+  sr_bf16, sr_fp16  the fused pass on either wire (6 B an element);
+  sr_bf16_head7     the same with the wide base one element past a 16-byte
+                    boundary: the cut's head is 7, every 16-byte vector
+                    straddles two Philox groups and draws both;
+  plain_hip         the plain compress of ``--wire`` (6 B an element);
+  ef_hip            the fused error-feedback compress of ``--wire`` (14 B);
+  sr_torch          torch's own composition for bf16 on the same buffers:
+                    randint, integer add on the viewed bits, shift, narrow (at
+                    least 26 B an element).
+
+and over the ResNet-50 table (165 segments, each under its own key) one SR plan
+launch against 165 one-tensor launches.  The first 1 Mi elements of each wire
+are compared with the numpy definition (prophet_amd/sr.py).  Gates:
+
+  sr_bf16 faster than sr_torch by more than the SUM of the two spreads;
+  the SR plan faster than the loop by more than the larger of the two spreads.
 """
 import argparse
 import json
@@ -132,7 +153,12 @@ def main() -> int:
     p.add_argument("--ef", action="store_true",
                    help="the error-feedback compress against torch's composition and the "
                         "plain compress; the ResNet-50 table as one EF plan")
+    p.add_argument("--sr", action="store_true",
+                   help="the stochastic-rounding compress against torch's composition, the "
+                        "plain and the error-feedback compress; the ResNet-50 table as one SR plan")
     args = p.parse_args()
+    if args.sr:
+        return sr_mode(args)
     if args.ef:
         return ef_mode(args)
     if args.wire == "bf16":
@@ -643,6 +669,161 @@ def ef_mode(args) -> int:
             f.write(line + "\n")
     ok = all(gates.values()) and all(same.values()) and \
         all(out["plan_bit_equal_to_per_segment_calls"].values())
+    return 0 if ok else 1
+
+
+def sr_mode(args) -> int:
+    """The stochastic-rounding compress: fused on both wires, a straddling
+    base, torch's composition, the plain and the error-feedback compress."""
+    import numpy as np
+    import torch
+
+    from prophet_amd import sr
+    from prophet_amd.dtypes import DType
+    from prophet_amd.reducer import GpuReducer, SrKey
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    F32, F16, BF16 = DType.FLOAT32, DType.FLOAT16, DType.BFLOAT16
+    wd = {"fp16": F16, "bf16": BF16}[args.wire]
+    n = args.elems
+    key = 0x1234
+    out = {"tool": "bench_compress", "mode": "stochastic rounding", "wire": args.wire, "elems": n,
+           "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    with step("setup", 120):
+        red = GpuReducer(device=0)
+        g = torch.Generator(device=dev).manual_seed(5)
+        sets = []
+        for _ in range(args.sets):
+            x = torch.randn(n + 8, device=dev, generator=g) * 64
+            h = torch.empty(n + 16, dtype=torch.int16, device=dev)
+            sets.append({"x": x[:n], "x1": x[1:1 + n], "h": h[:n], "h1": h[1:1 + n],
+                         "r": x[:n] * 2.0 ** -12, "ri": torch.empty(n, dtype=torch.int32, device=dev),
+                         "t": torch.empty(n, dtype=torch.int32, device=dev)})
+        torch.cuda.synchronize()
+    steps = [0]
+
+    def nxt():
+        steps[0] += 1
+        return steps[0]
+
+    def wire_of(t, w):
+        return t.view(torch.float16 if w == F16 else torch.bfloat16)
+
+    def sr_torch(k):
+        s = sets[k]
+        torch.randint(0, 65536, (n,), out=s["ri"], generator=g)
+        torch.add(s["x"].view(torch.int32), s["ri"], out=s["t"])
+        s["t"].bitwise_right_shift_(16)
+        s["h"].copy_(s["t"])
+
+    with step("check", 120):
+        m = min(n, 1 << 20)
+        same = {}
+        xs = sets[0]["x"][:m].cpu().numpy()
+        xs1 = sets[0]["x1"][:m].cpu().numpy()
+        for w, name in ((F16, "fp16"), (BF16, "bf16")):
+            red.compress_sr(wire_of(sets[0]["h"], w), sets[0]["x"], n, key, 3, w)
+            got = sets[0]["h"][:m].cpu().numpy().view(np.uint16)
+            same[name] = bool(np.array_equal(got, sr.sr_round(xs, key, 3, name)))
+        red.compress_sr(wire_of(sets[0]["h1"], BF16), sets[0]["x1"], n, key, 3, BF16)
+        got = sets[0]["h1"][:m].cpu().numpy().view(np.uint16)
+        same["bf16_head7"] = bool(np.array_equal(got, sr.sr_round(xs1, key, 3, "bf16")))
+        sr_torch(0)
+        torch.cuda.synchronize()
+    out["bit_equal_to_host_definition"] = same
+
+    res = timed_rounds(torch, {
+        "sr_bf16": (lambda k: red.compress_sr(wire_of(sets[k]["h"], BF16), sets[k]["x"], n, key,
+                                              nxt(), BF16), args.inner),
+        "sr_fp16": (lambda k: red.compress_sr(wire_of(sets[k]["h"], F16), sets[k]["x"], n, key,
+                                              nxt(), F16), args.inner),
+        "sr_bf16_head7": (lambda k: red.compress_sr(wire_of(sets[k]["h1"], BF16), sets[k]["x1"], n,
+                                                    key, nxt(), BF16), args.inner),
+        "plain_hip": (lambda k: red.compress(wire_of(sets[k]["h"], wd), sets[k]["x"], n, F32, wd),
+                      args.inner),
+        "ef_hip": (lambda k: red.compress_ef(wire_of(sets[k]["h"], wd), sets[k]["r"], sets[k]["x"],
+                                             n, F32, wd), args.inner),
+        "sr_torch": (sr_torch, args.inner),
+    }, len(sets), args)
+    for name, per in (("sr_bf16", 6), ("sr_fp16", 6), ("sr_bf16_head7", 6), ("plain_hip", 6),
+                      ("ef_hip", 14), ("sr_torch", 26)):
+        res[name]["bytes_per_elem"] = per
+        res[name]["roofline_frac"] = round(per * n / (res[name]["ms"] * 1e-3) / HBM_BYTES_PER_S, 4)
+    sp = res["sr_bf16"]["spread_ms"] + res["sr_torch"]["spread_ms"]
+    gates = {"sr_hip_beats_torch_composition": res["sr_torch"]["ms"] - res["sr_bf16"]["ms"] > sp}
+    psp = max(res["sr_bf16"]["spread_ms"], res["sr_fp16"]["spread_ms"],
+              res["plain_hip"]["spread_ms"])
+    out.update({"results": res, "gate_spread_sum_ms": round(sp, 5),
+                "torch_over_sr": round(res["sr_torch"]["ms"] / res["sr_bf16"]["ms"], 2),
+                "sr_bf16_over_plain": round(res["sr_bf16"]["ms"] / res["plain_hip"]["ms"], 3),
+                "sr_fp16_over_plain": round(res["sr_fp16"]["ms"] / res["plain_hip"]["ms"], 3),
+                "sr_bf16_over_ef": round(res["sr_bf16"]["ms"] / res["ef_hip"]["ms"], 3),
+                "head7_over_sr_bf16": round(res["sr_bf16_head7"]["ms"] / res["sr_bf16"]["ms"], 3),
+                "within_spreads_of_plain": {
+                    w: abs(res[f"sr_{w}"]["ms"] - res["plain_hip"]["ms"]) <= psp
+                    for w in ("bf16", "fp16")}})
+    del sets
+    torch.cuda.empty_cache()
+
+    total_bytes, rows = read_table(args.table)
+    tdt = torch.float16 if wd == F16 else torch.bfloat16
+    with step("setup, table", 120):
+        nelem = sum(ln // 2 for _, ln in rows)
+        tsets = []
+        for _ in range(args.sets):
+            wide = torch.randn(total_bytes // 2, device=dev, generator=g) * 64
+            half = torch.empty(total_bytes // 2, dtype=tdt, device=dev)
+            segs = [(wide[o // 2:(o + ln) // 2], half[o // 2:(o + ln) // 2], 1000 + i)
+                    for i, (o, ln) in enumerate(rows)]
+            tsets.append({"segs": segs, "half": half,
+                          "plan": red.cast_plan([(w, h, w.numel(), SrKey(k)) for w, h, k in segs],
+                                                F32, wd)})
+        torch.cuda.synchronize()
+    with step("check, table", 120):
+        s = tsets[0]
+        s["plan"].compress(step=9)
+        got_h = s["half"].clone()
+        for w, h, k in s["segs"]:
+            red.compress_sr(h, w, w.numel(), k, 9, wd)
+        cover = torch.zeros(s["half"].numel(), dtype=torch.bool, device=dev)
+        for o, ln in rows:
+            cover[o // 2:(o + ln) // 2] = True
+        out["plan_bit_equal_to_per_segment_calls"] = bool(
+            torch.equal(got_h.view(torch.int16)[cover], s["half"].view(torch.int16)[cover]))
+        del got_h, cover
+        torch.cuda.synchronize()
+
+    def loop(k):
+        st = nxt()
+        for w, h, kk in tsets[k]["segs"]:
+            red.compress_sr(h, w, w.numel(), kk, st, wd)
+
+    few = max(1, args.inner // 8)
+    tres = timed_rounds(torch, {"loop": (loop, few),
+                                "plan": (lambda k: tsets[k]["plan"].compress(step=nxt()),
+                                         args.inner)},
+                        len(tsets), args)
+    tsp = max(tres["loop"]["spread_ms"], tres["plan"]["spread_ms"])
+    gates["table_plan_beats_loop"] = tres["loop"]["ms"] - tres["plan"]["ms"] > tsp
+    tres["plan"]["roofline_frac"] = round(6 * nelem / (tres["plan"]["ms"] * 1e-3)
+                                          / HBM_BYTES_PER_S, 4)
+    out.update({"table": os.path.basename(args.table), "segments": len(rows),
+                "table_elems": nelem, "table_results": tres, "table_gate_spread_ms": tsp,
+                "loop_over_plan": round(tres["loop"]["ms"] / tres["plan"]["ms"], 2),
+                "gates": gates})
+    for s in tsets:
+        s["plan"].close()
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    ok = all(gates.values()) and all(same.values()) and out["plan_bit_equal_to_per_segment_calls"]
     return 0 if ok else 1
 
 
