@@ -75,8 +75,8 @@ pure function of the value's bits, a ``key``, a ``step`` and the element's
 index — Philox2x32-10 bits, no RNG state — defined by the numpy lines of
 ``prophet_amd/sr.py``.  ``compress_sr_into(out, tensor, key, step)`` writes
 it: device tensors in one pass of ``torch.ops.bpsr.compress_<wire>_sr_out``
-(``prophet_amd/csrc/bpsr_cast_sr.h``, 6 bytes an element like the plain
-compress), CPU tensors and numpy arrays through ``sr.py`` itself, bit for bit
+(the rounding scheme of ``prophet_amd/csrc/bpsr_cast_sr.h`` in the plain
+compress's kernel, 6 bytes an element like it), CPU tensors and numpy arrays through ``sr.py`` itself, bit for bit
 the same.  ``compress_many_sr_into`` is the cast-plan form, one ``step`` for
 the launch and one key per tensor.  A caller never uses a ``(key, step)`` pair
 twice.  ``compress(tensor)`` stays the plain cast, ``decompress*`` is

@@ -2,13 +2,19 @@
 // (bpsr_cast_single.h; bpsr_k_cast.hip for the fp16 wire, bpsr_k_cast_bf16.hip
 // for the bf16 wire) and the cast plan (bpsr_cast_plan.h; bpsr_k_cast_plan.hip,
 // bpsr_k_cast_plan_bf16.hip): the wide-side element types, the narrow (wire)
-// side's two formats, one element's arithmetic, the full tile, the guarded
-// partial tile and the element loop.  What the arithmetic is and why the full
-// tile re-deals its lanes: bpsr_k_cast.hip, bpsr_k_cast_bf16.hip.
+// side's two formats, one element's arithmetic, the compress's rounding scheme
+// (plain here; error feedback in bpsr_cast_ef.h, stochastic rounding in
+// bpsr_cast_sr.h), the full tile, the guarded partial tile and the element
+// loop, each written once over the scheme; and, host side, the store policy,
+// the tile-size / policy dispatch and the launch wrapper of every cast kernel.
+// What the arithmetic is and why the full tile re-deals its lanes:
+// bpsr_k_cast.hip, bpsr_k_cast_bf16.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "bpsr_kernels_impl.h"
 
@@ -119,6 +125,13 @@ __device__ __forceinline__ typename W::E decompress_elem(uint16_t h, bool div, f
 }
 
 template <class W, class N>
+__device__ __forceinline__ void decompress_unit(const vec16& h, bool div, float fd, vec16* o) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    W::put(o, e, decompress_elem<W, N>((uint16_t)(h.w[e >> 1] >> ((e & 1) * 16)), div, fd));
+}
+
+template <class W, class N>
 __device__ __forceinline__ vec16 compress_unit(const vec16* x) {
   vec16 o;
 #pragma unroll
@@ -128,19 +141,73 @@ __device__ __forceinline__ vec16 compress_unit(const vec16* x) {
   return o;
 }
 
-template <class W, class N>
-__device__ __forceinline__ void decompress_unit(const vec16& h, bool div, float fd, vec16* o) {
+// Rounding scheme S of the f32 compress: what a lane does with the f32
+// elements it loaded.  The tiles, the element loop, the two kernels and the
+// launches are written once over it.  A scheme supplies
+//   Narrow       the wire format
+//   State        wave-uniform; at(n) moves it n elements on, to a range's start
+//   kSide        a read-write f32 operand, side(st), lies beside the wide one
+//                in the wide operand's vector layout and at its offsets
+//   vec          one 16-byte vector of f32 to its 4 wire values in c[0..1];
+//                vi: the vector's index in the state's range, q: the side
+//                operand's vector, updated in place
+//   elem         one element, e: its index in the state's range
+//   Single, Plan the kernels' arguments; state() reads the State out of them,
+//                pin() keeps the scheme's own scalars in SGPRs
+//   kPlanSide    a plan has an array parallel to its records, plan_side(),
+//                which the record prefetch's third lane touches
+// CastPlain: N::from_f32 per element, no side operand and no state.  The other
+// wide dtypes and every decompress take no hook (compress_elem,
+// decompress_elem) and run under CastPlain.  Error feedback and stochastic
+// rounding: bpsr_cast_ef.h, bpsr_cast_sr.h.
+template <class N>
+struct CastPlain {
+  using Narrow = N;
+  static constexpr bool kSide = false, kPlanSide = false;
+  struct State {
+    __device__ __forceinline__ State at(uint64_t) const { return *this; }
+  };
+  struct Single {
+    CastArgs a;
+  };
+  struct Plan {
+    const CastRec* table;
+    uint32_t nrecords;
+    int divisor;
+  };
+  __device__ __forceinline__ static State state(const Single&) { return {}; }
+  __device__ __forceinline__ static State state(const Plan&, uint32_t) { return {}; }
+  __device__ __forceinline__ static void pin(const Single& p, const State&) {
+    asm volatile("" ::"s"(p.a.divisor));
+  }
+  __device__ __forceinline__ static void pin(const Plan& p, const State&) {
+    asm volatile("" ::"s"(p.divisor));
+  }
+  __device__ __forceinline__ static int divisor(const Plan& p) { return p.divisor; }
+  __device__ __forceinline__ static void vec(const State&, const vec16& x, vec16*, uint32_t,
+                                             uint32_t* c) {
 #pragma unroll
-  for (int e = 0; e < 8; ++e)
-    W::put(o, e, decompress_elem<W, N>((uint16_t)(h.w[e >> 1] >> ((e & 1) * 16)), div, fd));
-}
+    for (int k = 0; k < 2; ++k)
+      c[k] = (uint32_t)N::from_f32(x.w[2 * k]) | ((uint32_t)N::from_f32(x.w[2 * k + 1]) << 16);
+  }
+  __device__ __forceinline__ static uint16_t elem(const State&, uint32_t g, uint64_t, bool) {
+    return N::from_f32(g);
+  }
+};
+
+// Whether the compress of wide side W goes through the scheme's hooks.
+template <class W>
+constexpr bool kHooked = std::is_same<W, Wide<kFloat32>>::value;
 
 // Full tile: units [0, kBlock * U) of the tile whose first bytes are h0 (narrow
-// side) and w0 (wide side); lane handles units lane + j * kBlock.  One buffer
-// descriptor per operand sized to the tile, 32-bit lane offsets.
-template <class W, class N, bool COMPRESS, int U, int POL>
+// side) and w0 (wide side), `st` at its first element; lane handles units
+// lane + j * kBlock.  One buffer descriptor per operand sized to the tile,
+// 32-bit lane offsets.
+template <class S, class W, bool COMPRESS, int U, int POL>
 __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigned char* dst,
-                                               bool div, float fd, int lane) {
+                                               const typename S::State& st, bool div, float fd,
+                                               int lane) {
+  using N = typename S::Narrow;
   constexpr int kAux = 2;                            // loads: nt
   constexpr int kStAux = POL == kPolWt ? 16 : kAux;  // stores: sc1 (write-through) or nt
   constexpr int KV = W::kVecs;
@@ -153,29 +220,46 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
   if constexpr (COMPRESS && KV > 1) {
     // The mirror image of the decompress below: load instruction v reads the
     // wave's input vectors v * 64 + l (1 KiB contiguous), each lane rounds the
-    // elements it loaded, and lane l collects the fp16 values of ITS unit
-    // (vectors l * KV + s, all in load l / (64 / KV)) from the lanes that
-    // hold them.  Every element is rounded exactly once, by the lane that
-    // loaded it.
-    constexpr int EPV = 8 / KV, DW = EPV / 2;  // elements / fp16 dwords per input vector
+    // elements it loaded into c[v] — through the scheme's hook for f32 — and
+    // stores a side vector back at the offset it was loaded from, and lane l
+    // collects the 2-byte values of ITS unit (vectors l * KV + s, all in load
+    // l / (64 / KV)) from the lanes that hold them.  Every load of the tile,
+    // the side operand's included, is issued before the first use; every
+    // element is rounded exactly once, by the lane that loaded it.
+    constexpr bool kSide = kHooked<W> && S::kSide;
+    constexpr int DW = 4 / KV;
     const int l = lane & 63, wave0 = lane & ~63;
-    vec16 x[U][KV];
+    unsigned char* side = nullptr;
+    if constexpr (kSide) side = S::side(st);
+    const auto rr = __builtin_amdgcn_make_buffer_rsrc(side, 0, kWBytes, 0x00020000);
+    vec16 x[U][KV], q[U][KV];
 #pragma unroll
     for (int j = 0; j < U; ++j)
 #pragma unroll
-      for (int v = 0; v < KV; ++v)
-        x[j][v] = bitcast<vec16>(__builtin_amdgcn_raw_buffer_load_b128(
-            rs, ((j * kBlock + wave0) * KV + v * 64 + l) * 16, 0, kAux));
-    const int vi = l / (64 / KV);
+      for (int v = 0; v < KV; ++v) {
+        const int off = ((j * kBlock + wave0) * KV + v * 64 + l) * 16;
+        x[j][v] = bitcast<vec16>(__builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, kAux));
+        if constexpr (kSide)
+          q[j][v] = bitcast<vec16>(__builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, kAux));
+      }
+    const int vl = l / (64 / KV);
 #pragma unroll
     for (int j = 0; j < U; ++j) {
       uint32_t c[KV][DW];
 #pragma unroll
-      for (int v = 0; v < KV; ++v)
+      for (int v = 0; v < KV; ++v) {
+        const int vi = (j * kBlock + wave0) * KV + v * 64 + l;
+        if constexpr (kHooked<W>) {
+          S::vec(st, x[j][v], &q[j][v], (uint32_t)vi, c[v]);
+        } else {
 #pragma unroll
-        for (int k = 0; k < DW; ++k)
-          c[v][k] = (uint32_t)compress_elem<W, N>(W::get(&x[j][v], 2 * k)) |
-                    ((uint32_t)compress_elem<W, N>(W::get(&x[j][v], 2 * k + 1)) << 16);
+          for (int k = 0; k < DW; ++k)
+            c[v][k] = (uint32_t)compress_elem<W, N>(W::get(&x[j][v], 2 * k)) |
+                      ((uint32_t)compress_elem<W, N>(W::get(&x[j][v], 2 * k + 1)) << 16);
+        }
+        if constexpr (kSide)
+          __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(q[j][v]), rr, vi * 16, 0, kStAux);
+      }
       vec16 o;
 #pragma unroll
       for (int s = 0; s < KV; ++s) {
@@ -186,7 +270,7 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
 #pragma unroll
           for (int v = 1; v < KV; ++v) {
             const uint32_t t = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)c[v][k]);
-            r = vi == v ? t : r;
+            r = vl == v ? t : r;
           }
           o.w[s * DW + k] = r;
         }
@@ -195,6 +279,7 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
                                              kStAux);
     }
   } else if constexpr (COMPRESS) {
+    // a 2-byte wide side: the lane's one vector is its unit, nothing to re-deal
     vec16 x[U][KV];
 #pragma unroll
     for (int j = 0; j < U; ++j)
@@ -268,18 +353,32 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
 }
 
 // The partial last tile: units [u0, nunits) of the vector range (src / dst
-// already advanced to the range); a unit past nunits is neither read nor
-// written.
-template <class W, class N, bool COMPRESS, int U>
+// already advanced to the range, `st` at its first element); a unit past
+// nunits is neither read nor written.
+template <class S, class W, bool COMPRESS, int U>
 __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsigned char* dst,
-                                                  uint64_t u0, uint64_t nunits, bool div,
-                                                  float fd, int lane) {
+                                                  const typename S::State& st, uint64_t u0,
+                                                  uint64_t nunits, bool div, float fd, int lane) {
+  using N = typename S::Narrow;
   constexpr int KV = W::kVecs;
 #pragma unroll
   for (int j = 0; j < U; ++j) {
     const uint64_t u = u0 + (uint64_t)j * kBlock + lane;
     if (u >= nunits) continue;
-    if constexpr (COMPRESS) {
+    if constexpr (COMPRESS && kHooked<W>) {
+      vec16 x[KV], q[KV], o;
+#pragma unroll
+      for (int v = 0; v < KV; ++v) {
+        x[v] = ld16<true>(src + (u * KV + v) * 16);
+        if constexpr (S::kSide) q[v] = ld16<true>(S::side(st) + (u * KV + v) * 16);
+      }
+#pragma unroll
+      for (int v = 0; v < KV; ++v) {
+        S::vec(st, x[v], &q[v], (uint32_t)(u * KV + v), &o.w[2 * v]);
+        if constexpr (S::kSide) st16<true>(S::side(st) + (u * KV + v) * 16, q[v]);
+      }
+      st16<true>(dst + u * 16, o);
+    } else if constexpr (COMPRESS) {
       vec16 x[KV];
 #pragma unroll
       for (int v = 0; v < KV; ++v) x[v] = ld16<true>(src + (u * KV + v) * 16);
@@ -293,21 +392,62 @@ __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsi
   }
 }
 
-// Elements [0, head) and [tail_begin, n_elems), one per thread.
-template <class W, class N, bool COMPRESS>
-__device__ __forceinline__ void cast_elements(const CastArgs& a, bool div, float fd, uint64_t t,
-                                              uint64_t stride) {
+// Elements [0, head) and [tail_begin, n_elems), one per thread; `st` at
+// element 0.  a.aligned covers every operand, a side operand included.
+template <class S, class W, bool COMPRESS>
+__device__ __forceinline__ void cast_elements(const CastArgs& a, const typename S::State& st,
+                                              bool div, float fd, uint64_t t, uint64_t stride) {
+  using N = typename S::Narrow;
   using E = typename W::E;
   const bool al = a.aligned != 0;
   const uint64_t n_scalar = a.head + (a.n_elems - a.tail_begin);
   for (uint64_t s = t; s < n_scalar; s += stride) {
     const uint64_t e = s < a.head ? s : a.tail_begin + (s - a.head);
-    if constexpr (COMPRESS)
+    if constexpr (COMPRESS && kHooked<W>)
+      st_e<uint16_t>(a.dst + e * 2, S::elem(st, ld_e<E>(a.src + e * sizeof(E), al), e, al), al);
+    else if constexpr (COMPRESS)
       st_e<uint16_t>(a.dst + e * 2, compress_elem<W, N>(ld_e<E>(a.src + e * sizeof(E), al)), al);
     else
       st_e<E>(a.dst + e * sizeof(E),
               decompress_elem<W, N>(ld_e<uint16_t>(a.src + e * 2, al), div, fd), al);
   }
+}
+
+// ---------------------------------------------------------- host side ----
+// Store policy of a streaming launch (every byte is read once) that writes
+// `out_bytes`: write-through below Tuning::wt_max_bytes, nt from there on.
+inline int cast_store_pol(const Tuning& tu, uint64_t out_bytes) {
+  Tuning tn = tu;
+  tn.nt = 1;
+  return cache_pol(tn, out_bytes);
+}
+
+// f(U, POL) with the tile size u (1, 2 or 4) and the store policy as
+// std::integral_constants.
+template <class F>
+static hipError_t cast_dispatch(int u, int pol, F&& f) {
+  auto with_pol = [&](auto p) {
+    switch (u) {
+      case 1: return f(std::integral_constant<int, 1>{}, p);
+      case 2: return f(std::integral_constant<int, 2>{}, p);
+      default: return f(std::integral_constant<int, 4>{}, p);
+    }
+  };
+  return pol == kPolWt ? with_pol(std::integral_constant<int, kPolWt>{})
+                       : with_pol(std::integral_constant<int, kPolNt>{});
+}
+
+// One workgroup per tile or record; residency Tuning::copy_occ from
+// `occ_min_tiles` workgroups on.
+template <auto KERNEL, class A>
+static hipError_t launch_cast_kernel(const A& args, uint64_t grid, uint32_t occ_min_tiles,
+                                     const Tuning& tu, hipStream_t s) {
+  static KernelAttr attr;
+  const hipError_t lds_ok = allow_lds(attr, reinterpret_cast<const void*>(KERNEL));
+  if (lds_ok != hipSuccess) return lds_ok;
+  const int occ = grid >= occ_min_tiles ? tu.copy_occ : 0;
+  hipLaunchKernelGGL(KERNEL, dim3((uint32_t)grid), dim3(kBlock), occ_lds_bytes(occ), s, args);
+  return hipGetLastError();
 }
 
 }  // namespace bpsr

@@ -20,10 +20,10 @@
 // fraction to 16 bits; sr_round<NarrowF16> below is sr.py's sr_fp16 line by
 // line.
 //
-// The tile's shape is bpsr_cast_ef.h's without the residual: the KV = 2 full
-// tile with every load issued before the first use, the lane that loaded a
-// 16-byte f32 vector rounds its 4 elements, and only the 2-byte values are
-// re-dealt (ds_bpermute).  A lane's vector covers elements i0 .. i0 + 3 of the
+// The tile is the plain compress's (bpsr_cast_impl.h): the KV = 2 full tile
+// with every load issued before the first use, the lane that loaded a 16-byte
+// f32 vector rounds its 4 elements, and only the 2-byte values are re-dealt.
+// A lane's vector covers elements i0 .. i0 + 3 of the
 // tensor, i0 = first + 4 * (the vector's index in the range).  Where `first`
 // (the cut's head) is a multiple of 4 that is one Philox group; where it is
 // not (a wide base 4-byte but not 16-byte aligned) the vector straddles groups
@@ -32,13 +32,16 @@
 // launch's tensor (of a plan's record), so the second Philox call sits behind
 // a wave-uniform branch.
 //
-// A template on N, instantiated per wire format in bpsr_k_cast_sr.hip (fp16)
-// and bpsr_k_cast_sr_bf16.hip (bf16).
+// This header holds what stochastic rounding adds — the random bits, one
+// element's and one vector's rounding and the scheme that hands them to the
+// shared compress path.  The tiles are bpsr_cast_impl.h's, the kernels and
+// launches bpsr_cast_single.h's and bpsr_cast_plan.h's.  A template on N,
+// instantiated per wire format in bpsr_k_cast_sr.hip (fp16) and
+// bpsr_k_cast_sr_bf16.hip (bf16).
 #pragma once
 
-#include <cstring>
-
-#include "bpsr_cast_impl.h"
+#include "bpsr_cast_plan.h"
+#include "bpsr_cast_single.h"
 
 namespace bpsr {
 
@@ -123,262 +126,75 @@ __device__ __forceinline__ void sr_vec(const vec16& v, uint64_t x, uint32_t* c) 
 }
 
 // What every tile needs beside its two operands: the element index `first` of
-// the range's first element in its tensor, as its Philox group and the shift
-// within it, and the key and step.  All wave-uniform.
+// the range's first element in its tensor, the key and the step.  All
+// wave-uniform.
 struct SrSeed {
-  uint32_t q0;  // first >> 2
-  uint32_t sh;  // first & 3
+  uint64_t first;
   uint32_t key, step;
+  __device__ __forceinline__ SrSeed at(uint64_t n) const { return SrSeed{first + n, key, step}; }
 };
-__device__ __forceinline__ SrSeed sr_seed(uint64_t first, uint32_t key, uint32_t step) {
-  return SrSeed{(uint32_t)(first >> 2), (uint32_t)first & 3u, key, step};
-}
 
-// Full tile: cast_tile_full's KV = 2 compress; vector `vec` of the tile holds
-// elements first + 4 * vec .. + 3 of the tensor.
-template <class N, int U, int POL>
-__device__ __forceinline__ void cast_sr_tile_full(const unsigned char* src, unsigned char* dst,
-                                                  const SrSeed& sd, int lane) {
-  constexpr int kAux = 2;                            // loads: nt
-  constexpr int kStAux = POL == kPolWt ? 16 : kAux;  // stores: sc1 or nt
-  constexpr int KV = 2, DW = 2;
-  constexpr int kHBytes = kBlock * U * 16, kWBytes = kHBytes * KV;
-  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(src), 0, kWBytes,
-                                                    0x00020000);
-  const auto rd = __builtin_amdgcn_make_buffer_rsrc(dst, 0, kHBytes, 0x00020000);
-  const int l = lane & 63, wave0 = lane & ~63;
-  vec16 x[U][KV];
-#pragma unroll
-  for (int j = 0; j < U; ++j)
-#pragma unroll
-    for (int v = 0; v < KV; ++v)
-      x[j][v] = bitcast<vec16>(__builtin_amdgcn_raw_buffer_load_b128(
-          rs, ((j * kBlock + wave0) * KV + v * 64 + l) * 16, 0, kAux));
-  const int vi = l / (64 / KV);
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    uint32_t c[KV][DW];
-#pragma unroll
-    for (int v = 0; v < KV; ++v) {
-      const uint32_t vec = (uint32_t)((j * kBlock + wave0) * KV + v * 64 + l);
-      sr_vec<N>(x[j][v], sr_bits4(sd.q0 + vec, sd.sh, sd.key, sd.step), c[v]);
-    }
-    // the re-deal of cast_tile_full: lane l collects the 2-byte values of ITS
-    // unit (input vectors l * KV + s) from the lanes that rounded them
-    vec16 o;
-#pragma unroll
-    for (int s = 0; s < KV; ++s) {
-      const int from = ((l * KV + s) & 63) * 4;
-#pragma unroll
-      for (int k = 0; k < DW; ++k) {
-        const uint32_t t0 = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)c[0][k]);
-        const uint32_t t1 = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)c[1][k]);
-        o.w[s * DW + k] = vi == 1 ? t1 : t0;
-      }
-    }
-    __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(o), rd, (j * kBlock + lane) * 16, 0,
-                                           kStAux);
-  }
-}
-
-// The partial last tile: units [u0, nunits) of the vector range (both pointers
-// already advanced to the range, whose first element is `sd`'s); a unit past
-// nunits is neither read nor written.
-template <class N, int U>
-__device__ __forceinline__ void cast_sr_tile_guarded(const unsigned char* src, unsigned char* dst,
-                                                     uint64_t u0, uint64_t nunits,
-                                                     const SrSeed& sd, int lane) {
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    const uint64_t u = u0 + (uint64_t)j * kBlock + lane;
-    if (u >= nunits) continue;
-    vec16 x[2], o;
-#pragma unroll
-    for (int v = 0; v < 2; ++v) x[v] = ld16<true>(src + (u * 2 + v) * 16);
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-      sr_vec<N>(x[v], sr_bits4(sd.q0 + (uint32_t)(u * 2 + v), sd.sh, sd.key, sd.step),
-                &o.w[2 * v]);
-    st16<true>(dst + u * 16, o);
-  }
-}
-
-// Elements [0, head) and [tail_begin, n_elems), one per thread; element e of
-// the range is element first + e of its tensor.
+// The scheme (bpsr_cast_impl.h): the state is the seed; vector vi of a range
+// holds elements first + 4 * vi .. + 3 of the tensor, Philox group
+// (first >> 2) + vi shifted by first & 3.  The kernels' extra arguments are
+// the key and the step; a plan's parallel array gives each record its first
+// element's index in its segment and the segment's key.
 template <class N>
-__device__ __forceinline__ void cast_sr_elements(const CastArgs& a, uint64_t first, uint32_t key,
-                                                 uint32_t step, uint64_t t, uint64_t stride) {
-  const bool al = a.aligned != 0;
-  const uint64_t n_scalar = a.head + (a.n_elems - a.tail_begin);
-  for (uint64_t s = t; s < n_scalar; s += stride) {
-    const uint64_t e = s < a.head ? s : a.tail_begin + (s - a.head);
-    const uint16_t w =
-        sr_round<N>(ld_e<uint32_t>(a.src + e * 4, al), sr_bits1(first + e, key, step));
-    st_e<uint16_t>(a.dst + e * 2, w, al);
+struct CastSr {
+  using Narrow = N;
+  static constexpr bool kSide = false, kPlanSide = true;
+  using State = SrSeed;
+  struct Single {
+    CastArgs a;
+    uint32_t key, step;
+  };
+  struct Plan {
+    const CastRec* table;
+    const CastSrRec* stab;
+    uint32_t nrecords;
+    uint32_t step;
+  };
+  __device__ __forceinline__ static State state(const Single& p) { return State{0, p.key, p.step}; }
+  __device__ __forceinline__ static State state(const Plan& p, uint32_t b) {
+    return State{p.stab[b].first, p.stab[b].key, p.step};
   }
-}
-
-// ------------------------------------------------------- single launch ----
-// cast_kernel's shape: workgroup 0 takes the partial tile and the element
-// work, the full tiles follow in address order.
-template <class N, int U, int POL>
-__global__ __launch_bounds__(kBlock) void cast_sr_kernel(CastArgs a, uint32_t key, uint32_t step) {
-  asm volatile("" ::"s"(a.src), "s"(a.dst), "s"(a.nunits), "s"(a.head), "s"(a.grid), "s"(key),
-               "s"(step));
-  constexpr uint64_t kTileUnits = (uint64_t)kBlock * U;
-  const uint64_t full = a.nunits / kTileUnits;
-  const bool partial = full * kTileUnits < a.nunits;
-  const uint64_t bid = blockIdx.x;
-  const int elem_mode = a.nunits == 0 ? 2 : (bid == 0 ? 1 : 0);
-  const uint64_t tile = partial ? (bid == 0 ? full : bid - 1) : bid;
-  const unsigned char* vsrc = a.src + a.head * 4;
-  unsigned char* vdst = a.dst + a.head * 2;
-  if (tile < full)
-    cast_sr_tile_full<N, U, POL>(vsrc + tile * kTileUnits * 32, vdst + tile * kTileUnits * 16,
-                                 sr_seed(a.head + tile * kTileUnits * 8, key, step), threadIdx.x);
-  else if (tile * kTileUnits < a.nunits)
-    cast_sr_tile_guarded<N, U>(vsrc, vdst, tile * kTileUnits, a.nunits,
-                               sr_seed(a.head, key, step), threadIdx.x);
-  if (elem_mode == 2)
-    cast_sr_elements<N>(a, 0, key, step, (uint64_t)blockIdx.x * kBlock + threadIdx.x,
-                        a.grid * kBlock);
-  else if (elem_mode == 1)
-    cast_sr_elements<N>(a, 0, key, step, threadIdx.x, kBlock);
-}
-
-template <class N, int U, int POL>
-static hipError_t launch_sr_inst(const CastArgs& a, uint32_t key, uint32_t step, const Tuning& tu,
-                                 hipStream_t s) {
-  static KernelAttr attr;
-  const hipError_t lds_ok =
-      allow_lds(attr, reinterpret_cast<const void*>(&cast_sr_kernel<N, U, POL>));
-  if (lds_ok != hipSuccess) return lds_ok;
-  const int occ = a.grid >= tu.occ_min_tiles ? tu.copy_occ : 0;
-  hipLaunchKernelGGL((cast_sr_kernel<N, U, POL>), dim3((uint32_t)a.grid), dim3(kBlock),
-                     occ_lds_bytes(occ), s, a, key, step);
-  return hipGetLastError();
-}
-
-template <class N, int POL>
-static hipError_t launch_sr_u(const CastArgs& a, uint32_t key, uint32_t step, int u,
-                              const Tuning& tu, hipStream_t s) {
-  switch (u) {
-    case 1: return launch_sr_inst<N, 1, POL>(a, key, step, tu, s);
-    case 2: return launch_sr_inst<N, 2, POL>(a, key, step, tu, s);
-    default: return launch_sr_inst<N, 4, POL>(a, key, step, tu, s);
+  __device__ __forceinline__ static void pin(const Single& p, const State&) {
+    asm volatile("" ::"s"(p.key), "s"(p.step));
   }
-}
+  __device__ __forceinline__ static void pin(const Plan& p, const State& st) {
+    asm volatile("" ::"s"(st.first), "s"(st.key), "s"(p.step));
+  }
+  __device__ __forceinline__ static int divisor(const Plan&) { return 1; }
+  __device__ __forceinline__ static const CastSrRec* plan_side(const Plan& p) { return p.stab; }
+  __device__ __forceinline__ static void vec(const State& sd, const vec16& x, vec16*,
+                                             uint32_t vi, uint32_t* c) {
+    sr_vec<N>(x, sr_bits4((uint32_t)(sd.first >> 2) + vi, (uint32_t)sd.first & 3u, sd.key, sd.step),
+              c);
+  }
+  __device__ __forceinline__ static uint16_t elem(const State& sd, uint32_t g, uint64_t e, bool) {
+    return sr_round<N>(g, sr_bits1(sd.first + e, sd.key, sd.step));
+  }
+};
 
-// The single cast's launch rule (launch_cast): the tile size is copy_vpt,
-// halved while there would be fewer than kMinTiles tiles; occupancy as there;
-// the store policy is cache_pol's on the 2 bytes an element written.
+// `out_bytes` of either launch: 2 an element.
 template <class N>
 static hipError_t launch_compress_sr_t(void* dst, const void* src, size_t nelem, uint32_t key,
                                        uint32_t step, const Tuning& tu, hipStream_t s) {
-  CastArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.src = static_cast<const unsigned char*>(src);
-  a.dst = static_cast<unsigned char*>(dst);
-  a.divisor = 1;
-  const CastCut c = cast_cut(dst, src, nelem, 4);
-  a.n_elems = nelem;
-  a.aligned = c.aligned;
-  a.head = c.head;
-  a.nunits = c.nunits;
-  a.tail_begin = c.nunits ? c.head + c.nunits * 8 : 0;
-  auto tiles = [&a](int u) { return (a.nunits + (uint64_t)kBlock * u - 1) / ((uint64_t)kBlock * u); };
-  int u = tu.copy_vpt;
-  while (u > 1 && tiles(u) < kMinTiles) u >>= 1;
-  uint64_t grid = tiles(u);
-  if (grid == 0) {
-    grid = (nelem + kBlock - 1) / kBlock;
-    if (grid > 65536) grid = 65536;
-  }
-  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-  a.grid = grid;
-  Tuning tn = tu;
-  tn.nt = 1;  // streaming: every byte is read once
-  return cache_pol(tn, (uint64_t)nelem * 2) == kPolWt ? launch_sr_u<N, kPolWt>(a, key, step, u, tu, s)
-                                                      : launch_sr_u<N, kPolNt>(a, key, step, u, tu, s);
-}
-
-// --------------------------------------------------------- plan launch ----
-// cast_plan_kernel's compress over an SR plan: record b and, from the
-// parallel array, the index in its segment of the record's first element and
-// the segment's key — both read at wave-uniform addresses with no bounds test
-// in front (grid == nrecords) — and the same record prefetch, with a third
-// lane touching the parallel entry of the workgroup kPrefetchAhead later.
-template <class N, int U, int POL>
-__global__ __launch_bounds__(kBlock) void cast_sr_plan_kernel(
-    const CastRec* __restrict__ table, const CastSrRec* __restrict__ stab, uint32_t nrecords,
-    uint32_t step) {
-  const CastRec& r = table[blockIdx.x];
-  const unsigned char* const wide = r.wide;
-  unsigned char* const half = r.half;
-  const uint64_t first = stab[blockIdx.x].first;
-  const uint32_t key = stab[blockIdx.x].key;
-  const uint32_t kind = r.kind, count = r.count, aligned = r.aligned;
-  asm volatile("" ::"s"(wide), "s"(half), "s"(first), "s"(key), "s"(kind), "s"(count),
-               "s"(aligned), "s"(step));
-  uint32_t pf = 0;
-  if (threadIdx.x < 3 && blockIdx.x + kPrefetchAhead < nrecords) {
-    const uint32_t* rec = reinterpret_cast<const uint32_t*>(table + blockIdx.x + kPrefetchAhead);
-    const uint32_t* sp = reinterpret_cast<const uint32_t*>(stab + blockIdx.x + kPrefetchAhead);
-    pf = *(threadIdx.x < 2 ? rec + threadIdx.x * 7 : sp);
-  }
-  if (kind == kTileFull) {
-    cast_sr_tile_full<N, U, POL>(wide, half, sr_seed(first, key, step), threadIdx.x);
-  } else if (kind == kTilePartial) {
-    cast_sr_tile_guarded<N, U>(wide, half, 0, count, sr_seed(first, key, step), threadIdx.x);
-  } else {
-    CastArgs a;
-    a.src = wide;
-    a.dst = half;
-    a.n_elems = count;  // the range [0, count) as a tail that begins at 0
-    a.head = a.nunits = a.tail_begin = 0;
-    a.grid = 1;
-    a.divisor = 1;
-    a.aligned = (int)aligned;
-    cast_sr_elements<N>(a, first, key, step, threadIdx.x, kBlock);
-  }
-  keep_prefetch(pf);
-}
-
-template <class N, int U, int POL>
-static hipError_t launch_sr_plan_inst(const CastRec* table, const CastSrRec* stab,
-                                      uint32_t nrecords, uint32_t step, const Tuning& tu,
-                                      hipStream_t s) {
-  static KernelAttr attr;
-  const hipError_t lds_ok =
-      allow_lds(attr, reinterpret_cast<const void*>(&cast_sr_plan_kernel<N, U, POL>));
-  if (lds_ok != hipSuccess) return lds_ok;
-  const int occ = nrecords >= tu.occ_min_tiles_batch ? tu.copy_occ : 0;
-  hipLaunchKernelGGL((cast_sr_plan_kernel<N, U, POL>), dim3(nrecords), dim3(kBlock),
-                     occ_lds_bytes(occ), s, table, stab, nrecords, step);
-  return hipGetLastError();
-}
-
-template <class N, int POL>
-static hipError_t launch_sr_plan_u(const CastRec* table, const CastSrRec* stab, uint32_t nrecords,
-                                   uint32_t step, int u, const Tuning& tu, hipStream_t s) {
-  switch (u) {
-    case 1: return launch_sr_plan_inst<N, 1, POL>(table, stab, nrecords, step, tu, s);
-    case 2: return launch_sr_plan_inst<N, 2, POL>(table, stab, nrecords, step, tu, s);
-    default: return launch_sr_plan_inst<N, 4, POL>(table, stab, nrecords, step, tu, s);
-  }
+  typename CastSr<N>::Single p;
+  int u;
+  const hipError_t e = cast_rule(cast_cut(dst, src, nelem, 4), dst, src, nelem, 1, tu, &p.a, &u);
+  if (e != hipSuccess) return e;
+  p.key = key;
+  p.step = step;
+  return launch_single<CastSr<N>, Wide<kFloat32>, true>(p, u, (uint64_t)nelem * 2, tu, s);
 }
 
 template <class N>
 static hipError_t launch_cast_plan_sr_t(const CastRec* table, const CastSrRec* stab,
                                         uint32_t nrecords, uint32_t step, int u,
                                         uint64_t out_bytes, const Tuning& tu, hipStream_t s) {
-  if (u != 1 && u != 2 && u != 4) return hipErrorInvalidValue;
-  Tuning tn = tu;
-  tn.nt = 1;  // streaming: every byte is read once
-  return cache_pol(tn, out_bytes) == kPolWt
-             ? launch_sr_plan_u<N, kPolWt>(table, stab, nrecords, step, u, tu, s)
-             : launch_sr_plan_u<N, kPolNt>(table, stab, nrecords, step, u, tu, s);
+  const typename CastSr<N>::Plan p{table, stab, nrecords, step};
+  return launch_plan_s<CastSr<N>, Wide<kFloat32>, true>(p, u, out_bytes, tu, s);
 }
 
 }  // namespace bpsr

@@ -1,5 +1,6 @@
-"""Error-feedback cast plans (byteps_reduce_cast_plan_create_ef,
-prophet_amd/csrc/bpsr_cast_ef.h) on the GPU: one launch over an empty, a
+"""Error-feedback cast plans (byteps_reduce_cast_plan_create_ef; the plan kernel
+of prophet_amd/csrc/bpsr_cast_plan.h under the scheme of bpsr_cast_ef.h) on the
+GPU: one launch over an empty, a
 1-element, a never-co-aligned, a partial-tile and one- and several-tile
 segments against one ``compress_ef`` per segment (wire and residual, bit for
 bit, sentinel bytes between the segments intact) and against the host

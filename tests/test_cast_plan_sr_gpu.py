@@ -1,5 +1,6 @@
 """Stochastic-rounding cast plans (byteps_reduce_cast_plan_create_sr /
-_compress_sr, cast_sr_plan_kernel in prophet_amd/csrc/bpsr_cast_sr.h) on the
+_compress_sr, cast_plan_kernel of prophet_amd/csrc/bpsr_cast_plan.h under the
+scheme of bpsr_cast_sr.h) on the
 GPU: one launch over segments of mixed lengths, alignments and keys writes per
 segment the bytes of one ``compress_sr`` — and so of the host definition
 (prophet_amd/sr.py) — the plan's decompress is the plain one, a compress

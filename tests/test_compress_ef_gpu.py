@@ -1,4 +1,5 @@
-"""The error-feedback compress kernels (prophet_amd/csrc/bpsr_cast_ef.h,
+"""The error-feedback compress kernels (the scheme of
+prophet_amd/csrc/bpsr_cast_ef.h over bpsr_cast_impl.h and bpsr_cast_single.h;
 bpsr_k_cast_ef.hip, bpsr_k_cast_ef_bf16.hip) on the GPU against the host
 definition in CPU torch ops:
 

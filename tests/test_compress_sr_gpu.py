@@ -1,4 +1,5 @@
-"""The stochastic-rounding compress kernels (prophet_amd/csrc/bpsr_cast_sr.h,
+"""The stochastic-rounding compress kernels (the scheme of
+prophet_amd/csrc/bpsr_cast_sr.h over bpsr_cast_impl.h and bpsr_cast_single.h;
 bpsr_k_cast_sr.hip, bpsr_k_cast_sr_bf16.hip) on the GPU against the host
 definition (prophet_amd/sr.py): the wire bits are equal everywhere except
 where the expected value is a NaN (there only a NaN is required: the payload

@@ -562,8 +562,7 @@ def ef_mode(args) -> int:
     n = args.elems
     out = {"tool": "bench_compress", "mode": "error feedback", "wire": args.wire, "elems": n,
            "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
-           "device": torch.cuda.get_device_name(0),
-           "ef_resid_pol": os.environ.get("BPSR_EF_RESID_POL", "0")}
+           "device": torch.cuda.get_device_name(0)}
     with step("setup", 120):
         red = GpuReducer(device=0)
         g = torch.Generator(device=dev).manual_seed(5)
