@@ -66,7 +66,10 @@ extern "C" {
  *                       (byteps_cast_ef_desc: error-feedback compression)
  *    additive, still 5: byteps_reduce_compress_sr / _cast_plan_create_sr /
  *                       _cast_plan_compress_sr (byteps_cast_sr_desc:
- *                       stochastic-rounding compression) */
+ *                       stochastic-rounding compression)
+ *    additive, still 5: byteps_reduce_cast_plan_decompress_stats (the
+ *                       decompress that also reports each segment's sum of
+ *                       squares and non-finite count) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -490,6 +493,32 @@ int byteps_reduce_cast_plan_create_sr(const byteps_cast_sr_desc* segs, int nsegs
                                       int wire_dtype, byteps_reduce_cast_plan** out);
 int byteps_reduce_cast_plan_compress_sr(byteps_reduce_cast_plan* plan, uint32_t step,
                                         void* stream);
+
+/* Decompress statistics: _cast_plan_decompress that also reports, for every
+ * segment s of the plan (in the order of the table given to create, segments
+ * with nelem == 0 included), two numbers computed from exactly the values v it
+ * writes to the segment's `wide` (after the divide and the widening):
+ *   stats[2 s]     = the sum of (double)v * (double)v over the FINITE v, added
+ *                    up in f64.  Each square is exact (the wide types have at
+ *                    most 24 significant bits here); every addition rounds
+ *                    once.  The order of the additions is the library's: it
+ *                    depends on the plan alone, so two launches over the same
+ *                    bytes give the same bits.
+ *   stats[2 s + 1] = (double) the number of v that are +inf, -inf or NaN.
+ * The bytes written to `wide` are those of _cast_plan_decompress, bit for bit.
+ * Any plan (create, create_wire, create_ef, create_sr), as for _decompress.
+ *   stats:   device memory, 2 * nsegs doubles, every one of them written by
+ *            every call.  A null pointer (nsegs > 0), one that is not 8-byte
+ *            aligned, or a range that overlaps any byte range of the plan's
+ *            segments is EARGS, as are a null plan and divisor < 1; all before
+ *            any launch.  A plan of no segments writes nothing and succeeds.
+ *   Asynchronous on `stream`: the decompress, then a small kernel that adds
+ *   each segment's per-wave partial sums up.  The partials (64 bytes a record)
+ *   belong to the plan: its FIRST statistics call allocates them (hipMalloc,
+ *   which may synchronise the device), _destroy frees them, and two statistics
+ *   launches of one plan must not run concurrently. */
+int byteps_reduce_cast_plan_decompress_stats(byteps_reduce_cast_plan* plan, int divisor,
+                                             double* stats, void* stream);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

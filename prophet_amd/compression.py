@@ -84,6 +84,19 @@ inherited, and tensors other than float32 pass through, as for error
 feedback.  Not covered: the server's fold still rounds its sum to the wire
 format to nearest even, so stochastic rounding makes the worker's cast
 unbiased, not the whole round.
+
+``decompress_into(..., stats=)`` / ``decompress_many_into(..., stats=)`` also
+report, per tensor, two numbers computed from exactly the values the
+decompress writes: the sum of the squares of the finite ones, added up in
+float64, and the count of the others (+-inf, NaN) — what a global-norm clip
+and a GradScaler-style overflow check need, without a second sweep over the
+gradients.  :func:`decompress_stats` below is the definition; the order of the
+additions is the implementation's.  Device tensors go through the cast plan's
+``STATS`` decompress (``byteps_reduce_cast_plan_decompress_stats``, DESIGN.md
+§11.5): the plain decompress's bytes, the statistics from the registers that
+hold them, then a small kernel that adds each tensor's partial sums up.  The
+rows land in a float64 device tensor in stream order; nothing synchronises
+with the host.
 """
 from __future__ import annotations
 
@@ -134,6 +147,33 @@ def _as_host_bf16(x):
     """The same for a bf16 buffer: a numpy one carries raw uint16 bits."""
     import torch
     return x if _is_torch(x) else torch.from_numpy(x.view(np.int16)).view(torch.bfloat16)
+
+
+def decompress_stats(out):
+    """The decompress statistics of one output, the pinned definition:
+    ``(sum of squares of the finite values in float64, count of the
+    non-finite ones)`` of a CPU tensor or numpy array."""
+    if _is_torch(out):
+        import torch
+        x = out.detach().reshape(-1).to(torch.float64).numpy()
+    else:
+        x = out.reshape(-1).astype(np.float64)
+    fin = np.isfinite(x)
+    return float(np.square(x[fin]).sum()), int(np.count_nonzero(~fin))
+
+
+def _check_stats(stats, shape) -> None:
+    """``stats``: a float64 tensor or array of ``shape``."""
+    if _is_torch(stats):
+        import torch
+        ok = stats.dtype == torch.float64
+    else:
+        ok = isinstance(stats, np.ndarray) and stats.dtype == np.float64
+    if not ok:
+        raise ValueError(f"stats must be a float64 tensor or array, got "
+                         f"{getattr(stats, 'dtype', type(stats))}")
+    if tuple(stats.shape) != tuple(shape):
+        raise ValueError(f"stats must have shape {tuple(shape)}, got {tuple(stats.shape)}")
 
 
 class CastPlanCache:
@@ -191,7 +231,7 @@ def _new_plan(wide_dtype: int, pairs, wire_dtype: int = 2):
 
 
 def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None, keys=None,
-               step=None) -> None:
+               step=None, stats=None) -> None:
     """``pairs`` of ``(wide, half)`` tensors or arrays cast by compressor
     ``comp``: the device ones as one plan launch per (device, wide dtype, wire
     dtype), the host ones one by one.  With ``residuals`` (one per pair) the
@@ -199,15 +239,24 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None,
     the decompress the plain one through the same plan.  With ``keys`` (one
     per pair) they are stochastic-rounding plans: the compress is
     ``compress_sr_into``'s under ``step``, the decompress again the plain one
-    through the same plan."""
+    through the same plan.  ``stats`` (decompress only): float64
+    ``[len(pairs), 2]``, row i the statistics of pair i — a device pair's row
+    lives on its device, a host pair's on the host; each plan writes its own
+    rows, which are copied to their places in stream order."""
     if int(divisor) < 1:
         raise ValueError(f"divisor {divisor} < 1")
+    if stats is not None:
+        _check_stats(stats, (len(pairs), 2))
     groups: dict = {}
+    rows: dict = {}
     for i, (wide, half) in enumerate(pairs):
         resid = None if residuals is None else residuals[i]
         if not _on_device(wide) and not _on_device(half):
             if not compress:
-                comp.decompress_into(wide, half, divisor)
+                if stats is not None and _on_device(stats):
+                    raise ValueError(f"stats is on {stats.device}, tensor {i} on the host")
+                comp.decompress_into(wide, half, divisor,
+                                     **({} if stats is None else {"stats": stats[i]}))
             elif keys is not None:
                 comp.compress_sr_into(half, wide, keys[i], step)
             elif resid is None:
@@ -227,7 +276,11 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None,
         else:
             _check_cast_ef(half, resid, wide, wire)
             seg = (wide.reshape(-1), half.reshape(-1), resid.reshape(-1))
+        if stats is not None and (not _on_device(stats) or stats.device != wide.device):
+            raise ValueError(f"stats is on {getattr(stats, 'device', 'the host')}, "
+                             f"tensor {i} on {wide.device}")
         groups.setdefault((wide.device, wide.dtype, wire), []).append(seg)
+        rows.setdefault((wide.device, wide.dtype, wire), []).append(i)
     if not groups:
         return
     import torch
@@ -242,8 +295,22 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None,
                     plan.compress(step=step, stream=stream)
                 elif compress:
                     plan.compress(stream=stream)
-                else:
+                elif stats is None:
                     plan.decompress(int(divisor), stream=stream)
+                else:
+                    idx = rows[(device, dtype, wire)]
+                    whole = idx == list(range(len(pairs))) and stats.is_contiguous()
+                    buf = stats.reshape(-1) if whole else \
+                        torch.empty(2 * len(idx), dtype=torch.float64, device=device)
+                    plan.decompress(int(divisor), stream=stream, stats=buf)
+                    if not whole:         # the plan's rows to the caller's order, run by run
+                        got, a = buf.view(-1, 2), 0
+                        while a < len(idx):
+                            b = a + 1
+                            while b < len(idx) and idx[b] == idx[b - 1] + 1:
+                                b += 1
+                            stats[idx[a]:idx[a] + (b - a)].copy_(got[a:b])
+                            a = b
             finally:
                 if plans is None:
                     plan.close()          # waits for the launch
@@ -364,13 +431,29 @@ class _CastCompressor(Compressor):
         return cls.decompress_into(out, np.ascontiguousarray(tensor))
 
     @classmethod
-    def decompress_into(cls, out, compressed, divisor: int = 1):
+    def decompress_into(cls, out, compressed, divisor: int = 1, stats=None,
+                        plans: CastPlanCache | None = None):
         """``out[i] = T(compressed[i])``, or ``T(wire(compressed[i] / divisor))``
         for a divisor above 1 (divide on the 2-byte value, then widen), in one
-        pass; returns ``out``."""
+        pass; returns ``out``.  ``stats``: a float64 tensor or array of shape
+        ``(2,)`` — on ``out``'s device for a device tensor — that receives
+        ``decompress_stats(out)``; a device tensor then goes through a
+        one-segment cast plan (from ``plans`` if given, else built and
+        destroyed here, which waits for the launch)."""
         if int(divisor) < 1:
             raise ValueError(f"divisor {divisor} < 1")
         import torch
+        if stats is not None:
+            _check_stats(stats, (2,))
+            if _on_device(out) or _on_device(compressed):
+                _cast_many(cls, [(out, compressed)], False, divisor, plans,
+                           stats=stats.reshape(1, 2))
+                return out
+            if _on_device(stats):
+                raise ValueError(f"stats is on {stats.device}, the tensor on the host")
+            cls.decompress_into(out, compressed, divisor)
+            stats[0], stats[1] = decompress_stats(out)
+            return out
         if _on_device(out):
             from . import torch_ops  # noqa: F401
             with torch.cuda.device(out.device):
@@ -396,13 +479,15 @@ class _CastCompressor(Compressor):
 
     @classmethod
     def decompress_many_into(cls, outs, compressed, divisor: int = 1,
-                             plans: CastPlanCache | None = None):
+                             plans: CastPlanCache | None = None, stats=None):
         """``decompress_into(outs[i], compressed[i], divisor)`` for every i,
         the device tensors as one cast-plan launch per (device, dtype);
-        returns ``outs``."""
+        returns ``outs``.  ``stats``: a float64 tensor or array of shape
+        ``(len(outs), 2)`` where the outputs live; row i receives
+        ``decompress_stats(outs[i])``."""
         if len(outs) != len(compressed):
             raise ValueError("decompress_many_into: as many outputs as compressed tensors")
-        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans)
+        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans, stats=stats)
         return outs
 
 
@@ -501,15 +586,15 @@ class _ErrorFeedback:
 
     @classmethod
     def decompress_many_into(cls, outs, compressed, divisor: int = 1,
-                             plans: CastPlanCache | None = None, residuals=None):
-        """The inherited decompress.  ``residuals`` (those given to
+                             plans: CastPlanCache | None = None, residuals=None, stats=None):
+        """The inherited decompress, ``stats`` included.  ``residuals`` (those given to
         ``compress_many_ef_into`` over the same tensors) only names the plan:
         the error-feedback plan's own decompress is the plain one, so one
         cached plan serves both directions; the residuals are not touched."""
         if len(outs) != len(compressed):
             raise ValueError("decompress_many_into: as many outputs as compressed tensors")
         _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans,
-                   residuals=None if residuals is None else list(residuals))
+                   residuals=None if residuals is None else list(residuals), stats=stats)
         return outs
 
 
@@ -581,15 +666,15 @@ class _StochasticRounding:
 
     @classmethod
     def decompress_many_into(cls, outs, compressed, divisor: int = 1,
-                             plans: CastPlanCache | None = None, keys=None):
-        """The inherited decompress.  ``keys`` (those given to
+                             plans: CastPlanCache | None = None, keys=None, stats=None):
+        """The inherited decompress, ``stats`` included.  ``keys`` (those given to
         ``compress_many_sr_into`` over the same tensors) only names the plan:
         the stochastic-rounding plan's own decompress is the plain one, so one
         cached plan serves both directions."""
         if len(outs) != len(compressed):
             raise ValueError("decompress_many_into: as many outputs as compressed tensors")
         _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans,
-                   keys=None if keys is None else list(keys))
+                   keys=None if keys is None else list(keys), stats=stats)
         return outs
 
 
@@ -615,4 +700,4 @@ class Compression:
 
 __all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
            "FP16EFCompressor", "BF16EFCompressor", "FP16SRCompressor", "BF16SRCompressor",
-           "Compression", "CastPlanCache"]
+           "Compression", "CastPlanCache", "decompress_stats"]

@@ -581,7 +581,22 @@ struct byteps_reduce_cast_plan {
   void* dev_sr;     // stochastic-rounding plans: one CastSrRec per record
   bool sr;          // made by _create_sr (also when it has no records)
   CastTableInfo ti;
+  // decompress statistics (_decompress_stats): the segments' record lists,
+  // seg_begin[nsegs + 1] then seg_recs[records], uploaded with the table; the
+  // (record, wave) partials, made by the first statistics call; and the
+  // segments' byte ranges, which the statistics' output must stay clear of
+  int nsegs;
+  void* dev_seg;
+  void* dev_part;
+  std::vector<std::pair<uintptr_t, uintptr_t>> ranges;
 };
+
+typedef std::vector<std::pair<uintptr_t, uintptr_t>> CastRanges;
+// One operand's byte range (the table builder has validated it); nothing for
+// an empty segment.
+static void cast_plan_range(CastRanges& out, const void* p, size_t bytes) {
+  if (bytes) out.emplace_back((uintptr_t)p, (uintptr_t)p + bytes);
+}
 
 // table_dtype: what the table builder is given.  It cuts by element size alone
 // and knows the fp16 wire's three wide types, so a wide fp16 (bf16 wire) is
@@ -589,9 +604,13 @@ struct byteps_reduce_cast_plan {
 // Upload a built table (and, for an error-feedback plan, its residual
 // pointers: `resid` non-null; for a stochastic-rounding plan its parallel
 // array: `sr` non-null) into a new plan.
+// `lists`: every segment's records (nsegs = seg_begin.size() - 1), uploaded
+// whenever the plan has a segment, records or not.
 static int cast_plan_upload(const std::vector<char>& host,
                             const std::vector<unsigned char*>* resid, const CastTableInfo& ti,
                             int wide_dtype, int wire, byteps_reduce_cast_plan** out,
+                            const CastSegList& lists,
+                            CastRanges&& ranges,
                             const std::vector<CastSrRec>* sr = nullptr) {
   auto* p = new byteps_reduce_cast_plan();
   p->dtype = wide_dtype;
@@ -601,7 +620,21 @@ static int cast_plan_upload(const std::vector<char>& host,
   p->dev_resid = nullptr;
   p->dev_sr = nullptr;
   p->sr = sr != nullptr;
+  p->nsegs = (int)lists.seg_begin.size() - 1;
+  p->dev_seg = nullptr;
+  p->dev_part = nullptr;
+  p->ranges = std::move(ranges);
   hipError_t e = hipGetDevice(&p->device);
+  if (e == hipSuccess && p->nsegs > 0) {
+    const size_t nb = lists.seg_begin.size() * sizeof(uint32_t);
+    const size_t nr = lists.seg_recs.size() * sizeof(uint32_t);
+    e = hipMalloc(&p->dev_seg, nb + nr);
+    if (e == hipSuccess)
+      e = hipMemcpy(p->dev_seg, lists.seg_begin.data(), nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nr)
+      e = hipMemcpy(static_cast<char*>(p->dev_seg) + nb, lists.seg_recs.data(), nr,
+                    hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess && ti.records > 0) {
     e = hipMalloc(&p->dev_table, ti.bytes);
     if (e == hipSuccess)
@@ -621,6 +654,7 @@ static int cast_plan_upload(const std::vector<char>& host,
     if (p->dev_table) (void)hipFree(p->dev_table);
     if (p->dev_resid) (void)hipFree(p->dev_resid);
     if (p->dev_sr) (void)hipFree(p->dev_sr);
+    if (p->dev_seg) (void)hipFree(p->dev_seg);
     delete p;
     return hip_fail(e, "cast plan table upload");
   }
@@ -632,9 +666,16 @@ static int cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dt
                             int table_dtype, byteps_reduce_cast_plan** out) {
   std::vector<char> host;
   CastTableInfo ti;
-  const int rc = build_cast_table(segs, nsegs, table_dtype, tuning().copy_vpt, host, &ti);
+  CastSegList lists;
+  const int rc =
+      build_cast_table(segs, nsegs, table_dtype, tuning().copy_vpt, host, &ti, &lists);
   if (rc) return rc;
-  return cast_plan_upload(host, nullptr, ti, wide_dtype, wire, out);
+  CastRanges ranges;
+  for (int i = 0; i < nsegs; ++i) {
+    cast_plan_range(ranges, segs[i].wide, segs[i].nelem * (size_t)elem_size(table_dtype));
+    cast_plan_range(ranges, segs[i].half, segs[i].nelem * 2);
+  }
+  return cast_plan_upload(host, nullptr, ti, wide_dtype, wire, out, lists, std::move(ranges));
 }
 
 int byteps_reduce_cast_plan_create_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype,
@@ -646,10 +687,18 @@ int byteps_reduce_cast_plan_create_ef(const byteps_cast_ef_desc* segs, int nsegs
   std::vector<char> host;
   std::vector<unsigned char*> resid;
   CastTableInfo ti;
+  CastSegList lists;
   const int rc =
-      build_cast_table_ef(segs, nsegs, wide_dtype, tuning().copy_vpt, host, resid, &ti);
+      build_cast_table_ef(segs, nsegs, wide_dtype, tuning().copy_vpt, host, resid, &ti, &lists);
   if (rc) return rc;
-  return cast_plan_upload(host, &resid, ti, wide_dtype, wire_dtype, out);
+  CastRanges ranges;
+  for (int i = 0; i < nsegs; ++i) {
+    cast_plan_range(ranges, segs[i].wide, segs[i].nelem * 4);
+    cast_plan_range(ranges, segs[i].half, segs[i].nelem * 2);
+    cast_plan_range(ranges, segs[i].resid, segs[i].nelem * 4);
+  }
+  return cast_plan_upload(host, &resid, ti, wide_dtype, wire_dtype, out, lists,
+                          std::move(ranges));
 }
 
 int byteps_reduce_cast_plan_create_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype,
@@ -661,9 +710,17 @@ int byteps_reduce_cast_plan_create_sr(const byteps_cast_sr_desc* segs, int nsegs
   std::vector<char> host;
   std::vector<CastSrRec> sr;
   CastTableInfo ti;
-  const int rc = build_cast_table_sr(segs, nsegs, wide_dtype, tuning().copy_vpt, host, sr, &ti);
+  CastSegList lists;
+  const int rc =
+      build_cast_table_sr(segs, nsegs, wide_dtype, tuning().copy_vpt, host, sr, &ti, &lists);
   if (rc) return rc;
-  return cast_plan_upload(host, nullptr, ti, wide_dtype, wire_dtype, out, &sr);
+  CastRanges ranges;
+  for (int i = 0; i < nsegs; ++i) {
+    cast_plan_range(ranges, segs[i].wide, segs[i].nelem * 4);
+    cast_plan_range(ranges, segs[i].half, segs[i].nelem * 2);
+  }
+  return cast_plan_upload(host, nullptr, ti, wide_dtype, wire_dtype, out, lists,
+                          std::move(ranges), &sr);
 }
 
 int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
@@ -727,10 +784,46 @@ int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* p, int divisor, 
   return cast_plan_launch(p, false, divisor, stream);
 }
 
+int byteps_reduce_cast_plan_decompress_stats(byteps_reduce_cast_plan* p, int divisor,
+                                             double* stats, void* stream) {
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  if (p->nsegs <= 0) return BYTEPS_REDUCE_OK;  // no segment: no row, nothing to write
+  if (!stats) return fail(BYTEPS_REDUCE_EARGS, "null stats pointer");
+  const uintptr_t sb = (uintptr_t)stats;
+  const size_t bytes = (size_t)p->nsegs * 2 * sizeof(double);
+  if (sb % sizeof(double)) return fail(BYTEPS_REDUCE_EARGS, "stats is not 8-byte aligned");
+  if (sb > UINTPTR_MAX - bytes)
+    return fail(BYTEPS_REDUCE_EARGS, "stats wraps the address space");
+  for (const auto& r : p->ranges)
+    if (sb < r.second && r.first < sb + bytes)
+      return fail(BYTEPS_REDUCE_EARGS, "stats overlaps a segment of the plan");
+  hipStream_t s = to_stream(stream);
+  const uint32_t* seg = static_cast<const uint32_t*>(p->dev_seg);
+  if (p->ti.records > 0) {
+    if (!p->dev_part) {  // the first statistics call of a plan allocates
+      hipError_t e = hipMalloc(&p->dev_part, (size_t)p->ti.records * kStatPartBytes);
+      if (e != hipSuccess) return hip_fail(e, "cast plan statistics partials");
+    }
+    const auto launch = p->wire == kBFloat16 ? launch_cast_plan_stats_bf16 : launch_cast_plan_stats;
+    hipError_t e = launch(static_cast<const CastRec*>(p->dev_table), p->ti.records, p->dtype,
+                          divisor, p->ti.u, p->ti.nelem * (uint64_t)elem_size(p->dtype),
+                          p->dev_part, tuning(), s);
+    if (e != hipSuccess) return hip_fail(e, "cast plan kernel launch");
+  }
+  hipError_t e = launch_cast_stats_finish(seg, seg + p->nsegs + 1, p->dev_part, stats, p->nsegs, s);
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan statistics kernel launch");
+}
+
 int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* p) {
   if (!p) return BYTEPS_REDUCE_OK;
   hipError_t e = hipSuccess;
   if (p->dev_table) e = hipFree(p->dev_table);
+  for (void* q : {p->dev_seg, p->dev_part})
+    if (q) {
+      const hipError_t e2 = hipFree(q);
+      if (e == hipSuccess) e = e2;
+    }
   if (p->dev_resid) {
     const hipError_t e2 = hipFree(p->dev_resid);
     if (e == hipSuccess) e = e2;

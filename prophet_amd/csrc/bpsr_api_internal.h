@@ -119,6 +119,27 @@ int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dty
                         std::vector<char>& out, std::vector<CastSrRec>& sr_out,
                         CastTableInfo* ti);
 
+// Every segment's records, in CSR form (the decompress statistics'
+// finish kernel adds a segment's partials up from it): segment s of the
+// caller's table owns records seg_recs[seg_begin[s] .. seg_begin[s + 1]),
+// ascending; a segment with nelem == 0 owns none.  seg_begin has nsegs + 1
+// entries, seg_recs one per record.
+struct CastSegList {
+  std::vector<uint32_t> seg_begin;
+  std::vector<uint32_t> seg_recs;
+};
+// The three builders above, which also fill `lists` (where it is not null);
+// the table and the parallel arrays are byte for byte the same.  On an error
+// `lists` too is left as it was.
+int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                     std::vector<char>& out, CastTableInfo* ti, CastSegList* lists);
+int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                        std::vector<char>& out, std::vector<unsigned char*>& resid_out,
+                        CastTableInfo* ti, CastSegList* lists);
+int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                        std::vector<char>& out, std::vector<CastSrRec>& sr_out,
+                        CastTableInfo* ti, CastSegList* lists);
+
 // ------------------------------------- library queues (bpsr_queues.cpp) --
 // Per device, created on first use, never destroyed: the four library queues
 // (all-CU-masked streams, each a hardware queue of its own; queue 0 is

@@ -22,6 +22,7 @@ namespace bpsr {
 
 // Wide-side element: its 16-B vectors per unit, and the exact steps to and
 // from f32 bits.  get/put address element e (0..7) of a unit's vectors.
+// to_f64: the element's value, exactly (the decompress statistics).
 template <int DT>
 struct Wide;
 
@@ -30,6 +31,7 @@ struct Wide<kFloat32> {
   using E = uint32_t;
   static constexpr int kVecs = 2;
   __device__ static uint32_t to_f32(E x) { return x; }
+  __device__ static double to_f64(E x) { return (double)bitcast<float>(x); }
   __device__ static E from_f32(float f) { return bitcast<uint32_t>(f); }
   __device__ static E get(const vec16* x, int e) { return x[e >> 2].w[e & 3]; }
   __device__ static void put(vec16* x, int e, E v) { x[e >> 2].w[e & 3] = v; }
@@ -41,6 +43,7 @@ struct Wide<kFloat64> {
   static constexpr int kVecs = 4;
   // round to f32 first (RNE), as the host conversion does
   __device__ static uint32_t to_f32(E x) { return bitcast<uint32_t>((float)bitcast<double>(x)); }
+  __device__ static double to_f64(E x) { return bitcast<double>(x); }
   __device__ static E from_f32(float f) { return bitcast<uint64_t>((double)f); }
   __device__ static E get(const vec16* x, int e) {
     return ((uint64_t)x[e >> 1].w[(e & 1) * 2 + 1] << 32) | x[e >> 1].w[(e & 1) * 2];
@@ -56,6 +59,7 @@ struct Wide<kBFloat16> {
   using E = uint16_t;
   static constexpr int kVecs = 1;
   __device__ static uint32_t to_f32(E x) { return (uint32_t)x << 16; }  // exact
+  __device__ static double to_f64(E x) { return (double)bitcast<float>(to_f32(x)); }
   __device__ static E from_f32(float f) { return (E)f32_to_bf16_rne(bitcast<uint32_t>(f)); }
   __device__ static E get(const vec16* x, int e) {
     return (E)(x[0].w[e >> 1] >> ((e & 1) * 16));
@@ -73,6 +77,7 @@ struct Wide<kFloat16> {
   using E = uint16_t;
   static constexpr int kVecs = 1;
   __device__ static uint32_t to_f32(E x) { return bitcast<uint32_t>((float)bitcast<_Float16>(x)); }
+  __device__ static double to_f64(E x) { return (double)(float)bitcast<_Float16>(x); }
   __device__ static E from_f32(float f) { return (E)f2h_bits(bitcast<uint32_t>(f)); }
   __device__ static E get(const vec16* x, int e) {
     return (E)(x[0].w[e >> 1] >> ((e & 1) * 16));
@@ -124,11 +129,43 @@ __device__ __forceinline__ typename W::E decompress_elem(uint16_t h, bool div, f
   return W::from_f32(N::to_float(h));
 }
 
-template <class W, class N>
-__device__ __forceinline__ void decompress_unit(const vec16& h, bool div, float fd, vec16* o) {
+// Decompress statistics (byteps_reduce_cast_plan_decompress_stats): what a
+// lane has seen of the elements it WRITES, each exactly once — the sum of the
+// squares of the finite ones in f64 (a square of a value of at most 24
+// significant bits is exact; v_fma_f64 adds it with one rounding) and the
+// count of the others.  A compile-time choice: the tiles below take the
+// accumulator's type, and under StatNone — every compress, every plain
+// decompress — add() is nothing and the code is what it was without it.
+struct StatNone {
+  template <class W>
+  __device__ __forceinline__ void add(typename W::E) {}
+};
+struct StatAcc {
+  double sumsq = 0.0;
+  uint32_t nonfinite = 0;
+  template <class W>
+  __device__ __forceinline__ void add(typename W::E v) {
+    const double x = W::to_f64(v);
+    const bool fin = __builtin_isfinite(x);
+    sumsq = fin ? __builtin_fma(x, x, sumsq) : sumsq;
+    nonfinite += fin ? 0u : 1u;
+  }
+};
+
+// decompress_elem, the element shown to the accumulator on its way out
+template <class W, class N, class A>
+__device__ __forceinline__ typename W::E decompress_elem(uint16_t h, bool div, float fd, A& acc) {
+  const typename W::E v = decompress_elem<W, N>(h, div, fd);
+  acc.template add<W>(v);
+  return v;
+}
+
+template <class W, class N, class A>
+__device__ __forceinline__ void decompress_unit(const vec16& h, bool div, float fd, vec16* o,
+                                                A& acc) {
 #pragma unroll
   for (int e = 0; e < 8; ++e)
-    W::put(o, e, decompress_elem<W, N>((uint16_t)(h.w[e >> 1] >> ((e & 1) * 16)), div, fd));
+    W::put(o, e, decompress_elem<W, N>((uint16_t)(h.w[e >> 1] >> ((e & 1) * 16)), div, fd, acc));
 }
 
 template <class W, class N>
@@ -202,11 +239,13 @@ constexpr bool kHooked = std::is_same<W, Wide<kFloat32>>::value;
 // Full tile: units [0, kBlock * U) of the tile whose first bytes are h0 (narrow
 // side) and w0 (wide side), `st` at its first element; lane handles units
 // lane + j * kBlock.  One buffer descriptor per operand sized to the tile,
-// 32-bit lane offsets.
-template <class S, class W, bool COMPRESS, int U, int POL>
+// 32-bit lane offsets.  `acc` (here and in the two below): the decompress
+// statistics of the elements this lane writes — in the re-dealt decompress
+// that is the lane that stores the output vector.
+template <class S, class W, bool COMPRESS, int U, int POL, class A = StatNone>
 __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigned char* dst,
                                                const typename S::State& st, bool div, float fd,
-                                               int lane) {
+                                               int lane, A&& acc = A{}) {
   using N = typename S::Narrow;
   constexpr int kAux = 2;                            // loads: nt
   constexpr int kStAux = POL == kPolWt ? 16 : kAux;  // stores: sc1 (write-through) or nt
@@ -333,7 +372,8 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
           vec16 o{};
 #pragma unroll
           for (int e = 0; e < EPV; ++e)  // e < EPV: all within the one vector
-            W::put(&o, e, decompress_elem<W, N>((uint16_t)(d[e >> 1] >> ((e & 1) * 16)), div, fd));
+            W::put(&o, e,
+                   decompress_elem<W, N>((uint16_t)(d[e >> 1] >> ((e & 1) * 16)), div, fd, acc));
           __builtin_amdgcn_raw_buffer_store_b128(
               bitcast<u4>(o), rd, ((j * kBlock + wave0) * KV + g) * 16, 0, kStAux);
         }
@@ -343,7 +383,7 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
 #pragma unroll
     for (int j = 0; j < U; ++j) {
       vec16 o[KV];
-      decompress_unit<W, N>(h[j], div, fd, o);
+      decompress_unit<W, N>(h[j], div, fd, o, acc);
 #pragma unroll
       for (int v = 0; v < KV; ++v)
         __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(o[v]), rd,
@@ -355,10 +395,11 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
 // The partial last tile: units [u0, nunits) of the vector range (src / dst
 // already advanced to the range, `st` at its first element); a unit past
 // nunits is neither read nor written.
-template <class S, class W, bool COMPRESS, int U>
+template <class S, class W, bool COMPRESS, int U, class A = StatNone>
 __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsigned char* dst,
                                                   const typename S::State& st, uint64_t u0,
-                                                  uint64_t nunits, bool div, float fd, int lane) {
+                                                  uint64_t nunits, bool div, float fd, int lane,
+                                                  A&& acc = A{}) {
   using N = typename S::Narrow;
   constexpr int KV = W::kVecs;
 #pragma unroll
@@ -385,7 +426,7 @@ __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsi
       st16<true>(dst + u * 16, compress_unit<W, N>(x));
     } else {
       vec16 o[KV];
-      decompress_unit<W, N>(ld16<true>(src + u * 16), div, fd, o);
+      decompress_unit<W, N>(ld16<true>(src + u * 16), div, fd, o, acc);
 #pragma unroll
       for (int v = 0; v < KV; ++v) st16<true>(dst + (u * KV + v) * 16, o[v]);
     }
@@ -394,9 +435,10 @@ __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsi
 
 // Elements [0, head) and [tail_begin, n_elems), one per thread; `st` at
 // element 0.  a.aligned covers every operand, a side operand included.
-template <class S, class W, bool COMPRESS>
+template <class S, class W, bool COMPRESS, class A = StatNone>
 __device__ __forceinline__ void cast_elements(const CastArgs& a, const typename S::State& st,
-                                              bool div, float fd, uint64_t t, uint64_t stride) {
+                                              bool div, float fd, uint64_t t, uint64_t stride,
+                                              A&& acc = A{}) {
   using N = typename S::Narrow;
   using E = typename W::E;
   const bool al = a.aligned != 0;
@@ -409,7 +451,7 @@ __device__ __forceinline__ void cast_elements(const CastArgs& a, const typename 
       st_e<uint16_t>(a.dst + e * 2, compress_elem<W, N>(ld_e<E>(a.src + e * sizeof(E), al)), al);
     else
       st_e<E>(a.dst + e * sizeof(E),
-              decompress_elem<W, N>(ld_e<uint16_t>(a.src + e * 2, al), div, fd), al);
+              decompress_elem<W, N>(ld_e<uint16_t>(a.src + e * 2, al), div, fd, acc), al);
   }
 }
 

@@ -4,15 +4,72 @@
 // translation unit of its own (plain: bpsr_k_cast_plan.hip,
 // bpsr_k_cast_plan_bf16.hip; error feedback: bpsr_k_cast_ef*.hip; stochastic
 // rounding: bpsr_k_cast_sr*.hip).  What a plan is and how a record is read:
-// bpsr_k_cast_plan.hip.
+// bpsr_k_cast_plan.hip.  The decompress has a STATS variant that also reports
+// each segment's sum of squares and non-finite count.
 #pragma once
 
 #include "bpsr_cast_impl.h"
 
 namespace bpsr {
 
-template <class S, class W, bool COMPRESS, int U, int POL>
-__global__ __launch_bounds__(kBlock) void cast_plan_kernel(typename S::Plan p) {
+// One wave's statistics of one record (byteps_reduce_cast_plan_decompress_stats):
+// kBlock / 64 of them a record, 64 bytes, in a plan-owned array indexed by
+// (record, wave) that cast_stats_finish_kernel adds up per segment.
+struct StatPart {
+  double sumsq;
+  uint64_t nonfinite;
+};
+static_assert(sizeof(StatPart) * (kBlock / 64) == 64, "64 bytes of partials a record");
+
+// The STATS variant's kernel argument: the plan and the partials.
+template <class S>
+struct PlanStats {
+  typename S::Plan plan;
+  StatPart* part;
+};
+template <class P>
+__device__ __forceinline__ const P& plan_of(const P& a) { return a; }
+template <class S>
+__device__ __forceinline__ const typename S::Plan& plan_of(const PlanStats<S>& a) {
+  return a.plan;
+}
+
+// Lane l's 64 bits from lane `from / 4`: the two halves through ds_bpermute.
+__device__ __forceinline__ uint64_t stat_from_lane(uint64_t b, int from) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)(uint32_t)b);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)(uint32_t)(b >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// The sums over the wave's 64 lanes, in every lane: six butterfly steps.  All
+// 64 lanes active.  The pairing is fixed, so the same lane values give the
+// same bits.  C: uint32_t (a record's count) or uint64_t (a segment's).
+template <class C>
+__device__ __forceinline__ void stat_wave_sum(double& x, C& n) {
+  const int l = (int)(threadIdx.x & 63);
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const int from = (l ^ m) * 4;
+    x += bitcast<double>(stat_from_lane(bitcast<uint64_t>(x), from));
+    if constexpr (sizeof(C) == 8) n += stat_from_lane(n, from);
+    else n += (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)n);
+  }
+}
+
+// STATS (decompress only): every lane also squares and classifies the
+// elements it writes (StatAcc), each wave adds its 64 lanes up and one lane
+// stores the wave's partial — no LDS, no barrier, no atomics.  A template
+// parameter: with STATS false the argument is S::Plan itself and the
+// accumulator is StatNone, which is no code.
+template <class S, class W, bool COMPRESS, int U, int POL, bool STATS = false>
+__global__ __launch_bounds__(kBlock) void cast_plan_kernel(
+    std::conditional_t<STATS, PlanStats<S>, typename S::Plan> arg) {
+  static_assert(!(STATS && COMPRESS), "statistics are the decompress's");
+  const typename S::Plan& p = plan_of(arg);
+  // (the plain variant makes the calls below without it, as before: even an
+  // empty accumulator passed by reference changed the compiler's choices in
+  // the error-feedback and stochastic compresses: a 32-bit for a 64-bit compare)
+  [[maybe_unused]] std::conditional_t<STATS, StatAcc, StatNone> acc;
   // grid == nrecords (launch_plan_s): no bounds test in front of the record
   // load, nor of the scheme's load from its parallel array (S::state), which
   // would put a second scalar round trip before them
@@ -47,9 +104,15 @@ __global__ __launch_bounds__(kBlock) void cast_plan_kernel(typename S::Plan p) {
   const bool div = !COMPRESS && divisor > 1;
   const float fd = (float)divisor;
   if (kind == kTileFull) {
-    cast_tile_full<S, W, COMPRESS, U, POL>(src, dst, st, div, fd, threadIdx.x);
+    if constexpr (STATS)
+      cast_tile_full<S, W, COMPRESS, U, POL>(src, dst, st, div, fd, threadIdx.x, acc);
+    else
+      cast_tile_full<S, W, COMPRESS, U, POL>(src, dst, st, div, fd, threadIdx.x);
   } else if (kind == kTilePartial) {
-    cast_tile_guarded<S, W, COMPRESS, U>(src, dst, st, 0, count, div, fd, threadIdx.x);
+    if constexpr (STATS)
+      cast_tile_guarded<S, W, COMPRESS, U>(src, dst, st, 0, count, div, fd, threadIdx.x, acc);
+    else
+      cast_tile_guarded<S, W, COMPRESS, U>(src, dst, st, 0, count, div, fd, threadIdx.x);
   } else {
     CastArgs a;
     a.src = src;
@@ -59,7 +122,16 @@ __global__ __launch_bounds__(kBlock) void cast_plan_kernel(typename S::Plan p) {
     a.grid = 1;
     a.divisor = divisor;
     a.aligned = (int)aligned;
-    cast_elements<S, W, COMPRESS>(a, st, div, fd, threadIdx.x, kBlock);
+    if constexpr (STATS) cast_elements<S, W, COMPRESS>(a, st, div, fd, threadIdx.x, kBlock, acc);
+    else cast_elements<S, W, COMPRESS>(a, st, div, fd, threadIdx.x, kBlock);
+  }
+  if constexpr (STATS) {
+    // every lane is back here, whatever it wrote (a lane that wrote nothing
+    // adds 0 and 0): the record's kBlock / 64 partials are always written
+    stat_wave_sum(acc.sumsq, acc.nonfinite);
+    if ((threadIdx.x & 63) == 0)
+      arg.part[(uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)] =
+          StatPart{acc.sumsq, (uint64_t)acc.nonfinite};
   }
   keep_prefetch(pf);
 }
@@ -95,6 +167,31 @@ static hipError_t launch_plan(bool compress, const CastRec* table, uint32_t nrec
     case WIDE16:
       return compress ? launch_plan_s<S, Wide<WIDE16>, true>(p, u, out_bytes, tu, s)
                       : launch_plan_s<S, Wide<WIDE16>, false>(p, u, out_bytes, tu, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The plain plan's decompress with statistics: the STATS variant, partials to
+// `part` (kBlock / 64 per record).
+template <class N, int WIDE16>
+static hipError_t launch_plan_stats(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                    int divisor, int u, uint64_t out_bytes, StatPart* part,
+                                    const Tuning& tu, hipStream_t s) {
+  using S = CastPlain<N>;
+  if (u != 1 && u != 2 && u != 4) return hipErrorInvalidValue;
+  const PlanStats<S> p{{table, nrecords, divisor}, part};
+  auto go = [&](auto w) {
+    using W = decltype(w);
+    return cast_dispatch(u, cast_store_pol(tu, out_bytes), [&](auto U, auto POL) {
+      return launch_cast_kernel<
+          cast_plan_kernel<S, W, false, decltype(U)::value, decltype(POL)::value, true>>(
+          p, nrecords, tu.occ_min_tiles_batch, tu, s);
+    });
+  };
+  switch (wide_dtype) {
+    case kFloat32: return go(Wide<kFloat32>{});
+    case kFloat64: return go(Wide<kFloat64>{});
+    case WIDE16: return go(Wide<WIDE16>{});
     default: return hipErrorInvalidValue;
   }
 }

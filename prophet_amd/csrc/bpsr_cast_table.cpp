@@ -2,8 +2,9 @@
 // tile records one plan launch reads, compress or decompress, and for an
 // error-feedback plan the parallel array of one residual pointer per record,
 // for a stochastic-rounding plan that of one (first element index, key) per
-// record.  No HIP runtime call (tests/test_cast_table.py, test_cast_table_ef.py
-// and test_cast_table_sr.py build this file with g++).
+// record; and, for the decompress statistics, every segment's records.  No HIP
+// runtime call (tests/test_cast_table.py, test_cast_table_ef.py,
+// test_cast_table_sr.py and test_cast_table_stats.py build this file with g++).
 #include <algorithm>
 #include <cstring>
 
@@ -30,6 +31,7 @@ struct Seg {
   uint64_t nelem;
   CastCut cut;
   uint32_t key;          // stochastic-rounding plans, else 0
+  int index;             // the segment's place in the caller's table
 };
 
 struct Range {
@@ -46,9 +48,10 @@ struct Range {
 // sout: null but for a stochastic-rounding plan; it receives per record the
 // index in its segment of the record's first element and the segment's key,
 // and a segment of more than kSrMaxElems elements is an error.
+// lout: null, or it receives every segment's records (CastSegList).
 static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
                  std::vector<char>& out, std::vector<unsigned char*>* rout,
-                 std::vector<CastSrRec>* sout, CastTableInfo* ti) {
+                 std::vector<CastSrRec>* sout, CastTableInfo* ti, CastSegList* lout = nullptr) {
   const int nsegs = (int)segs.size();
   const bool ef = rout != nullptr;
   const uint64_t es = (uint64_t)elem_size(wide_dtype);
@@ -79,7 +82,7 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
                     static_cast<unsigned char*>(d.resid), (uint64_t)d.nelem,
                     ef ? cast_cut_ef(d.half, d.wide, d.resid, d.nelem)
                        : cast_cut(d.half, d.wide, d.nelem, (int)es),
-                    d.key});
+                    d.key, i});
   }
   // The plan serves both directions, so every range is written in one of
   // them (the residual by the compress): all 2 * live ranges (3 * live with
@@ -121,6 +124,8 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
   if (ef) rtab.reserve((size_t)records);
   std::vector<CastSrRec> stab;
   if (sout) stab.reserve((size_t)records);
+  std::vector<uint32_t> owner;  // the segment of every record, as emitted
+  if (lout) owner.reserve((size_t)records);
   // `first` elements into the segment, `count` units (vector tiles) or
   // elements (element ranges)
   auto put = [&](const Seg& s, uint32_t kind, uint64_t first, uint64_t count) {
@@ -135,6 +140,7 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
     rec += sizeof(r);
     if (ef) rtab.push_back(s.resid + first * es);
     if (sout) stab.push_back(CastSrRec{first, s.key, 0});
+    if (lout) owner.push_back((uint32_t)s.index);
   };
   for (const Seg& s : live) {
     if (s.cut.nunits == 0) {
@@ -152,6 +158,18 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
   for (const Seg& s : live)
     for (uint64_t t = 0; t < s.cut.nunits / tile_units; ++t)
       put(s, kTileFull, s.cut.head + 8 * t * tile_units, tile_units);
+  if (lout) {
+    // counting sort by segment: stable, so a segment's records stay ascending
+    CastSegList l;
+    l.seg_begin.assign((size_t)nsegs + 1, 0);
+    for (uint32_t o : owner) ++l.seg_begin[(size_t)o + 1];
+    for (int i = 0; i < nsegs; ++i) l.seg_begin[(size_t)i + 1] += l.seg_begin[(size_t)i];
+    l.seg_recs.resize(owner.size());
+    std::vector<uint32_t> at(l.seg_begin.begin(), l.seg_begin.end() - 1);
+    for (uint32_t r = 0; r < (uint32_t)owner.size(); ++r) l.seg_recs[at[owner[r]]++] = r;
+    lout->seg_begin.swap(l.seg_begin);
+    lout->seg_recs.swap(l.seg_recs);
+  }
   out.swap(tab);
   if (ef) rout->swap(rtab);
   if (sout) sout->swap(stab);
@@ -165,17 +183,28 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
 
 int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                      std::vector<char>& out, CastTableInfo* ti) {
+  return build_cast_table(segs, nsegs, wide_dtype, copy_vpt, out, ti, nullptr);
+}
+
+int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                     std::vector<char>& out, CastTableInfo* ti, CastSegList* lists) {
   if (wide_dtype != kFloat32 && wide_dtype != kFloat64 && wide_dtype != kBFloat16)
     return fail(BYTEPS_REDUCE_EDTYPE, "fp16 compression of data type %d", wide_dtype);
   if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
   std::vector<Desc> d((size_t)nsegs);
   for (int i = 0; i < nsegs; ++i) d[i] = {segs[i].wide, segs[i].half, nullptr, segs[i].nelem, 0};
-  return build(d, wide_dtype, copy_vpt, out, nullptr, nullptr, ti);
+  return build(d, wide_dtype, copy_vpt, out, nullptr, nullptr, ti, lists);
 }
 
 int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                         std::vector<char>& out, std::vector<unsigned char*>& resid_out,
                         CastTableInfo* ti) {
+  return build_cast_table_ef(segs, nsegs, wide_dtype, copy_vpt, out, resid_out, ti, nullptr);
+}
+
+int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                        std::vector<char>& out, std::vector<unsigned char*>& resid_out,
+                        CastTableInfo* ti, CastSegList* lists) {
   if (wide_dtype != kFloat32)
     return fail(BYTEPS_REDUCE_EDTYPE, "error-feedback compression of data type %d (FLOAT32 only)",
                 wide_dtype);
@@ -183,12 +212,18 @@ int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dty
   std::vector<Desc> d((size_t)nsegs);
   for (int i = 0; i < nsegs; ++i)
     d[i] = {segs[i].wide, segs[i].half, segs[i].resid, segs[i].nelem, 0};
-  return build(d, wide_dtype, copy_vpt, out, &resid_out, nullptr, ti);
+  return build(d, wide_dtype, copy_vpt, out, &resid_out, nullptr, ti, lists);
 }
 
 int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                         std::vector<char>& out, std::vector<CastSrRec>& sr_out,
                         CastTableInfo* ti) {
+  return build_cast_table_sr(segs, nsegs, wide_dtype, copy_vpt, out, sr_out, ti, nullptr);
+}
+
+int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
+                        std::vector<char>& out, std::vector<CastSrRec>& sr_out,
+                        CastTableInfo* ti, CastSegList* lists) {
   if (wide_dtype != kFloat32)
     return fail(BYTEPS_REDUCE_EDTYPE,
                 "stochastic-rounding compression of data type %d (FLOAT32 only)", wide_dtype);
@@ -196,7 +231,7 @@ int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dty
   std::vector<Desc> d((size_t)nsegs);
   for (int i = 0; i < nsegs; ++i)
     d[i] = {segs[i].wide, segs[i].half, nullptr, segs[i].nelem, segs[i].key};
-  return build(d, wide_dtype, copy_vpt, out, nullptr, &sr_out, ti);
+  return build(d, wide_dtype, copy_vpt, out, nullptr, &sr_out, ti, lists);
 }
 
 }  // namespace bpsr

@@ -420,6 +420,23 @@ hipError_t launch_cast_plan(bool compress, const CastRec* table, uint32_t nrecor
 hipError_t launch_cast_plan_bf16(bool compress, const CastRec* table, uint32_t nrecords,
                                  int wide_dtype, int divisor, int u, uint64_t out_bytes,
                                  const Tuning& tu, hipStream_t s);
+// The decompress with statistics (byteps_reduce_cast_plan_decompress_stats,
+// DESIGN.md §11.5): the plain decompress's bytes, and per record kBlock / 64
+// wave partials {f64 sum of the squares of the finite values written, u64
+// count of the others} at part[record * (kBlock / 64) + wave], 64 bytes a
+// record ...
+constexpr size_t kStatPartBytes = 64;
+hipError_t launch_cast_plan_stats(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                  int divisor, int u, uint64_t out_bytes, void* part,
+                                  const Tuning& tu, hipStream_t s);
+hipError_t launch_cast_plan_stats_bf16(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                       int divisor, int u, uint64_t out_bytes, void* part,
+                                       const Tuning& tu, hipStream_t s);
+// ... which this adds up per segment, one workgroup each, in an order the plan
+// alone fixes: stats[2 s] = sum of squares, stats[2 s + 1] = (double)count, for
+// the records seg_recs[seg_begin[s] .. seg_begin[s + 1]).  Every row is written.
+hipError_t launch_cast_stats_finish(const uint32_t* seg_begin, const uint32_t* seg_recs,
+                                    const void* part, double* stats, int nsegs, hipStream_t s);
 // Error-feedback compress (bpsr_cast_ef.h; bpsr_k_cast_ef.hip: fp16 wire,
 // bpsr_k_cast_ef_bf16.hip: bf16 wire): nelem f32 ELEMENTS of src plus the f32
 // residual to the wire format at dst, the residual updated in place.  Operands

@@ -28,4 +28,90 @@ hipError_t launch_cast_plan(bool compress, const CastRec* table, uint32_t nrecor
                                            out_bytes, tu, s);
 }
 
+hipError_t launch_cast_plan_stats(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                  int divisor, int u, uint64_t out_bytes, void* part,
+                                  const Tuning& tu, hipStream_t s) {
+  return launch_plan_stats<NarrowF16, kBFloat16>(table, nrecords, wide_dtype, divisor, u,
+                                                 out_bytes, static_cast<StatPart*>(part), tu, s);
+}
+
+// Finishes the statistics, one workgroup per segment, on the stream of the
+// decompress (the kernel boundary makes every XCD's partials visible).  The
+// segment's records — seg_recs[seg_begin[s] .. seg_begin[s + 1]), ascending —
+// are dealt to the lanes in that order, lane t taking records t, t +
+// kFinishBlock, ...; a lane adds its records' partials as they come, ascending
+// record then wave; the waves add their lanes up (stat_wave_sum) and lane 0 the
+// waves, in wave order.  The order depends on the plan alone.  Every row is
+// written: a segment without records (nelem == 0) gets {0, 0}.
+// One segment can own most of a plan's records (a 64 Mi-element tensor: 16 Ki
+// records, 1 MiB of partials), and a record costs two dependent round trips —
+// its index, then its 64 bytes of partials — to memory another XCD wrote.  One
+// entry at a time on 256 lanes that was 0.16 ms against the decompress's 0.07
+// (kernel trace).  So 1024 lanes; each loads kFinishIdx record
+// indices at once, then the partials of kFinishAhead records at once.
+constexpr uint32_t kFinishBlock = 1024, kFinishIdx = 16, kFinishAhead = 4;
+__global__ __launch_bounds__(kFinishBlock) void cast_stats_finish_kernel(
+    const uint32_t* __restrict__ seg_begin, const uint32_t* __restrict__ seg_recs,
+    const StatPart* __restrict__ part, double* __restrict__ stats) {
+  constexpr uint32_t kWaves = kBlock / 64;  // partials a record
+  constexpr uint32_t kFinishWaves = kFinishBlock / 64;
+  __shared__ double wsum[kFinishWaves];
+  __shared__ uint64_t wcnt[kFinishWaves];
+  const uint32_t s = blockIdx.x, b = seg_begin[s], n = seg_begin[s + 1] - b;
+  double sum = 0.0;
+  uint64_t cnt = 0;
+  for (uint32_t r0 = threadIdx.x; r0 < n; r0 += kFinishBlock * kFinishIdx) {
+    // n < 2^31 (build_cast_table) and r0 < n: r0 + a * kFinishBlock < 2^32
+    uint32_t rec[kFinishIdx];
+#pragma unroll
+    for (uint32_t a = 0; a < kFinishIdx; ++a) {
+      const uint32_t r = r0 + a * kFinishBlock;
+      rec[a] = r < n ? seg_recs[b + r] : 0;
+    }
+#pragma unroll
+    for (uint32_t a0 = 0; a0 < kFinishIdx; a0 += kFinishAhead) {
+      StatPart q[kFinishAhead][kWaves];
+#pragma unroll
+      for (uint32_t a = 0; a < kFinishAhead; ++a)
+#pragma unroll
+        for (uint32_t w = 0; w < kWaves; ++w)
+          q[a][w] = r0 + (a0 + a) * kFinishBlock < n ? part[(uint64_t)rec[a0 + a] * kWaves + w]
+                                                     : StatPart{0.0, 0};
+#pragma unroll
+      for (uint32_t a = 0; a < kFinishAhead; ++a)
+        if (r0 + (a0 + a) * kFinishBlock < n) {
+#pragma unroll
+          for (uint32_t w = 0; w < kWaves; ++w) {
+            sum += q[a][w].sumsq;
+            cnt += q[a][w].nonfinite;
+          }
+        }
+    }
+  }
+  stat_wave_sum(sum, cnt);
+  if ((threadIdx.x & 63) == 0) {
+    wsum[threadIdx.x >> 6] = sum;
+    wcnt[threadIdx.x >> 6] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double total = wsum[0];
+    uint64_t c = wcnt[0];
+    for (uint32_t w = 1; w < kFinishWaves; ++w) {
+      total += wsum[w];
+      c += wcnt[w];
+    }
+    stats[2 * (uint64_t)s] = total;
+    stats[2 * (uint64_t)s + 1] = (double)c;
+  }
+}
+
+hipError_t launch_cast_stats_finish(const uint32_t* seg_begin, const uint32_t* seg_recs,
+                                    const void* part, double* stats, int nsegs, hipStream_t s) {
+  if (nsegs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cast_stats_finish_kernel, dim3((uint32_t)nsegs), dim3(kFinishBlock), 0, s,
+                     seg_begin, seg_recs, static_cast<const StatPart*>(part), stats);
+  return hipGetLastError();
+}
+
 }  // namespace bpsr

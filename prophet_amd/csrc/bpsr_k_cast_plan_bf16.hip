@@ -13,4 +13,11 @@ hipError_t launch_cast_plan_bf16(bool compress, const CastRec* table, uint32_t n
                                            out_bytes, tu, s);
 }
 
+hipError_t launch_cast_plan_stats_bf16(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                       int divisor, int u, uint64_t out_bytes, void* part,
+                                       const Tuning& tu, hipStream_t s) {
+  return launch_plan_stats<NarrowBF16, kFloat16>(table, nrecords, wide_dtype, divisor, u,
+                                                 out_bytes, static_cast<StatPart*>(part), tu, s);
+}
+
 }  // namespace bpsr

@@ -55,6 +55,14 @@ independent bits — and the step is a per-worker counter (``Worker.sr_step``)
 that advances by one for every stochastic compress call or plan launch, so no
 ``(key, step)`` pair is used twice.  The init push is the plain cast; the
 decompress is the plain compressor's.
+
+``push_pull(..., stats=True)`` / ``push_pull_iteration(..., stats=True)`` make
+the decompress the statistics one (``decompress_many_into(..., stats=)``,
+DESIGN.md §11.5) and leave ``Worker.grad_stats``: per compressed context the
+sum of squares and the non-finite count of the aggregate just written — the
+global gradient norm and GradScaler's ``found_inf`` without a second sweep.
+For device tensors the rows and everything derived from them stay on the
+device, in stream order.
 """
 from __future__ import annotations
 
@@ -113,6 +121,51 @@ class Context:
     init_lock: threading.Lock = field(default_factory=threading.Lock)
 
 
+class GradStats:
+    """The decompress statistics of one ``push_pull(stats=True)`` /
+    ``push_pull_iteration(stats=True)``: ``names`` — the compressed contexts,
+    in row order; ``rows`` — float64 ``[len(names), 2]``, row i the sum of the
+    squares of the finite values written to context i's output and the count
+    of its non-finite ones (``compression.decompress_stats``); ``skipped`` —
+    the contexts of the call that travel uncompressed and so have no row.
+    ``rows`` lives where the outputs live.  For device rows every method
+    returns a 0-d device tensor and nothing synchronises with the host: a
+    caller can clip (``torch.clamp(max_norm / (stats.norm() + eps), max=1)``)
+    or skip (``torch.where(stats.nonfinite() > 0, ...)``) on the device in
+    stream order."""
+
+    def __init__(self, names, rows, skipped=()):
+        self.names = list(names)
+        self.rows = rows
+        self.skipped = list(skipped)
+
+    def __getitem__(self, name: str):
+        """The row of context ``name``: ``(sumsq, nonfinite)``."""
+        return self.rows[self.names.index(name)]
+
+    def sumsq(self):
+        """The sum of squares over all rows."""
+        return self.rows[:, 0].sum()
+
+    def nonfinite(self):
+        """The number of non-finite values over all rows (float64)."""
+        return self.rows[:, 1].sum()
+
+    def norm(self):
+        """The global L2 norm of the finite values: ``sqrt(sumsq())``."""
+        t = self.sumsq()
+        return t.sqrt() if hasattr(t, "data_ptr") else t ** 0.5
+
+
+def _stat_rows(n: int, like):
+    """float64 ``[n, 2]`` where ``like`` lives."""
+    if hasattr(like, "data_ptr"):
+        import torch
+        return torch.empty((n, 2), dtype=torch.float64, device=like.device)
+    import numpy as np
+    return np.empty((n, 2), dtype=np.float64)
+
+
 class Worker:
     """One BytePS worker (its root device) talking to the server front end."""
 
@@ -153,6 +206,9 @@ class Worker:
         self.sr_seed = int(sr_seed) & 0xffffffff
         self._sr_step = 0
         self._sr_lock = threading.Lock()
+        # the decompress statistics of the last push_pull / push_pull_iteration
+        # with stats=True (GradStats); None before the first
+        self.grad_stats = None
 
     @property
     def sr_step(self) -> int:
@@ -224,18 +280,23 @@ class Worker:
 
     # ---------------------------------------------------------------- push_pull
     def push_pull(self, name: str, tensor, output=None, order=None,
-                  average: bool = False) -> None:
+                  average: bool = False, stats: bool = False) -> None:
         """EnqueueTensor + the PUSH/PULL stages for one tensor: push every
         partition (in ``order`` — a list of partition indices — if given), then
         pull every partition into ``output`` (default: ``tensor`` itself, in
         place, as byteps_push_pull does).  ``average``: divide the sum by the
         number of workers afterwards, as byteps/torch's push_pull(average=True)
-        does (floating dtypes only)."""
+        does (floating dtypes only).  ``stats``: a compressed context's
+        decompress also leaves ``grad_stats`` (one row; a device tensor's
+        through a one-segment cast plan kept on this worker); an uncompressed
+        context has no row and is named in ``grad_stats.skipped``."""
         ctx = self.contexts[name]
         if not ctx.initialized:
             raise RuntimeError(f"{name}: init_tensor first")
         if ctx.compressor is not None:
-            return self._push_pull_compressed(ctx, tensor, output, order, average)
+            return self._push_pull_compressed(ctx, tensor, output, order, average, stats)
+        if stats:
+            self.grad_stats = GradStats([], _stat_rows(0, tensor), [name])
         if _nbytes(tensor) != ctx.size:
             raise ValueError(f"{name}: {_nbytes(tensor)} bytes, declared {ctx.size}")
         out = tensor if output is None else output
@@ -254,7 +315,8 @@ class Worker:
                 raise ValueError("average: the frontend does not know the worker count")
             _divide_(out, size)
 
-    def _push_pull_compressed(self, ctx: Context, tensor, output, order, average: bool) -> None:
+    def _push_pull_compressed(self, ctx: Context, tensor, output, order, average: bool,
+                              stats: bool = False) -> None:
         """push_pull of a context initialised with a compressor: cast into the
         context's staging buffer, push and pull THAT (its partitions, the wire
         dtype — FLOAT16 or BFLOAT16 — in the request word), then one launch
@@ -289,7 +351,13 @@ class Worker:
             self.frontend.push(cmd, key, self.rank, _slice(wire, off, ln), ln)
         for key, off, ln in ctx.parts:
             self.frontend.pull(key, _slice(wire, off, ln), ln)
-        ctx.compressor.decompress_into(_contiguous(out), wire, divisor)
+        if not stats:
+            ctx.compressor.decompress_into(_contiguous(out), wire, divisor)
+            return
+        rows = _stat_rows(1, out)
+        ctx.compressor.decompress_into(_contiguous(out), wire, divisor, stats=rows[0],
+                                       plans=self._cast_plans)
+        self.grad_stats = GradStats([ctx.name], rows)
 
     # byteps/torch/ops.py: push_pull_async -> handle, poll(handle),
     # synchronize(handle).  Calls run in call order on the worker's own
@@ -352,7 +420,8 @@ class Worker:
         self.push_pull(name, src, output=out)
         return out
 
-    def push_pull_iteration(self, tensors: dict, scheduler=None, average: bool = False) -> list:
+    def push_pull_iteration(self, tensors: dict, scheduler=None, average: bool = False,
+                            stats: bool = False) -> list:
         """One training iteration: every declared tensor, gradients arriving in
         backward order (highest declared index first).  With a Prophet
         ``scheduler`` (``ProphetPushQueue``) the partitions are pushed in the
@@ -363,6 +432,10 @@ class Worker:
         this worker).  ``average``: divide by the number of workers as
         ``push_pull(average=True)`` does — compressed contexts on the 2-byte
         value inside the decompress, the others in place afterwards.
+        ``stats``: the decompress is the statistics one and ``grad_stats``
+        holds one row per compressed context, grouped by compressor in the
+        order the compressors first appear (``grad_stats.names``); the rows
+        live where the first compressed tensor lives.
         Returns the release groups as lists of (declared key, partition)."""
         from .prophet import PushTask, release_groups
         ctxs = [self.contexts[n] for n in self._declared if n in tensors]
@@ -412,11 +485,20 @@ class Worker:
         for c in ctxs:
             for key, off, ln in c.parts:
                 self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
+        rows, at = None, 0
+        if stats:
+            names = [c.name for cs in casts.values() for c in cs]
+            rows = _stat_rows(len(names), tensors[names[0]] if names else None)
+            self.grad_stats = GradStats(names, rows,
+                                        [c.name for c in ctxs if c.compressor is None])
         for comp, cs in casts.items():
             # an error-feedback plan decompresses too: named by its residuals
             # — and a stochastic-rounding plan, named by its keys
             extra = {"residuals": [c.residual for c in cs]} if comp.ERROR_FEEDBACK else \
                 {"keys": [c.sr_key for c in cs]} if comp.STOCHASTIC else {}
+            if stats:
+                extra["stats"] = rows[at:at + len(cs)]
+                at += len(cs)
             comp.decompress_many_into([_contiguous(tensors[c.name]) for c in cs],
                                       [c.staging for c in cs], divisor,
                                       plans=self._cast_plans, **extra)
@@ -476,4 +558,4 @@ def _slice(x, off: int, ln: int):
     return x.reshape(-1).view(np.uint8)[off:off + ln]
 
 
-__all__ = ["ServerFrontend", "Worker", "Context", "K_DEFAULT_PUSH_PULL", "DType", "elem_size"]
+__all__ = ["ServerFrontend", "Worker", "Context", "GradStats", "K_DEFAULT_PUSH_PULL", "DType", "elem_size"]

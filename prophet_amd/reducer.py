@@ -65,6 +65,7 @@ EXPORTS = (
     "byteps_reduce_compress_ef", "byteps_reduce_cast_plan_create_ef",
     "byteps_reduce_compress_sr", "byteps_reduce_cast_plan_create_sr",
     "byteps_reduce_cast_plan_compress_sr",
+    "byteps_reduce_cast_plan_decompress_stats",
 )
 
 
@@ -166,6 +167,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_cast_plan_create_sr.argtypes = [ctypes.POINTER(CastSrDesc), _int, _int, _int,
                                                     ctypes.POINTER(_vp)]
     L.byteps_reduce_cast_plan_compress_sr.argtypes = [_vp, ctypes.c_uint32, _vp]
+    L.byteps_reduce_cast_plan_decompress_stats.argtypes = [_vp, _int, _vp, _vp]
     _LIB = L
     return L
 
@@ -529,15 +531,45 @@ class CastPlan:
         _check(self.lib.byteps_reduce_cast_plan_compress(self.handle,
                                                          _stream_of(self.first, stream)))
 
-    def decompress(self, divisor: int = 1, stream=None) -> None:
-        _check(self.lib.byteps_reduce_cast_plan_decompress(self.handle, int(divisor),
-                                                           _stream_of(self.first, stream)))
+    def decompress(self, divisor: int = 1, stream=None, stats=None) -> None:
+        """One launch.  With ``stats`` — a contiguous float64 device tensor
+        of ``2 * nsegs`` elements on the plan's device, or a raw pointer to as
+        much — the same bytes are written and ``stats[2 s], stats[2 s + 1]``
+        receive segment ``s``'s sum of the squares of the finite values
+        written (f64) and the count of the non-finite ones
+        (byteps_reduce_cast_plan_decompress_stats; a second, small launch on
+        the same stream).  A tensor is bounds-checked like the other
+        operands, and the plan holds it until its next statistics call or
+        ``close``: the launches are asynchronous.  A plan's first statistics
+        call allocates its partial sums; two statistics launches of one plan
+        must not run concurrently."""
+        if stats is None:
+            _check(self.lib.byteps_reduce_cast_plan_decompress(self.handle, int(divisor),
+                                                               _stream_of(self.first, stream)))
+            return
+        if hasattr(stats, "data_ptr"):
+            import torch
+            if stats.dtype != torch.float64:
+                raise ValueError(f"stats must be float64, got {stats.dtype}")
+            if not stats.is_contiguous():
+                raise ValueError("stats must be contiguous")
+            if stats.numel() != 2 * self.nsegs:
+                raise ValueError(f"stats has {stats.numel()} elements, the plan's "
+                                 f"{self.nsegs} segments need {2 * self.nsegs}")
+            dev = getattr(self.first, "device", None)
+            if stats.device.type != "cuda" or (dev is not None and stats.device != dev):
+                raise ValueError(f"stats is on {stats.device}, the plan on {dev or 'a device'}")
+            _fits(16 * self.nsegs, stats)
+        self._stats = stats           # held: the launches are asynchronous
+        _check(self.lib.byteps_reduce_cast_plan_decompress_stats(
+            self.handle, int(divisor), _ptr(stats), _stream_of(self.first, stream)))
 
     def close(self) -> None:
         if self.handle:
             self.lib.byteps_reduce_cast_plan_destroy(self.handle)
             self.handle = _vp()
         self._keep = []
+        self._stats = None
 
     def __del__(self):
         try:

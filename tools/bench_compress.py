@@ -98,6 +98,28 @@ are compared with the numpy definition (prophet_amd/sr.py).  Gates:
 
   sr_bf16 faster than sr_torch by more than the SUM of the two spreads;
   the SR plan faster than the loop by more than the larger of the two spreads.
+
+``--stats`` measures the decompress with statistics
+(byteps_reduce_cast_plan_decompress_stats: per segment the sum of squares and
+the non-finite count of what the decompress writes) in one
+run, by the same method, the candidates alternated round by round, over the
+ResNet-50 table (165 f32 segments, divisor 8) and over one ``--elems`` segment:
+
+  plan        the plain plan decompress (6 B an element);
+  plan_stats  the decompress with statistics, both kernels (6 B an element);
+  torch       the plain plan decompress followed by what a user writes today —
+              table: torch._foreach_norm over the 165 outputs, stack, norm, and
+              isfinite over the stacked norms (GradScaler's way: a non-finite
+              element makes its tensor's norm non-finite); one segment:
+              vector_norm and isfinite of it.  A second read of every output:
+              10 B an element at least.
+
+The statistics are compared with torch's f64 arithmetic on the device first
+(counts exact, sums within nelem * 2^-52).  Gate, at both shapes:
+
+  plan_stats faster than torch by more than the larger of the two spreads.
+
+``plan_stats / plan`` is recorded, not gated.
 """
 import argparse
 import json
@@ -156,7 +178,12 @@ def main() -> int:
     p.add_argument("--sr", action="store_true",
                    help="the stochastic-rounding compress against torch's composition, the "
                         "plain and the error-feedback compress; the ResNet-50 table as one SR plan")
+    p.add_argument("--stats", action="store_true",
+                   help="the decompress with statistics against the plain decompress and "
+                        "torch's norm + isfinite after it; the ResNet-50 table and one segment")
     args = p.parse_args()
+    if args.stats:
+        return stats_mode(args)
     if args.sr:
         return sr_mode(args)
     if args.ef:
@@ -823,6 +850,111 @@ def sr_mode(args) -> int:
         with open(args.out, "a") as f:
             f.write(line + "\n")
     ok = all(gates.values()) and all(same.values()) and out["plan_bit_equal_to_per_segment_calls"]
+    return 0 if ok else 1
+
+
+def stats_mode(args) -> int:
+    """The decompress with statistics: against the plain decompress, and
+    against the plain decompress followed by torch's norm and isfinite."""
+    import torch
+
+    from prophet_amd.dtypes import DType
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    F32 = DType.FLOAT32
+    wd, tdt = {"fp16": (DType.FLOAT16, torch.float16),
+               "bf16": (DType.BFLOAT16, torch.bfloat16)}[args.wire]
+    DIV = 8
+    out = {"tool": "bench_compress", "mode": "decompress statistics", "wire": args.wire,
+           "divisor": DIV, "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+
+    def shape(label, nsegs_rows, arena_elems):
+        """One shape: ``nsegs_rows`` = (first element, elements) per segment."""
+        nelem = sum(n for _, n in nsegs_rows)
+        with step(f"setup, {label}", 120):
+            g = torch.Generator(device=dev).manual_seed(7)
+            sets = []
+            for _ in range(args.sets):
+                half = (torch.randn(arena_elems, device=dev, generator=g) * 64).to(tdt)
+                wide = torch.empty(arena_elems, device=dev)
+                outs = [wide[o:o + n] for o, n in nsegs_rows]
+                sets.append({"wide": wide, "half": half, "outs": outs,
+                             "st": torch.empty(2 * len(outs), dtype=torch.float64, device=dev),
+                             "plan": red.cast_plan([(w, half[o:o + n], n)
+                                                    for w, (o, n) in zip(outs, nsegs_rows)],
+                                                   F32, wd)})
+            for s in sets:                       # the first statistics call allocates
+                s["plan"].decompress(DIV, stats=s["st"])
+            torch.cuda.synchronize()
+
+        def torch_after(k):
+            s = sets[k]
+            s["plan"].decompress(DIV)
+            if len(s["outs"]) == 1:
+                nrm = torch.linalg.vector_norm(s["outs"][0])
+                return nrm, torch.isfinite(nrm)
+            per = torch.stack(torch._foreach_norm(s["outs"]))
+            return per.norm(), torch.isfinite(per).logical_not().sum()
+
+        with step(f"check, {label}", 120):
+            s = sets[0]
+            s["st"].fill_(float("nan"))
+            s["plan"].decompress(DIV, stats=s["st"])
+            got = s["st"].view(-1, 2)
+            ref = torch.stack([w.double().square().sum() for w in s["outs"]])
+            tol = torch.tensor([n * 2.0 ** -52 for _, n in nsegs_rows], dtype=torch.float64,
+                               device=dev) * ref
+            plain = s["wide"].clone()
+            s["wide"].fill_(-1.0)
+            s["plan"].decompress(DIV)
+            checks[label] = {
+                "sumsq_within_bound": bool(((got[:, 0] - ref).abs() <= tol).all()),
+                "nonfinite_zero": bool((got[:, 1] == 0).all()),
+                "bytes_equal_plain": bool(torch.equal(plain.view(torch.int32),
+                                                      s["wide"].view(torch.int32))),
+                "norm": float(got[:, 0].sum().sqrt()), "torch_norm": float(torch_after(0)[0])}
+            del plain, ref
+            torch.cuda.synchronize()
+        res = timed_rounds(torch, {
+            "plan": (lambda k: sets[k]["plan"].decompress(DIV), args.inner),
+            "plan_stats": (lambda k: sets[k]["plan"].decompress(DIV, stats=sets[k]["st"]),
+                           args.inner),
+            "torch": (torch_after, args.inner)}, len(sets), args)
+        for name, per in (("plan", 6), ("plan_stats", 6), ("torch", 10)):
+            res[name]["bytes_per_elem"] = per
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        sp = max(res["plan_stats"]["spread_ms"], res["torch"]["spread_ms"])
+        gates[f"{label}_plan_stats_beats_torch"] = res["torch"]["ms"] - res["plan_stats"]["ms"] > sp
+        for s in sets:
+            s["plan"].close()
+        return {"segments": len(nsegs_rows), "elems": nelem, "results": res,
+                "gate_spread_ms": sp,
+                "plan_stats_over_plan": round(res["plan_stats"]["ms"] / res["plan"]["ms"], 3),
+                "torch_over_plan_stats": round(res["torch"]["ms"] / res["plan_stats"]["ms"], 2)}
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    total_bytes, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    out["iteration"] = shape("table", [(o // 2, ln // 2) for o, ln in rows], total_bytes // 2)
+    torch.cuda.empty_cache()
+    out["big"] = shape("big", [(0, args.elems)], args.elems)
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    ok = all(gates.values()) and all(v for c in checks.values() for k, v in c.items()
+                                     if isinstance(v, bool))
     return 0 if ok else 1
 
 
