@@ -230,15 +230,15 @@ def _new_plan(wide_dtype: int, pairs, wire_dtype: int = 2):
                             wide_dtype, wire_dtype)
 
 
-def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None, keys=None,
-               step=None, stats=None) -> None:
+def _cast_many(comp, pairs, compress: bool, divisor: int, plans, extras=None, step=None,
+               stats=None) -> None:
     """``pairs`` of ``(wide, half)`` tensors or arrays cast by compressor
     ``comp``: the device ones as one plan launch per (device, wide dtype, wire
-    dtype), the host ones one by one.  With ``residuals`` (one per pair) the
-    plans are error-feedback plans: the compress is ``compress_ef_into``'s,
-    the decompress the plain one through the same plan.  With ``keys`` (one
-    per pair) they are stochastic-rounding plans: the compress is
-    ``compress_sr_into``'s under ``step``, the decompress again the plain one
+    dtype), the host ones one by one.  ``extras`` (one per pair, as a cast
+    plan's segments carry them) name the scheme: with f32 residuals the plans
+    are error-feedback plans and the compress is ``compress_ef_into``'s, with
+    ``SrKey`` keys they are stochastic-rounding plans and the compress is
+    ``compress_sr_into``'s under ``step``; the decompress is the plain one
     through the same plan.  ``stats`` (decompress only): float64
     ``[len(pairs), 2]``, row i the statistics of pair i — a device pair's row
     lives on its device, a host pair's on the host; each plan writes its own
@@ -250,37 +250,25 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None,
     groups: dict = {}
     rows: dict = {}
     for i, (wide, half) in enumerate(pairs):
-        resid = None if residuals is None else residuals[i]
+        extra = None if extras is None else extras[i]
         if not _on_device(wide) and not _on_device(half):
-            if not compress:
+            if compress:
+                comp.compress_with(half, wide, extra, step)
+            else:
                 if stats is not None and _on_device(stats):
                     raise ValueError(f"stats is on {stats.device}, tensor {i} on the host")
                 comp.decompress_into(wide, half, divisor,
                                      **({} if stats is None else {"stats": stats[i]}))
-            elif keys is not None:
-                comp.compress_sr_into(half, wide, keys[i], step)
-            elif resid is None:
-                comp.compress_into(half, wide)
-            else:
-                comp.compress_ef_into(half, resid, wide)
             continue
-        from .torch_ops import _check_cast, _check_cast_ef
-        wire = comp.wire_torch_dtype()
-        if keys is not None:
-            from .torch_ops import _check_cast_sr
-            _check_cast_sr(half, wide, wire)
-            seg = (wide.reshape(-1), half.reshape(-1), SrKey(int(keys[i]) & 0xffffffff))
-        elif resid is None:
-            _check_cast(half, wide, wire)
-            seg = (wide.reshape(-1), half.reshape(-1))
-        else:
-            _check_cast_ef(half, resid, wide, wire)
-            seg = (wide.reshape(-1), half.reshape(-1), resid.reshape(-1))
+        comp._check_segment(half, wide, extra)
+        seg = (wide.reshape(-1), half.reshape(-1)) + (
+            () if extra is None else (extra.reshape(-1) if _is_torch(extra) else extra,))
         if stats is not None and (not _on_device(stats) or stats.device != wide.device):
             raise ValueError(f"stats is on {getattr(stats, 'device', 'the host')}, "
                              f"tensor {i} on {wide.device}")
-        groups.setdefault((wide.device, wide.dtype, wire), []).append(seg)
-        rows.setdefault((wide.device, wide.dtype, wire), []).append(i)
+        key = (wide.device, wide.dtype, comp.wire_torch_dtype())
+        groups.setdefault(key, []).append(seg)
+        rows.setdefault(key, []).append(i)
     if not groups:
         return
     import torch
@@ -291,10 +279,8 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, residuals=None,
                 else _new_plan(from_torch(dtype), segs, from_torch(wire))
             stream = torch.cuda.current_stream(device)
             try:
-                if compress and keys is not None:
-                    plan.compress(step=step, stream=stream)
-                elif compress:
-                    plan.compress(stream=stream)
+                if compress:
+                    plan.compress(stream=stream, step=step)
                 elif stats is None:
                     plan.decompress(int(divisor), stream=stream)
                 else:
@@ -485,9 +471,48 @@ class _CastCompressor(Compressor):
         returns ``outs``.  ``stats``: a float64 tensor or array of shape
         ``(len(outs), 2)`` where the outputs live; row i receives
         ``decompress_stats(outs[i])``."""
+        return cls.decompress_many_with(outs, compressed, None, divisor, plans, stats)
+
+    # The forms that take the scheme's per-tensor operand — an error-feedback
+    # residual, a stochastic-rounding SrKey, None for the plain cast — as cast
+    # plans and push_pull's contexts carry it.  The scheme mix-ins override all
+    # but the last; given None, theirs are these.
+    @classmethod
+    def cast_extra(cls, tensor, key):
+        """The operand a context of this compressor keeps for ``tensor``;
+        ``key()`` is the context's stochastic-rounding key."""
+        return None
+
+    @classmethod
+    def _check_segment(cls, half, wide, extra) -> None:
+        """The device operands of one cast-plan segment."""
+        from .torch_ops import _check_cast
+        _check_cast(half, wide, cls.wire_torch_dtype())
+
+    @classmethod
+    def compress_with(cls, out, tensor, extra=None, step=None):
+        """This compressor's compress of one tensor: ``compress_into``,
+        ``compress_ef_into`` or ``compress_sr_into``."""
+        return cls.compress_into(out, tensor)
+
+    @classmethod
+    def compress_many_with(cls, outs, tensors, extras, step=None,
+                           plans: CastPlanCache | None = None):
+        """... of many: ``compress_many_into``, ``compress_many_ef_into`` or
+        ``compress_many_sr_into``."""
+        return cls.compress_many_into(outs, tensors, plans)
+
+    @classmethod
+    def decompress_many_with(cls, outs, compressed, extras, divisor: int = 1,
+                             plans: CastPlanCache | None = None, stats=None):
+        """``decompress_many_into``; ``extras`` (those of the compress over the
+        same tensors, or None) only name the plan: every scheme's decompress is
+        the plain one, so one cached plan serves both directions, and residuals
+        are not touched."""
         if len(outs) != len(compressed):
             raise ValueError("decompress_many_into: as many outputs as compressed tensors")
-        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans, stats=stats)
+        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans, extras=extras,
+                   stats=stats)
         return outs
 
 
@@ -539,6 +564,27 @@ class _ErrorFeedback:
         return _is_f32(tensor)
 
     @classmethod
+    def cast_extra(cls, tensor, key):
+        return cls.residual_like(tensor)
+
+    @classmethod
+    def _check_segment(cls, half, wide, resid) -> None:
+        if resid is None:
+            return super()._check_segment(half, wide, None)
+        from .torch_ops import _check_cast_ef
+        _check_cast_ef(half, resid, wide, cls.wire_torch_dtype())
+
+    @classmethod
+    def compress_with(cls, out, tensor, resid=None, step=None):
+        return cls.compress_into(out, tensor) if resid is None else \
+            cls.compress_ef_into(out, resid, tensor)
+
+    @classmethod
+    def compress_many_with(cls, outs, tensors, residuals, step=None,
+                           plans: CastPlanCache | None = None):
+        return cls.compress_many_ef_into(outs, residuals, tensors, plans)
+
+    @classmethod
     def residual_like(cls, x):
         """A zeroed f32 residual of x's kind, device and element count."""
         if _is_torch(x):
@@ -581,7 +627,7 @@ class _ErrorFeedback:
         for t, r in zip(tensors, residuals):
             if not cls.compresses(t) or not _is_f32(r):
                 raise ValueError("error feedback needs float32 tensors and float32 residuals")
-        _cast_many(cls, list(zip(tensors, outs)), True, 1, plans, residuals=list(residuals))
+        _cast_many(cls, list(zip(tensors, outs)), True, 1, plans, extras=list(residuals))
         return outs
 
     @classmethod
@@ -591,11 +637,9 @@ class _ErrorFeedback:
         ``compress_many_ef_into`` over the same tensors) only names the plan:
         the error-feedback plan's own decompress is the plain one, so one
         cached plan serves both directions; the residuals are not touched."""
-        if len(outs) != len(compressed):
-            raise ValueError("decompress_many_into: as many outputs as compressed tensors")
-        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans,
-                   residuals=None if residuals is None else list(residuals), stats=stats)
-        return outs
+        return cls.decompress_many_with(outs, compressed,
+                                        None if residuals is None else list(residuals),
+                                        divisor, plans, stats)
 
 
 class FP16EFCompressor(_ErrorFeedback, FP16Compressor):
@@ -604,6 +648,11 @@ class FP16EFCompressor(_ErrorFeedback, FP16Compressor):
 
 class BF16EFCompressor(_ErrorFeedback, BF16Compressor):
     """float32 tensors travel as bf16 with error feedback."""
+
+
+def _sr_keys(keys) -> list:
+    """Keys (mod 2^32) as a stochastic-rounding plan's segments carry them."""
+    return [SrKey(int(k) & 0xffffffff) for k in keys]
 
 
 class _StochasticRounding:
@@ -620,6 +669,27 @@ class _StochasticRounding:
     @classmethod
     def compresses(cls, tensor) -> bool:
         return _is_f32(tensor)
+
+    @classmethod
+    def cast_extra(cls, tensor, key):
+        return SrKey(key())
+
+    @classmethod
+    def _check_segment(cls, half, wide, key) -> None:
+        if key is None:
+            return super()._check_segment(half, wide, None)
+        from .torch_ops import _check_cast_sr
+        _check_cast_sr(half, wide, cls.wire_torch_dtype())
+
+    @classmethod
+    def compress_with(cls, out, tensor, key=None, step=None):
+        return cls.compress_into(out, tensor) if key is None else \
+            cls.compress_sr_into(out, tensor, key, step)
+
+    @classmethod
+    def compress_many_with(cls, outs, tensors, keys, step=None,
+                           plans: CastPlanCache | None = None):
+        return cls.compress_many_sr_into(outs, tensors, keys, step, plans)
 
     @classmethod
     def compress_sr_into(cls, out, tensor, key: int, step: int):
@@ -661,7 +731,7 @@ class _StochasticRounding:
         for t in tensors:
             if not cls.compresses(t):
                 raise ValueError("stochastic rounding needs float32 tensors")
-        _cast_many(cls, list(zip(tensors, outs)), True, 1, plans, keys=list(keys), step=step)
+        _cast_many(cls, list(zip(tensors, outs)), True, 1, plans, extras=_sr_keys(keys), step=step)
         return outs
 
     @classmethod
@@ -671,11 +741,8 @@ class _StochasticRounding:
         ``compress_many_sr_into`` over the same tensors) only names the plan:
         the stochastic-rounding plan's own decompress is the plain one, so one
         cached plan serves both directions."""
-        if len(outs) != len(compressed):
-            raise ValueError("decompress_many_into: as many outputs as compressed tensors")
-        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans,
-                   keys=None if keys is None else list(keys), stats=stats)
-        return outs
+        return cls.decompress_many_with(outs, compressed, None if keys is None else _sr_keys(keys),
+                                        divisor, plans, stats)
 
 
 class FP16SRCompressor(_StochasticRounding, FP16Compressor):

@@ -437,351 +437,274 @@ int byteps_reduce_copy(void* dst, const void* src, size_t len, void* stream) {
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "copy kernel launch");
 }
 
-// Which wide dtypes travel in which 2-byte wire format: fp16 carries f32, f64
-// and bf16, bf16 carries f32, f64 and fp16.  Anything else, wide == wire
-// included, is the dtype error.
-static int cast_pair_check(int dtype, int wire) {
-  if (wire != kFloat16 && wire != kBFloat16)
-    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire);
-  const int other = wire == kFloat16 ? kBFloat16 : kFloat16;
-  if (dtype != kFloat32 && dtype != kFloat64 && dtype != other)
-    return fail(BYTEPS_REDUCE_EDTYPE, "%s compression of data type %d",
-                wire == kFloat16 ? "fp16" : "bf16", dtype);
-  return BYTEPS_REDUCE_OK;
+}  // extern "C"
+
+// ------------------------------------------------------------------ casts --
+// The launch wrappers of one wire format (bpsr_internal.h): the single casts,
+// and the plan's per direction and scheme.
+struct CastWire {
+  int wire;
+  decltype(launch_compress_fp16)* compress;
+  decltype(launch_decompress_fp16)* decompress;
+  decltype(launch_compress_ef)* compress_ef;
+  decltype(launch_compress_sr)* compress_sr;
+  decltype(launch_cast_plan)* plan;
+  decltype(launch_cast_plan_ef)* plan_ef;
+  decltype(launch_cast_plan_sr)* plan_sr;
+  decltype(launch_cast_plan_stats)* plan_stats;
+};
+static const CastWire kCastWires[] = {
+    {kFloat16, launch_compress_fp16, launch_decompress_fp16, launch_compress_ef,
+     launch_compress_sr, launch_cast_plan, launch_cast_plan_ef, launch_cast_plan_sr,
+     launch_cast_plan_stats},
+    {kBFloat16, launch_compress_bf16, launch_decompress_bf16, launch_compress_ef_bf16,
+     launch_compress_sr_bf16, launch_cast_plan_bf16, launch_cast_plan_ef_bf16,
+     launch_cast_plan_sr_bf16, launch_cast_plan_stats_bf16},
+};
+
+// The row of a wire format; null, with the dtype error set, for any other.
+static const CastWire* cast_wire(int wire) {
+  for (const CastWire& w : kCastWires)
+    if (w.wire == wire) return &w;
+  fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire);
+  return nullptr;
 }
 
-// Shared checks of the casts, all before any HIP call: h = the 2-byte operand
-// (of `wire`), w = the wide one.  Returns 1 when there is nothing to do.
-static int cast_check(const void* h, const void* w, size_t nelem, int dtype, int divisor,
-                      int wire = kFloat16) {
-  const int pair = cast_pair_check(dtype, wire);
-  if (pair != BYTEPS_REDUCE_OK) return pair;
-  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
-  if (nelem == 0) return 1;
-  if (!h || !w) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
-  const size_t es = (size_t)elem_size(dtype);
-  if (nelem > SIZE_MAX / es) return fail(BYTEPS_REDUCE_EARGS, "element count overflows");
-  const uintptr_t x = (uintptr_t)h, y = (uintptr_t)w;
-  const size_t hb = nelem * 2, wb = nelem * es;
-  if (x > UINTPTR_MAX - hb || y > UINTPTR_MAX - wb)
-    return fail(BYTEPS_REDUCE_EARGS, "operand wraps the address space");
-  if (x < y + wb && y < x + hb) return fail(BYTEPS_REDUCE_EARGS, "dst and src overlap");
-  return BYTEPS_REDUCE_OK;
-}
-
-int byteps_reduce_compress_fp16(void* dst, const void* src, size_t nelem, int src_dtype,
-                                void* stream) {
-  const int rc = cast_check(dst, src, nelem, src_dtype, 1);
+// A single cast: every check before any HIP call (cast_check), then `launch`
+// with the wire's row; `what` names the launch in a HIP error.
+template <class Launch>
+static int cast_single(int wire, int wide_dtype, CastScheme scheme, int divisor, size_t nelem,
+                       std::initializer_list<CastOperand> ops, const char* what, Launch launch) {
+  const int rc =
+      cast_check(wire, wide_dtype, scheme, divisor, nelem, ops.begin(), (int)ops.size());
   if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
-  hipError_t e = launch_compress_fp16(dst, src, nelem, src_dtype, tuning(), to_stream(stream));
-  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "compress kernel launch");
-}
-
-int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
-                                  int divisor, void* stream) {
-  const int rc = cast_check(src, dst, nelem, dst_dtype, divisor);
-  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
-  hipError_t e = launch_decompress_fp16(dst, src, nelem, dst_dtype, divisor, tuning(),
-                                        to_stream(stream));
-  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "decompress kernel launch");
-}
-
-int byteps_reduce_compress_to(void* dst, const void* src, size_t nelem, int src_dtype,
-                              int wire_dtype, void* stream) {
-  if (wire_dtype == kFloat16)
-    return byteps_reduce_compress_fp16(dst, src, nelem, src_dtype, stream);
-  const int rc = cast_check(dst, src, nelem, src_dtype, 1, wire_dtype);
-  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
-  hipError_t e = launch_compress_bf16(dst, src, nelem, src_dtype, tuning(), to_stream(stream));
-  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "compress kernel launch");
-}
-
-int byteps_reduce_decompress_from(void* dst, const void* src, size_t nelem, int dst_dtype,
-                                  int wire_dtype, int divisor, void* stream) {
-  if (wire_dtype == kFloat16)
-    return byteps_reduce_decompress_fp16(dst, src, nelem, dst_dtype, divisor, stream);
-  const int rc = cast_check(src, dst, nelem, dst_dtype, divisor, wire_dtype);
-  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
-  hipError_t e = launch_decompress_bf16(dst, src, nelem, dst_dtype, divisor, tuning(),
-                                        to_stream(stream));
-  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "decompress kernel launch");
-}
-
-// The three byte ranges of an error-feedback compress are pairwise disjoint:
-// dst and resid are written, src is read.  All checks before any HIP call;
-// returns 1 when there is nothing to do.
-static int cast_ef_check(const void* dst, const void* resid, const void* src, size_t nelem,
-                         int src_dtype, int wire) {
-  if (wire != kFloat16 && wire != kBFloat16)
-    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire);
-  if (src_dtype != kFloat32)
-    return fail(BYTEPS_REDUCE_EDTYPE, "error-feedback compression of data type %d (FLOAT32 only)",
-                src_dtype);
-  if (nelem == 0) return 1;
-  if (!dst || !resid || !src) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
-  if (nelem > SIZE_MAX / 4) return fail(BYTEPS_REDUCE_EARGS, "element count overflows");
-  const uintptr_t b[3] = {(uintptr_t)dst, (uintptr_t)resid, (uintptr_t)src};
-  const size_t n[3] = {nelem * 2, nelem * 4, nelem * 4};
-  for (int i = 0; i < 3; ++i)
-    if (b[i] > UINTPTR_MAX - n[i])
-      return fail(BYTEPS_REDUCE_EARGS, "operand wraps the address space");
-  static const char* const name[3] = {"dst", "resid", "src"};
-  for (int i = 0; i < 3; ++i)
-    for (int j = i + 1; j < 3; ++j)
-      if (b[i] < b[j] + n[j] && b[j] < b[i] + n[i])
-        return fail(BYTEPS_REDUCE_EARGS, "%s and %s overlap", name[i], name[j]);
-  return BYTEPS_REDUCE_OK;
-}
-
-int byteps_reduce_compress_ef(void* dst, void* resid, const void* src, size_t nelem,
-                              int src_dtype, int wire_dtype, void* stream) {
-  const int rc = cast_ef_check(dst, resid, src, nelem, src_dtype, wire_dtype);
-  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
-  const auto launch = wire_dtype == kBFloat16 ? launch_compress_ef_bf16 : launch_compress_ef;
-  hipError_t e = launch(dst, resid, src, nelem, tuning(), to_stream(stream));
-  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "error-feedback compress kernel launch");
-}
-
-// dst (2 * nelem bytes, written) and src (4 * nelem, read) are disjoint.  All
-// checks before any HIP call; returns 1 when there is nothing to do.
-static int cast_sr_check(const void* dst, const void* src, size_t nelem, int src_dtype,
-                         int wire) {
-  if (wire != kFloat16 && wire != kBFloat16)
-    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire);
-  if (src_dtype != kFloat32)
-    return fail(BYTEPS_REDUCE_EDTYPE,
-                "stochastic-rounding compression of data type %d (FLOAT32 only)", src_dtype);
-  if (nelem == 0) return 1;
-  if (!dst || !src) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
-  if (nelem > kSrMaxElems) return fail(BYTEPS_REDUCE_EARGS, "more than 2^34 elements");
-  const uintptr_t x = (uintptr_t)dst, y = (uintptr_t)src;
-  const size_t hb = nelem * 2, wb = nelem * 4;
-  if (x > UINTPTR_MAX - hb || y > UINTPTR_MAX - wb)
-    return fail(BYTEPS_REDUCE_EARGS, "operand wraps the address space");
-  if (x < y + wb && y < x + hb) return fail(BYTEPS_REDUCE_EARGS, "dst and src overlap");
-  return BYTEPS_REDUCE_OK;
-}
-
-int byteps_reduce_compress_sr(void* dst, const void* src, size_t nelem, int src_dtype,
-                              int wire_dtype, uint32_t key, uint32_t step, void* stream) {
-  const int rc = cast_sr_check(dst, src, nelem, src_dtype, wire_dtype);
-  if (rc != BYTEPS_REDUCE_OK) return rc > 0 ? BYTEPS_REDUCE_OK : rc;
-  const auto launch = wire_dtype == kBFloat16 ? launch_compress_sr_bf16 : launch_compress_sr;
-  hipError_t e = launch(dst, src, nelem, key, step, tuning(), to_stream(stream));
-  return e == hipSuccess ? BYTEPS_REDUCE_OK
-                         : hip_fail(e, "stochastic-rounding compress kernel launch");
+  const hipError_t e = launch(*cast_wire(wire));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, what);
 }
 
 struct byteps_reduce_cast_plan {
   int device;
   int dtype;
-  int wire;
-  void* dev_table;
-  void* dev_resid;  // error-feedback plans: one residual pointer per record
-  void* dev_sr;     // stochastic-rounding plans: one CastSrRec per record
-  bool sr;          // made by _create_sr (also when it has no records)
+  const CastWire* wire;
+  CastScheme scheme;  // also for a plan without records
   CastTableInfo ti;
-  // decompress statistics (_decompress_stats): the segments' record lists,
-  // seg_begin[nsegs + 1] then seg_recs[records], uploaded with the table; the
-  // (record, wave) partials, made by the first statistics call; and the
-  // segments' byte ranges, which the statistics' output must stay clear of
   int nsegs;
-  void* dev_seg;
-  void* dev_part;
+  // What the plan owns on the device: the table; for the decompress statistics
+  // (_decompress_stats) the segments' record lists, seg_begin[nsegs + 1] then
+  // seg_recs[records], uploaded with the table, and the (record, wave)
+  // partials, made by the first statistics call; and the scheme's array of one
+  // entry per record — a residual pointer (error feedback) or a CastSrRec
+  // (stochastic rounding).
+  enum { kTable, kSeg, kPart, kSide, kDevArrays };
+  void* dev[kDevArrays] = {};
+  // the segments' byte ranges, which the statistics' output must stay clear of
   std::vector<std::pair<uintptr_t, uintptr_t>> ranges;
 };
 
-typedef std::vector<std::pair<uintptr_t, uintptr_t>> CastRanges;
-// One operand's byte range (the table builder has validated it); nothing for
-// an empty segment.
-static void cast_plan_range(CastRanges& out, const void* p, size_t bytes) {
-  if (bytes) out.emplace_back((uintptr_t)p, (uintptr_t)p + bytes);
+// Frees what the plan owns and the plan; the first error wins.
+static hipError_t cast_plan_free(byteps_reduce_cast_plan* p) {
+  hipError_t e = hipSuccess;
+  for (void* q : p->dev)
+    if (q) {
+      const hipError_t e2 = hipFree(q);
+      if (e == hipSuccess) e = e2;
+    }
+  delete p;
+  return e;
 }
 
-// table_dtype: what the table builder is given.  It cuts by element size alone
-// and knows the fp16 wire's three wide types, so a wide fp16 (bf16 wire) is
-// cut as its 2-byte peer.
-// Upload a built table (and, for an error-feedback plan, its residual
-// pointers: `resid` non-null; for a stochastic-rounding plan its parallel
-// array: `sr` non-null) into a new plan.
-// `lists`: every segment's records (nsegs = seg_begin.size() - 1), uploaded
-// whenever the plan has a segment, records or not.
-static int cast_plan_upload(const std::vector<char>& host,
-                            const std::vector<unsigned char*>* resid, const CastTableInfo& ti,
-                            int wide_dtype, int wire, byteps_reduce_cast_plan** out,
-                            const CastSegList& lists,
-                            CastRanges&& ranges,
-                            const std::vector<CastSrRec>* sr = nullptr) {
+// A host array as a new device array.
+template <class T>
+static hipError_t cast_plan_upload(void** dev, const std::vector<T>& host) {
+  const size_t bytes = host.size() * sizeof(T);
+  const hipError_t e = hipMalloc(dev, bytes);
+  return e == hipSuccess ? hipMemcpy(*dev, host.data(), bytes, hipMemcpyHostToDevice) : e;
+}
+
+// The three table builders under one name: `side` is the scheme's array of one
+// entry per record (none for a plain plan).
+static int cast_plan_table(const byteps_cast_desc* segs, int nsegs, int dtype, int copy_vpt,
+                           std::vector<char>& out, std::vector<char>& /*side*/, CastTableInfo* ti,
+                           CastSegList* lists) {
+  return build_cast_table(segs, nsegs, dtype, copy_vpt, out, ti, lists);
+}
+static int cast_plan_table(const byteps_cast_ef_desc* segs, int nsegs, int dtype, int copy_vpt,
+                           std::vector<char>& out, std::vector<unsigned char*>& side,
+                           CastTableInfo* ti, CastSegList* lists) {
+  return build_cast_table_ef(segs, nsegs, dtype, copy_vpt, out, side, ti, lists);
+}
+static int cast_plan_table(const byteps_cast_sr_desc* segs, int nsegs, int dtype, int copy_vpt,
+                           std::vector<char>& out, std::vector<CastSrRec>& side, CastTableInfo* ti,
+                           CastSegList* lists) {
+  return build_cast_table_sr(segs, nsegs, dtype, copy_vpt, out, side, ti, lists);
+}
+
+// A new plan of `scheme`: build the table (and the scheme's array, of `Side`
+// entries), take the byte ranges the builder tested, and upload — the record
+// lists whenever the plan has a segment, records or not.
+template <class Side, class D>
+static int cast_plan_create(CastScheme scheme, const D* segs, int nsegs, int wide_dtype, int wire,
+                            byteps_reduce_cast_plan** out) {
+  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
+  *out = nullptr;
+  const int pair = cast_dtype_check(wire, wide_dtype, scheme);
+  if (pair != BYTEPS_REDUCE_OK) return pair;
+  // The table builder cuts by element size alone and knows the fp16 wire's
+  // three wide types, so a wide fp16 (bf16 wire) is cut as its 2-byte peer.
+  const int table_dtype = wide_dtype == kFloat16 ? kBFloat16 : wide_dtype;
+  std::vector<char> host;
+  std::vector<Side> side;
+  CastTableInfo ti;
+  CastSegList lists;
+  const int rc =
+      cast_plan_table(segs, nsegs, table_dtype, tuning().copy_vpt, host, side, &ti, &lists);
+  if (rc) return rc;
   auto* p = new byteps_reduce_cast_plan();
   p->dtype = wide_dtype;
-  p->wire = wire;
+  p->wire = cast_wire(wire);
+  p->scheme = scheme;
   p->ti = ti;
-  p->dev_table = nullptr;
-  p->dev_resid = nullptr;
-  p->dev_sr = nullptr;
-  p->sr = sr != nullptr;
-  p->nsegs = (int)lists.seg_begin.size() - 1;
-  p->dev_seg = nullptr;
-  p->dev_part = nullptr;
-  p->ranges = std::move(ranges);
+  p->nsegs = nsegs;
+  p->ranges = std::move(lists.ranges);
   hipError_t e = hipGetDevice(&p->device);
-  if (e == hipSuccess && p->nsegs > 0) {
-    const size_t nb = lists.seg_begin.size() * sizeof(uint32_t);
-    const size_t nr = lists.seg_recs.size() * sizeof(uint32_t);
-    e = hipMalloc(&p->dev_seg, nb + nr);
-    if (e == hipSuccess)
-      e = hipMemcpy(p->dev_seg, lists.seg_begin.data(), nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nr)
-      e = hipMemcpy(static_cast<char*>(p->dev_seg) + nb, lists.seg_recs.data(), nr,
-                    hipMemcpyHostToDevice);
+  if (e == hipSuccess && nsegs > 0) {
+    std::vector<uint32_t>& seg = lists.seg_begin;
+    seg.insert(seg.end(), lists.seg_recs.begin(), lists.seg_recs.end());
+    e = cast_plan_upload(&p->dev[p->kSeg], seg);
   }
   if (e == hipSuccess && ti.records > 0) {
-    e = hipMalloc(&p->dev_table, ti.bytes);
-    if (e == hipSuccess)
-      e = hipMemcpy(p->dev_table, host.data(), ti.bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && resid) {
-      const size_t rb = resid->size() * sizeof(unsigned char*);
-      e = hipMalloc(&p->dev_resid, rb);
-      if (e == hipSuccess) e = hipMemcpy(p->dev_resid, resid->data(), rb, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && sr) {
-      const size_t sb = sr->size() * sizeof(CastSrRec);
-      e = hipMalloc(&p->dev_sr, sb);
-      if (e == hipSuccess) e = hipMemcpy(p->dev_sr, sr->data(), sb, hipMemcpyHostToDevice);
-    }
+    e = cast_plan_upload(&p->dev[p->kTable], host);
+    if (e == hipSuccess && scheme != kCastPlain) e = cast_plan_upload(&p->dev[p->kSide], side);
   }
   if (e != hipSuccess) {
-    if (p->dev_table) (void)hipFree(p->dev_table);
-    if (p->dev_resid) (void)hipFree(p->dev_resid);
-    if (p->dev_sr) (void)hipFree(p->dev_sr);
-    if (p->dev_seg) (void)hipFree(p->dev_seg);
-    delete p;
+    (void)cast_plan_free(p);
     return hip_fail(e, "cast plan table upload");
   }
   *out = p;
   return BYTEPS_REDUCE_OK;
 }
 
-static int cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int wire,
-                            int table_dtype, byteps_reduce_cast_plan** out) {
-  std::vector<char> host;
-  CastTableInfo ti;
-  CastSegList lists;
-  const int rc =
-      build_cast_table(segs, nsegs, table_dtype, tuning().copy_vpt, host, &ti, &lists);
-  if (rc) return rc;
-  CastRanges ranges;
-  for (int i = 0; i < nsegs; ++i) {
-    cast_plan_range(ranges, segs[i].wide, segs[i].nelem * (size_t)elem_size(table_dtype));
-    cast_plan_range(ranges, segs[i].half, segs[i].nelem * 2);
-  }
-  return cast_plan_upload(host, nullptr, ti, wide_dtype, wire, out, lists, std::move(ranges));
+// The plan's one launch, by direction and scheme (validated by the callers;
+// the plan has records): a compress is its scheme's — `step` for stochastic
+// rounding — a decompress the plain one for every scheme, with the statistics'
+// partials where `part` is not null.
+static int cast_plan_launch(byteps_reduce_cast_plan* p, bool compress, int divisor, uint32_t step,
+                            void* part, void* stream) {
+  const CastRec* table = static_cast<const CastRec*>(p->dev[p->kTable]);
+  void* side = p->dev[p->kSide];
+  const uint32_t n = p->ti.records;
+  const int u = p->ti.u;
+  const uint64_t wide_bytes = p->ti.nelem * (uint64_t)elem_size(p->dtype);
+  const Tuning tu = tuning();
+  hipStream_t s = to_stream(stream);
+  hipError_t e;
+  if (!compress)
+    e = part ? p->wire->plan_stats(table, n, p->dtype, divisor, u, wide_bytes, part, tu, s)
+             : p->wire->plan(false, table, n, p->dtype, divisor, u, wide_bytes, tu, s);
+  else if (p->scheme == kCastEf)  // 2 + 4 bytes written an element
+    e = p->wire->plan_ef(table, static_cast<unsigned char* const*>(side), n, u, p->ti.nelem * 6,
+                         tu, s);
+  else if (p->scheme == kCastSr)
+    e = p->wire->plan_sr(table, static_cast<const CastSrRec*>(side), n, step, u, p->ti.nelem * 2,
+                         tu, s);
+  else
+    e = p->wire->plan(true, table, n, p->dtype, 1, u, p->ti.nelem * 2, tu, s);
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan kernel launch");
 }
 
-int byteps_reduce_cast_plan_create_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype,
-                                      int wire_dtype, byteps_reduce_cast_plan** out) {
-  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
-  *out = nullptr;
-  if (wire_dtype != kFloat16 && wire_dtype != kBFloat16)
-    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire_dtype);
-  std::vector<char> host;
-  std::vector<unsigned char*> resid;
-  CastTableInfo ti;
-  CastSegList lists;
-  const int rc =
-      build_cast_table_ef(segs, nsegs, wide_dtype, tuning().copy_vpt, host, resid, &ti, &lists);
-  if (rc) return rc;
-  CastRanges ranges;
-  for (int i = 0; i < nsegs; ++i) {
-    cast_plan_range(ranges, segs[i].wide, segs[i].nelem * 4);
-    cast_plan_range(ranges, segs[i].half, segs[i].nelem * 2);
-    cast_plan_range(ranges, segs[i].resid, segs[i].nelem * 4);
-  }
-  return cast_plan_upload(host, &resid, ti, wide_dtype, wire_dtype, out, lists,
-                          std::move(ranges));
+extern "C" {
+
+int byteps_reduce_compress_to(void* dst, const void* src, size_t nelem, int src_dtype,
+                              int wire_dtype, void* stream) {
+  return cast_single(wire_dtype, src_dtype, kCastPlain, 1, nelem,
+                     {{"dst", dst, 2}, {"src", src, (size_t)elem_size(src_dtype)}},
+                     "compress kernel launch", [&](const CastWire& w) {
+                       return w.compress(dst, src, nelem, src_dtype, tuning(), to_stream(stream));
+                     });
 }
 
-int byteps_reduce_cast_plan_create_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype,
-                                      int wire_dtype, byteps_reduce_cast_plan** out) {
-  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
-  *out = nullptr;
-  if (wire_dtype != kFloat16 && wire_dtype != kBFloat16)
-    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire_dtype);
-  std::vector<char> host;
-  std::vector<CastSrRec> sr;
-  CastTableInfo ti;
-  CastSegList lists;
-  const int rc =
-      build_cast_table_sr(segs, nsegs, wide_dtype, tuning().copy_vpt, host, sr, &ti, &lists);
-  if (rc) return rc;
-  CastRanges ranges;
-  for (int i = 0; i < nsegs; ++i) {
-    cast_plan_range(ranges, segs[i].wide, segs[i].nelem * 4);
-    cast_plan_range(ranges, segs[i].half, segs[i].nelem * 2);
-  }
-  return cast_plan_upload(host, nullptr, ti, wide_dtype, wire_dtype, out, lists,
-                          std::move(ranges), &sr);
+int byteps_reduce_decompress_from(void* dst, const void* src, size_t nelem, int dst_dtype,
+                                  int wire_dtype, int divisor, void* stream) {
+  return cast_single(wire_dtype, dst_dtype, kCastPlain, divisor, nelem,
+                     {{"dst", dst, (size_t)elem_size(dst_dtype)}, {"src", src, 2}},
+                     "decompress kernel launch", [&](const CastWire& w) {
+                       return w.decompress(dst, src, nelem, dst_dtype, divisor, tuning(),
+                                           to_stream(stream));
+                     });
 }
 
-int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
-                                   byteps_reduce_cast_plan** out) {
-  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
-  *out = nullptr;
-  return cast_plan_create(segs, nsegs, wide_dtype, kFloat16, wide_dtype, out);
+int byteps_reduce_compress_fp16(void* dst, const void* src, size_t nelem, int src_dtype,
+                                void* stream) {
+  return byteps_reduce_compress_to(dst, src, nelem, src_dtype, kFloat16, stream);
+}
+
+int byteps_reduce_decompress_fp16(void* dst, const void* src, size_t nelem, int dst_dtype,
+                                  int divisor, void* stream) {
+  return byteps_reduce_decompress_from(dst, src, nelem, dst_dtype, kFloat16, divisor, stream);
+}
+
+// dst and resid are written, src is read: three pairwise disjoint ranges.
+int byteps_reduce_compress_ef(void* dst, void* resid, const void* src, size_t nelem,
+                              int src_dtype, int wire_dtype, void* stream) {
+  return cast_single(wire_dtype, src_dtype, kCastEf, 1, nelem,
+                     {{"dst", dst, 2}, {"resid", resid, 4}, {"src", src, 4}},
+                     "error-feedback compress kernel launch", [&](const CastWire& w) {
+                       return w.compress_ef(dst, resid, src, nelem, tuning(), to_stream(stream));
+                     });
+}
+
+int byteps_reduce_compress_sr(void* dst, const void* src, size_t nelem, int src_dtype,
+                              int wire_dtype, uint32_t key, uint32_t step, void* stream) {
+  return cast_single(wire_dtype, src_dtype, kCastSr, 1, nelem, {{"dst", dst, 2}, {"src", src, 4}},
+                     "stochastic-rounding compress kernel launch", [&](const CastWire& w) {
+                       return w.compress_sr(dst, src, nelem, key, step, tuning(),
+                                            to_stream(stream));
+                     });
 }
 
 int byteps_reduce_cast_plan_create_wire(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
                                         int wire_dtype, byteps_reduce_cast_plan** out) {
-  if (wire_dtype == kFloat16) return byteps_reduce_cast_plan_create(segs, nsegs, wide_dtype, out);
-  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
-  *out = nullptr;
-  const int pair = cast_pair_check(wide_dtype, wire_dtype);
-  if (pair != BYTEPS_REDUCE_OK) return pair;
-  return cast_plan_create(segs, nsegs, wide_dtype, wire_dtype,
-                          wide_dtype == kFloat16 ? kBFloat16 : wide_dtype, out);
+  return cast_plan_create<char>(kCastPlain, segs, nsegs, wide_dtype, wire_dtype, out);
 }
 
-static int cast_plan_launch(byteps_reduce_cast_plan* p, bool compress, int divisor,
-                            void* stream) {
+int byteps_reduce_cast_plan_create(const byteps_cast_desc* segs, int nsegs, int wide_dtype,
+                                   byteps_reduce_cast_plan** out) {
+  return byteps_reduce_cast_plan_create_wire(segs, nsegs, wide_dtype, kFloat16, out);
+}
+
+int byteps_reduce_cast_plan_create_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype,
+                                      int wire_dtype, byteps_reduce_cast_plan** out) {
+  return cast_plan_create<unsigned char*>(kCastEf, segs, nsegs, wide_dtype, wire_dtype, out);
+}
+
+int byteps_reduce_cast_plan_create_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype,
+                                      int wire_dtype, byteps_reduce_cast_plan** out) {
+  return cast_plan_create<CastSrRec>(kCastSr, segs, nsegs, wide_dtype, wire_dtype, out);
+}
+
+int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* p, void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
-  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
-  if (compress && p->sr)
+  if (p->scheme == kCastSr)
     return fail(BYTEPS_REDUCE_EARGS,
                 "a stochastic-rounding plan is compressed with a step "
                 "(byteps_reduce_cast_plan_compress_sr)");
   if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
-  if (compress && p->dev_resid) {  // error-feedback plan: 2 + 4 bytes written an element
-    const auto ef = p->wire == kBFloat16 ? launch_cast_plan_ef_bf16 : launch_cast_plan_ef;
-    hipError_t e = ef(static_cast<const CastRec*>(p->dev_table),
-                      static_cast<unsigned char* const*>(p->dev_resid), p->ti.records, p->ti.u,
-                      p->ti.nelem * 6, tuning(), to_stream(stream));
-    return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan kernel launch");
-  }
-  const uint64_t out_bytes = p->ti.nelem * (compress ? 2 : (uint64_t)elem_size(p->dtype));
-  const auto launch = p->wire == kBFloat16 ? launch_cast_plan_bf16 : launch_cast_plan;
-  hipError_t e = launch(compress, static_cast<const CastRec*>(p->dev_table), p->ti.records,
-                        p->dtype, divisor, p->ti.u, out_bytes, tuning(), to_stream(stream));
-  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan kernel launch");
-}
-
-int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* p, void* stream) {
-  return cast_plan_launch(p, true, 1, stream);
+  return cast_plan_launch(p, true, 1, 0, nullptr, stream);
 }
 
 int byteps_reduce_cast_plan_compress_sr(byteps_reduce_cast_plan* p, uint32_t step, void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
-  if (!p->sr)
+  if (p->scheme != kCastSr)
     return fail(BYTEPS_REDUCE_EARGS, "the plan carries no keys (byteps_reduce_cast_plan_create_sr)");
   if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
-  const auto launch = p->wire == kBFloat16 ? launch_cast_plan_sr_bf16 : launch_cast_plan_sr;
-  hipError_t e = launch(static_cast<const CastRec*>(p->dev_table),
-                        static_cast<const CastSrRec*>(p->dev_sr), p->ti.records, step, p->ti.u,
-                        p->ti.nelem * 2, tuning(), to_stream(stream));
-  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan kernel launch");
+  return cast_plan_launch(p, true, 1, step, nullptr, stream);
 }
 
 int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* p, int divisor, void* stream) {
-  return cast_plan_launch(p, false, divisor, stream);
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
+  return cast_plan_launch(p, false, divisor, 0, nullptr, stream);
 }
 
 int byteps_reduce_cast_plan_decompress_stats(byteps_reduce_cast_plan* p, int divisor,
@@ -798,41 +721,24 @@ int byteps_reduce_cast_plan_decompress_stats(byteps_reduce_cast_plan* p, int div
   for (const auto& r : p->ranges)
     if (sb < r.second && r.first < sb + bytes)
       return fail(BYTEPS_REDUCE_EARGS, "stats overlaps a segment of the plan");
-  hipStream_t s = to_stream(stream);
-  const uint32_t* seg = static_cast<const uint32_t*>(p->dev_seg);
+  void*& part = p->dev[p->kPart];
   if (p->ti.records > 0) {
-    if (!p->dev_part) {  // the first statistics call of a plan allocates
-      hipError_t e = hipMalloc(&p->dev_part, (size_t)p->ti.records * kStatPartBytes);
+    if (!part) {  // the first statistics call of a plan allocates
+      hipError_t e = hipMalloc(&part, (size_t)p->ti.records * kStatPartBytes);
       if (e != hipSuccess) return hip_fail(e, "cast plan statistics partials");
     }
-    const auto launch = p->wire == kBFloat16 ? launch_cast_plan_stats_bf16 : launch_cast_plan_stats;
-    hipError_t e = launch(static_cast<const CastRec*>(p->dev_table), p->ti.records, p->dtype,
-                          divisor, p->ti.u, p->ti.nelem * (uint64_t)elem_size(p->dtype),
-                          p->dev_part, tuning(), s);
-    if (e != hipSuccess) return hip_fail(e, "cast plan kernel launch");
+    const int rc = cast_plan_launch(p, false, divisor, 0, part, stream);
+    if (rc) return rc;
   }
-  hipError_t e = launch_cast_stats_finish(seg, seg + p->nsegs + 1, p->dev_part, stats, p->nsegs, s);
+  const uint32_t* seg = static_cast<const uint32_t*>(p->dev[p->kSeg]);
+  hipError_t e = launch_cast_stats_finish(seg, seg + p->nsegs + 1, part, stats, p->nsegs,
+                                          to_stream(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan statistics kernel launch");
 }
 
 int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* p) {
   if (!p) return BYTEPS_REDUCE_OK;
-  hipError_t e = hipSuccess;
-  if (p->dev_table) e = hipFree(p->dev_table);
-  for (void* q : {p->dev_seg, p->dev_part})
-    if (q) {
-      const hipError_t e2 = hipFree(q);
-      if (e == hipSuccess) e = e2;
-    }
-  if (p->dev_resid) {
-    const hipError_t e2 = hipFree(p->dev_resid);
-    if (e == hipSuccess) e = e2;
-  }
-  if (p->dev_sr) {
-    const hipError_t e2 = hipFree(p->dev_sr);
-    if (e == hipSuccess) e = e2;
-  }
-  delete p;
+  const hipError_t e = cast_plan_free(p);
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan free");
 }
 

@@ -91,54 +91,71 @@ struct CastTableInfo {
   size_t bytes = 0;      // bytes to upload
 };
 
-// Validate the segments (null pointers, pairwise disjoint byte ranges, grid
-// size) and write [CastRec x records] into `out` (bpsr_internal.h: CastRec);
-// on an error `out` is left as it was.  Every segment is cut as a single cast
-// is (cast_cut); the tile size is the single cast's rule applied to the whole
-// launch: `copy_vpt` (Tuning::copy_vpt), halved while the launch would have
-// fewer than kMinTiles vector tiles.  No HIP call.
-int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
-                     std::vector<char>& out, CastTableInfo* ti);
-// The same for an error-feedback plan (wide_dtype FLOAT32, else EDTYPE): the
-// cut also asks the residual to co-align (cast_cut_ef), all 3 * nsegs byte
-// ranges must be pairwise disjoint, a null residual with nelem > 0 is EARGS,
-// and `resid_out` receives one pointer per record: the segment's residual
-// plus (the record's wide pointer - the segment's wide pointer).  On an error
-// both outputs are left as they were.  No HIP call.
-int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
-                        std::vector<char>& out, std::vector<unsigned char*>& resid_out,
-                        CastTableInfo* ti);
-// The same for a stochastic-rounding plan (wide_dtype FLOAT32, else EDTYPE):
-// the cut is the plain one (cast_cut), the 2 * nsegs byte ranges must be
-// pairwise disjoint, a segment of more than 2^34 elements is EARGS, the
-// records are byte for byte build_cast_table's, and `sr_out` receives one
-// entry per record: the index in its segment of the record's first element
-// and the segment's key.  On an error both outputs are left as they were.
-// No HIP call.
-int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
-                        std::vector<char>& out, std::vector<CastSrRec>& sr_out,
-                        CastTableInfo* ti);
+// The rounding scheme of a cast: what a single compress, a plan and its table
+// are made for.
+enum CastScheme { kCastPlain = 0, kCastEf = 1, kCastSr = 2 };
+
+// Which wide dtypes travel in which 2-byte wire format, per scheme: fp16
+// carries f32, f64 and bf16, bf16 carries f32, f64 and fp16; error feedback
+// and stochastic rounding take f32 alone.  Anything else, an unknown wire and
+// wide == wire included, is the dtype error.
+int cast_dtype_check(int wire, int wide_dtype, CastScheme scheme);
+
+// One operand of a single cast: `nelem` elements of `es` bytes at `p`; `name`
+// is what an overlap message calls it.
+struct CastOperand {
+  const char* name;
+  const void* p;
+  size_t es;
+};
+// Every check of a single cast, in this order: the dtypes (cast_dtype_check),
+// the divisor (1 for a compress), nelem == 0 (returns 1: nothing to do, null
+// pointers allowed), a null operand, the element count (2^34 at most for
+// stochastic rounding; no byte count may overflow), an operand that wraps the
+// address space, and any two of the `n` operands overlapping.  No HIP call.
+int cast_check(int wire, int wide_dtype, CastScheme scheme, int divisor, size_t nelem,
+               const CastOperand* ops, int n);
 
 // Every segment's records, in CSR form (the decompress statistics'
 // finish kernel adds a segment's partials up from it): segment s of the
 // caller's table owns records seg_recs[seg_begin[s] .. seg_begin[s + 1]),
 // ascending; a segment with nelem == 0 owns none.  seg_begin has nsegs + 1
-// entries, seg_recs one per record.
+// entries, seg_recs one per record.  `ranges`: the byte range of every operand
+// of every non-empty segment, ascending by first byte (the statistics' output
+// must stay clear of them).
 struct CastSegList {
   std::vector<uint32_t> seg_begin;
   std::vector<uint32_t> seg_recs;
+  std::vector<std::pair<uintptr_t, uintptr_t>> ranges;
 };
-// The three builders above, which also fill `lists` (where it is not null);
-// the table and the parallel arrays are byte for byte the same.  On an error
-// `lists` too is left as it was.
+
+// Validate the segments (null pointers, pairwise disjoint byte ranges, grid
+// size) and write [CastRec x records] into `out` (bpsr_internal.h: CastRec);
+// on an error every output is left as it was.  Every segment is cut as a
+// single cast is (cast_cut); the tile size is the single cast's rule applied
+// to the whole launch: `copy_vpt` (Tuning::copy_vpt), halved while the launch
+// would have fewer than kMinTiles vector tiles.  `lists`, where it is not
+// null, is filled too; the table and the parallel arrays are byte for byte
+// the same with and without it.  No HIP call.
 int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
-                     std::vector<char>& out, CastTableInfo* ti, CastSegList* lists);
+                     std::vector<char>& out, CastTableInfo* ti, CastSegList* lists = nullptr);
+// The same for an error-feedback plan (wide_dtype FLOAT32, else EDTYPE): the
+// cut also asks the residual to co-align (cast_cut_ef), all 3 * nsegs byte
+// ranges must be pairwise disjoint, a null residual with nelem > 0 is EARGS,
+// and `resid_out` receives one pointer per record: the segment's residual
+// plus (the record's wide pointer - the segment's wide pointer).
 int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                         std::vector<char>& out, std::vector<unsigned char*>& resid_out,
-                        CastTableInfo* ti, CastSegList* lists);
+                        CastTableInfo* ti, CastSegList* lists = nullptr);
+// The same for a stochastic-rounding plan (wide_dtype FLOAT32, else EDTYPE):
+// the cut is the plain one (cast_cut), the 2 * nsegs byte ranges must be
+// pairwise disjoint, a segment of more than 2^34 elements is EARGS, the
+// records are byte for byte build_cast_table's, and `sr_out` receives one
+// entry per record: the index in its segment of the record's first element
+// and the segment's key.
 int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                         std::vector<char>& out, std::vector<CastSrRec>& sr_out,
-                        CastTableInfo* ti, CastSegList* lists);
+                        CastTableInfo* ti, CastSegList* lists = nullptr);
 
 // ------------------------------------- library queues (bpsr_queues.cpp) --
 // Per device, created on first use, never destroyed: the four library queues

@@ -1,10 +1,12 @@
-// Host arithmetic of the cast plan (byteps_reduce_cast_plan_*): the table of
+// Host arithmetic of the casts: the operand checks of a single cast
+// (cast_check), and of the cast plan (byteps_reduce_cast_plan_*) the table of
 // tile records one plan launch reads, compress or decompress, and for an
 // error-feedback plan the parallel array of one residual pointer per record,
 // for a stochastic-rounding plan that of one (first element index, key) per
 // record; and, for the decompress statistics, every segment's records.  No HIP
-// runtime call (tests/test_cast_table.py, test_cast_table_ef.py,
-// test_cast_table_sr.py and test_cast_table_stats.py build this file with g++).
+// runtime call (tests/test_cast_check.py, test_cast_table.py,
+// test_cast_table_ef.py, test_cast_table_sr.py and test_cast_table_stats.py
+// build this file with g++).
 #include <algorithm>
 #include <cstring>
 
@@ -48,10 +50,11 @@ struct Range {
 // sout: null but for a stochastic-rounding plan; it receives per record the
 // index in its segment of the record's first element and the segment's key,
 // and a segment of more than kSrMaxElems elements is an error.
-// lout: null, or it receives every segment's records (CastSegList).
+// lout: null, or it receives every segment's records and the byte ranges
+// tested here (CastSegList).
 static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
                  std::vector<char>& out, std::vector<unsigned char*>* rout,
-                 std::vector<CastSrRec>* sout, CastTableInfo* ti, CastSegList* lout = nullptr) {
+                 std::vector<CastSrRec>* sout, CastTableInfo* ti, CastSegList* lout) {
   const int nsegs = (int)segs.size();
   const bool ef = rout != nullptr;
   const uint64_t es = (uint64_t)elem_size(wide_dtype);
@@ -167,8 +170,8 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
     l.seg_recs.resize(owner.size());
     std::vector<uint32_t> at(l.seg_begin.begin(), l.seg_begin.end() - 1);
     for (uint32_t r = 0; r < (uint32_t)owner.size(); ++r) l.seg_recs[at[owner[r]]++] = r;
-    lout->seg_begin.swap(l.seg_begin);
-    lout->seg_recs.swap(l.seg_recs);
+    for (const Range& r : ranges) l.ranges.emplace_back(r.begin, r.end);
+    *lout = std::move(l);
   }
   out.swap(tab);
   if (ef) rout->swap(rtab);
@@ -181,57 +184,85 @@ static int build(const std::vector<Desc>& segs, int wide_dtype, int copy_vpt,
   return BYTEPS_REDUCE_OK;
 }
 
-int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
-                     std::vector<char>& out, CastTableInfo* ti) {
-  return build_cast_table(segs, nsegs, wide_dtype, copy_vpt, out, ti, nullptr);
+// The three descriptor kinds as Desc.
+static Desc desc_of(const byteps_cast_desc& d) { return {d.wide, d.half, nullptr, d.nelem, 0}; }
+static Desc desc_of(const byteps_cast_ef_desc& d) { return {d.wide, d.half, d.resid, d.nelem, 0}; }
+static Desc desc_of(const byteps_cast_sr_desc& d) {
+  return {d.wide, d.half, nullptr, d.nelem, d.key};
+}
+
+// What the three builders share ahead of build(): the scheme's dtype rule (a
+// table is cut by element size alone, so the fp16 wire stands for both), the
+// table's count and pointer, and the descriptors as Desc.
+template <class D>
+static int build_from(const D* segs, int nsegs, int wide_dtype, CastScheme scheme, int copy_vpt,
+                      std::vector<char>& out, std::vector<unsigned char*>* rout,
+                      std::vector<CastSrRec>* sout, CastTableInfo* ti, CastSegList* lists) {
+  const int rc = cast_dtype_check(kFloat16, wide_dtype, scheme);
+  if (rc != BYTEPS_REDUCE_OK) return rc;
+  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
+  std::vector<Desc> d((size_t)nsegs);
+  for (int i = 0; i < nsegs; ++i) d[i] = desc_of(segs[i]);
+  return build(d, wide_dtype, copy_vpt, out, rout, sout, ti, lists);
 }
 
 int build_cast_table(const byteps_cast_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                      std::vector<char>& out, CastTableInfo* ti, CastSegList* lists) {
-  if (wide_dtype != kFloat32 && wide_dtype != kFloat64 && wide_dtype != kBFloat16)
-    return fail(BYTEPS_REDUCE_EDTYPE, "fp16 compression of data type %d", wide_dtype);
-  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
-  std::vector<Desc> d((size_t)nsegs);
-  for (int i = 0; i < nsegs; ++i) d[i] = {segs[i].wide, segs[i].half, nullptr, segs[i].nelem, 0};
-  return build(d, wide_dtype, copy_vpt, out, nullptr, nullptr, ti, lists);
-}
-
-int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
-                        std::vector<char>& out, std::vector<unsigned char*>& resid_out,
-                        CastTableInfo* ti) {
-  return build_cast_table_ef(segs, nsegs, wide_dtype, copy_vpt, out, resid_out, ti, nullptr);
+  return build_from(segs, nsegs, wide_dtype, kCastPlain, copy_vpt, out, nullptr, nullptr, ti,
+                    lists);
 }
 
 int build_cast_table_ef(const byteps_cast_ef_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                         std::vector<char>& out, std::vector<unsigned char*>& resid_out,
                         CastTableInfo* ti, CastSegList* lists) {
-  if (wide_dtype != kFloat32)
-    return fail(BYTEPS_REDUCE_EDTYPE, "error-feedback compression of data type %d (FLOAT32 only)",
-                wide_dtype);
-  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
-  std::vector<Desc> d((size_t)nsegs);
-  for (int i = 0; i < nsegs; ++i)
-    d[i] = {segs[i].wide, segs[i].half, segs[i].resid, segs[i].nelem, 0};
-  return build(d, wide_dtype, copy_vpt, out, &resid_out, nullptr, ti, lists);
-}
-
-int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
-                        std::vector<char>& out, std::vector<CastSrRec>& sr_out,
-                        CastTableInfo* ti) {
-  return build_cast_table_sr(segs, nsegs, wide_dtype, copy_vpt, out, sr_out, ti, nullptr);
+  return build_from(segs, nsegs, wide_dtype, kCastEf, copy_vpt, out, &resid_out, nullptr, ti,
+                    lists);
 }
 
 int build_cast_table_sr(const byteps_cast_sr_desc* segs, int nsegs, int wide_dtype, int copy_vpt,
                         std::vector<char>& out, std::vector<CastSrRec>& sr_out,
                         CastTableInfo* ti, CastSegList* lists) {
-  if (wide_dtype != kFloat32)
-    return fail(BYTEPS_REDUCE_EDTYPE,
-                "stochastic-rounding compression of data type %d (FLOAT32 only)", wide_dtype);
-  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
-  std::vector<Desc> d((size_t)nsegs);
-  for (int i = 0; i < nsegs; ++i)
-    d[i] = {segs[i].wide, segs[i].half, nullptr, segs[i].nelem, segs[i].key};
-  return build(d, wide_dtype, copy_vpt, out, nullptr, &sr_out, ti, lists);
+  return build_from(segs, nsegs, wide_dtype, kCastSr, copy_vpt, out, nullptr, &sr_out, ti, lists);
+}
+
+int cast_dtype_check(int wire, int wide_dtype, CastScheme scheme) {
+  if (wire != kFloat16 && wire != kBFloat16)
+    return fail(BYTEPS_REDUCE_EDTYPE, "compression to data type %d", wire);
+  if (scheme != kCastPlain) {
+    if (wide_dtype != kFloat32)
+      return fail(BYTEPS_REDUCE_EDTYPE, "%s compression of data type %d (FLOAT32 only)",
+                  scheme == kCastEf ? "error-feedback" : "stochastic-rounding", wide_dtype);
+    return BYTEPS_REDUCE_OK;
+  }
+  const int other = wire == kFloat16 ? kBFloat16 : kFloat16;
+  if (wide_dtype != kFloat32 && wide_dtype != kFloat64 && wide_dtype != other)
+    return fail(BYTEPS_REDUCE_EDTYPE, "%s compression of data type %d",
+                wire == kFloat16 ? "fp16" : "bf16", wide_dtype);
+  return BYTEPS_REDUCE_OK;
+}
+
+int cast_check(int wire, int wide_dtype, CastScheme scheme, int divisor, size_t nelem,
+               const CastOperand* ops, int n) {
+  const int rc = cast_dtype_check(wire, wide_dtype, scheme);
+  if (rc != BYTEPS_REDUCE_OK) return rc;
+  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  if (nelem == 0) return 1;
+  for (int i = 0; i < n; ++i)
+    if (!ops[i].p) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
+  if (scheme == kCastSr && nelem > kSrMaxElems)
+    return fail(BYTEPS_REDUCE_EARGS, "more than 2^34 elements");
+  for (int i = 0; i < n; ++i)
+    if (nelem > SIZE_MAX / ops[i].es) return fail(BYTEPS_REDUCE_EARGS, "element count overflows");
+  for (int i = 0; i < n; ++i)
+    if ((uintptr_t)ops[i].p > UINTPTR_MAX - nelem * ops[i].es)
+      return fail(BYTEPS_REDUCE_EARGS, "operand wraps the address space");
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j) {
+      const uintptr_t a = (uintptr_t)ops[i].p, b = (uintptr_t)ops[j].p;
+      if (a < b + nelem * ops[j].es && b < a + nelem * ops[i].es)
+        return fail(BYTEPS_REDUCE_EARGS, "%s and %s overlap", ops[i].name, ops[j].name);
+    }
+  return BYTEPS_REDUCE_OK;
 }
 
 }  // namespace bpsr

@@ -73,6 +73,7 @@ from .buckets import (DEFAULT_PARTITION_BYTES, cantor_command, depair_command,
                       local_size_from_env, partition_bound, partition_bytes_from_env)
 from .compression import CastPlanCache, Compression
 from .dtypes import DType, elem_size
+from .reducer import SrKey
 
 K_DEFAULT_PUSH_PULL = 0     # RequestType::kDefaultPushPull (common.h:68-71)
 
@@ -113,12 +114,22 @@ class Context:
     orig_dtype: int = 0
     orig_size: int = 0
     staging: object = None
-    # error feedback (Compression.*_ef): the f32 residual, of the tensor's
-    # kind, device and element count; None otherwise
-    residual: object = None
-    # stochastic rounding (Compression.*_sr): the context's Philox key
-    sr_key: int = 0
+    # the compressor's per-tensor operand of a cast, as cast plans take it:
+    # error feedback (Compression.*_ef) — the f32 residual, of the tensor's
+    # kind, device and element count; stochastic rounding (Compression.*_sr) —
+    # the context's Philox key, an SrKey; None otherwise
+    extra: object = None
     init_lock: threading.Lock = field(default_factory=threading.Lock)
+
+    @property
+    def residual(self):
+        """The error-feedback residual, or None."""
+        return None if isinstance(self.extra, SrKey) else self.extra
+
+    @property
+    def sr_key(self) -> int:
+        """The stochastic-rounding key, or 0."""
+        return int(self.extra) if isinstance(self.extra, SrKey) else 0
 
 
 class GradStats:
@@ -216,7 +227,11 @@ class Worker:
         next one rounds under."""
         return self._sr_step
 
-    def _next_sr_step(self) -> int:
+    def _next_step(self, compressor):
+        """The step the next compress of ``compressor`` rounds under: drawn
+        for stochastic rounding alone, None for every other."""
+        if not compressor.STOCHASTIC:
+            return None
         with self._sr_lock:
             step = self._sr_step
             self._sr_step += 1
@@ -259,11 +274,9 @@ class Worker:
                 ctx.compressor = compression
                 ctx.orig_dtype, ctx.orig_size = int(dtype), size
                 ctx.staging = compression.wire_like(data)
-                if compression.ERROR_FEEDBACK:
-                    ctx.residual = compression.residual_like(data)
-                if compression.STOCHASTIC:
-                    from .sr import context_key
-                    ctx.sr_key = context_key(ctx.declared_key, self.rank, self.sr_seed)
+                from .sr import context_key
+                ctx.extra = compression.cast_extra(
+                    data, lambda: context_key(ctx.declared_key, self.rank, self.sr_seed))
                 # the init push is the plain cast: the residual stays zero
                 data = compression.compress_into(ctx.staging, data)
                 size, dtype = _nbytes(data), DType(compression.WIRE_DTYPE)
@@ -337,13 +350,8 @@ class Worker:
             divisor = getattr(self.frontend, "size", None)
             if not divisor:
                 raise ValueError("average: the frontend does not know the worker count")
-        if ctx.residual is not None:
-            wire = ctx.compressor.compress_ef_into(ctx.staging, ctx.residual, _contiguous(tensor))
-        elif ctx.compressor.STOCHASTIC:
-            wire = ctx.compressor.compress_sr_into(ctx.staging, _contiguous(tensor), ctx.sr_key,
-                                                   self._next_sr_step())
-        else:
-            wire = ctx.compressor.compress_into(ctx.staging, _contiguous(tensor))
+        wire = ctx.compressor.compress_with(ctx.staging, _contiguous(tensor), ctx.extra,
+                                            self._next_step(ctx.compressor))
         cmd = cantor_command(K_DEFAULT_PUSH_PULL, ctx.dtype)
         idx = range(len(ctx.parts)) if order is None else order
         for i in idx:
@@ -462,19 +470,9 @@ class Worker:
             if c.compressor is not None:
                 casts.setdefault(c.compressor, []).append(c)
         for comp, cs in casts.items():
-            if comp.ERROR_FEEDBACK:
-                comp.compress_many_ef_into([c.staging for c in cs], [c.residual for c in cs],
-                                           [_contiguous(tensors[c.name]) for c in cs],
-                                           plans=self._cast_plans)
-                continue
-            if comp.STOCHASTIC:
-                comp.compress_many_sr_into([c.staging for c in cs],
-                                           [_contiguous(tensors[c.name]) for c in cs],
-                                           [c.sr_key for c in cs], self._next_sr_step(),
-                                           plans=self._cast_plans)
-                continue
-            comp.compress_many_into([c.staging for c in cs],
+            comp.compress_many_with([c.staging for c in cs],
                                     [_contiguous(tensors[c.name]) for c in cs],
+                                    [c.extra for c in cs], self._next_step(comp),
                                     plans=self._cast_plans)
         for g in groups:
             for t in g:
@@ -492,16 +490,13 @@ class Worker:
             self.grad_stats = GradStats(names, rows,
                                         [c.name for c in ctxs if c.compressor is None])
         for comp, cs in casts.items():
-            # an error-feedback plan decompresses too: named by its residuals
-            # — and a stochastic-rounding plan, named by its keys
-            extra = {"residuals": [c.residual for c in cs]} if comp.ERROR_FEEDBACK else \
-                {"keys": [c.sr_key for c in cs]} if comp.STOCHASTIC else {}
-            if stats:
-                extra["stats"] = rows[at:at + len(cs)]
-                at += len(cs)
-            comp.decompress_many_into([_contiguous(tensors[c.name]) for c in cs],
-                                      [c.staging for c in cs], divisor,
-                                      plans=self._cast_plans, **extra)
+            # the plan that compressed decompresses too: named by the same
+            # residuals or keys
+            comp.decompress_many_with([_contiguous(tensors[c.name]) for c in cs],
+                                      [c.staging for c in cs], [c.extra for c in cs], divisor,
+                                      plans=self._cast_plans,
+                                      stats=rows[at:at + len(cs)] if stats else None)
+            at += len(cs)
         if average:
             for c in ctxs:
                 if c.compressor is None:

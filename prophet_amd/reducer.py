@@ -255,29 +255,24 @@ class GpuReducer:
 
     def compress_fp16(self, dst, src, nelem: int, src_dtype: int, stream=None) -> int:
         """``dst[i] = fp16(src[i])`` for ``nelem`` ELEMENTS of f32, f64 or bf16
-        (byteps_reduce_compress_fp16; round to nearest even, f64 through f32)."""
-        _fits_cast(nelem, dst, src, src_dtype)
-        _check(self.lib.byteps_reduce_compress_fp16(_ptr(dst), _ptr(src), int(nelem),
-                                                    int(src_dtype), _stream_of(dst, stream)))
-        return 0
+        (``compress`` over the FLOAT16 wire; round to nearest even, f64 through
+        f32)."""
+        return self.compress(dst, src, nelem, src_dtype, DType.FLOAT16, stream)
 
     def decompress_fp16(self, dst, src, nelem: int, dst_dtype: int, divisor: int = 1,
                         stream=None) -> int:
         """``dst[i] = T(src[i])``, or ``T(fp16(src[i] / divisor))`` for a
         divisor above 1: the average of a compressed push_pull, divided on the
-        fp16 value as the reference does (byteps_reduce_decompress_fp16)."""
-        _fits_cast(nelem, src, dst, dst_dtype)
-        _check(self.lib.byteps_reduce_decompress_fp16(_ptr(dst), _ptr(src), int(nelem),
-                                                      int(dst_dtype), int(divisor),
-                                                      _stream_of(dst, stream)))
-        return 0
+        fp16 value as the reference does (``decompress`` over the FLOAT16
+        wire)."""
+        return self.decompress(dst, src, nelem, dst_dtype, DType.FLOAT16, divisor, stream)
 
     def compress(self, dst, src, nelem: int, src_dtype: int, wire_dtype: int,
                  stream=None) -> int:
         """``dst[i] = wire(src[i])`` for ``nelem`` ELEMENTS, the 2-byte wire
-        format named (byteps_reduce_compress_to): FLOAT16 is ``compress_fp16``,
-        BFLOAT16 takes f32, f64 or fp16 (round to nearest even, f64 through
-        f32, f32 subnormals kept)."""
+        format named (byteps_reduce_compress_to): FLOAT16 takes f32, f64 or
+        bf16, BFLOAT16 takes f32, f64 or fp16 (round to nearest even, f64
+        through f32, f32 subnormals kept)."""
         _fits_cast(nelem, dst, src, src_dtype)
         _check(self.lib.byteps_reduce_compress_to(_ptr(dst), _ptr(src), int(nelem),
                                                   int(src_dtype), int(wire_dtype),
@@ -433,6 +428,26 @@ class Plan:
             pass
 
 
+def _create_plain(lib, descs, n, wide_dtype, wire_dtype, out):
+    """The plain plan's creator: the fp16 wire has an entry of its own."""
+    if wire_dtype == DType.FLOAT16:
+        return lib.byteps_reduce_cast_plan_create(descs, n, wide_dtype, out)
+    return lib.byteps_reduce_cast_plan_create_wire(descs, n, wide_dtype, wire_dtype, out)
+
+
+# Per scheme of a cast plan: the descriptor, the creator (library, descriptors,
+# count, wide dtype, wire dtype, out-pointer), and for a segment's fourth item
+# the descriptor's field, its value there and its bounds check (element count,
+# item).
+_CAST_SCHEMES = {
+    "plain": (CastDesc, _create_plain, None, None, None),
+    "ef": (CastEfDesc, lambda lib, *a: lib.byteps_reduce_cast_plan_create_ef(*a),
+           "resid", _ptr, lambda nelem, resid: _fits(int(nelem) * 4, resid)),
+    "sr": (CastSrDesc, lambda lib, *a: lib.byteps_reduce_cast_plan_create_sr(*a),
+           "key", lambda key: int(key) & 0xffffffff, None),
+}
+
+
 class CastPlan:
     """``byteps_reduce_cast_plan``: the segments' tile table resident on the
     device.  ``compress`` writes every fp16 side from its wide side,
@@ -462,63 +477,31 @@ class CastPlan:
         self.wire_dtype = int(wire_dtype)
         self.handle = _vp()
         segments = [tuple(s) for s in segments]
-        self.stochastic = any(len(s) == 4 and isinstance(s[3], SrKey) for s in segments)
-        if self.stochastic:
-            self.error_feedback = False
-            if not all(len(s) == 4 and isinstance(s[3], SrKey) for s in segments):
-                raise ValueError("cast plan: every segment carries a key, or none does")
-            for wide, half, nelem, key in segments:
-                _fits_cast(nelem, half, wide, wide_dtype)
-            self._keep = segments     # keep the tensors alive
-            self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
-            self.nsegs = len(segments)
-            descs = (CastSrDesc * max(1, len(segments)))()
-            for i, (wide, half, nelem, key) in enumerate(segments):
-                descs[i].wide = _ptr(wide)
-                descs[i].half = _ptr(half)
-                descs[i].nelem = int(nelem)
-                descs[i].key = int(key) & 0xffffffff
-            _check(lib.byteps_reduce_cast_plan_create_sr(descs, len(segments), int(wide_dtype),
-                                                         self.wire_dtype,
-                                                         ctypes.byref(self.handle)))
-            return
-        self.error_feedback = any(len(s) == 4 for s in segments)
-        if self.error_feedback:
-            if not all(len(s) == 4 for s in segments):
-                raise ValueError("cast plan: every segment carries a residual, or none does")
-            for wide, half, nelem, resid in segments:
-                _fits_cast(nelem, half, wide, wide_dtype)
-                _fits(int(nelem) * 4, resid)
-            self._keep = segments     # keep the tensors alive, the residuals too
-            self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
-            self.nsegs = len(segments)
-            descs = (CastEfDesc * max(1, len(segments)))()
-            for i, (wide, half, nelem, resid) in enumerate(segments):
-                descs[i].wide = _ptr(wide)
-                descs[i].half = _ptr(half)
-                descs[i].resid = _ptr(resid)
-                descs[i].nelem = int(nelem)
-            _check(lib.byteps_reduce_cast_plan_create_ef(descs, len(segments), int(wide_dtype),
-                                                         self.wire_dtype,
-                                                         ctypes.byref(self.handle)))
-            return
-        for wide, half, nelem in segments:
-            _fits_cast(nelem, half, wide, wide_dtype)
-        self._keep = segments         # keep the tensors alive
+        keyed = [len(s) == 4 and isinstance(s[3], SrKey) for s in segments]
+        self.stochastic = any(keyed)
+        self.error_feedback = not self.stochastic and any(len(s) == 4 for s in segments)
+        if self.stochastic and not all(keyed):
+            raise ValueError("cast plan: every segment carries a key, or none does")
+        if self.error_feedback and not all(len(s) == 4 for s in segments):
+            raise ValueError("cast plan: every segment carries a residual, or none does")
+        desc, create, field, value, fits = _CAST_SCHEMES[
+            "sr" if self.stochastic else "ef" if self.error_feedback else "plain"]
+        for s in segments:
+            if len(s) != (3 if field is None else 4):
+                raise ValueError(f"cast plan: a segment of {len(s)} items")
+            _fits_cast(s[2], s[1], s[0], wide_dtype)
+            if fits is not None:
+                fits(s[2], s[3])
+        self._keep = segments         # keep the tensors alive, the residuals too
         self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
         self.nsegs = len(segments)
-        descs = (CastDesc * max(1, len(segments)))()
-        for i, (wide, half, nelem) in enumerate(segments):
-            descs[i].wide = _ptr(wide)
-            descs[i].half = _ptr(half)
-            descs[i].nelem = int(nelem)
-        if self.wire_dtype == DType.FLOAT16:
-            _check(lib.byteps_reduce_cast_plan_create(descs, len(segments), int(wide_dtype),
-                                                      ctypes.byref(self.handle)))
-        else:
-            _check(lib.byteps_reduce_cast_plan_create_wire(descs, len(segments), int(wide_dtype),
-                                                           self.wire_dtype,
-                                                           ctypes.byref(self.handle)))
+        descs = (desc * max(1, len(segments)))()
+        for d, s in zip(descs, segments):
+            d.wide, d.half, d.nelem = _ptr(s[0]), _ptr(s[1]), int(s[2])
+            if field is not None:
+                setattr(d, field, value(s[3]))
+        _check(create(lib, descs, len(segments), int(wide_dtype), self.wire_dtype,
+                      ctypes.byref(self.handle)))
 
     def compress(self, stream=None, *, step: int | None = None) -> None:
         """One launch; ``step`` (mod 2^32) for a stochastic-rounding plan and

@@ -21,11 +21,11 @@ op                                    reference / C ABI
                                       ``srcs[0]``: the zero-copy accumulator)
 ``bpsr::compress_fp16(src) -> out``   ``FP16Compressor.compress``,
                                       byteps/torch/compression.py
-                                      -> byteps_reduce_compress_fp16
+                                      -> byteps_reduce_compress_to
 ``bpsr::compress_fp16_out(dst, src)`` the same into a preallocated fp16 ``dst``
 ``bpsr::decompress_fp16_out(dst,      ``FP16Compressor.decompress`` fused with
 src, divisor)``                       average's divide on the fp16 value
-                                      -> byteps_reduce_decompress_fp16
+                                      -> byteps_reduce_decompress_from
 ``bpsr::compress_bf16(src) -> out``   ``BF16Compressor.compress`` (build
                                       extension: f32 / f64 / fp16 as bf16)
                                       -> byteps_reduce_compress_to
@@ -126,15 +126,19 @@ _WIDE_OF = {torch.float16: (torch.float32, torch.float64, torch.bfloat16),
 _WIRE_NAME = {torch.float16: "fp16", torch.bfloat16: "bf16"}
 
 
-def _check_cast(half: torch.Tensor, wide: torch.Tensor, wire=torch.float16) -> int:
-    """Operands of a cast: ``half`` of the wire dtype (fp16 unless named),
-    ``wide`` f32 / f64 / the other 2-byte float, as many elements, one device,
-    contiguous.  Returns the element count."""
-    for t in (half, wide):
+def _check_on_device(*tensors) -> None:
+    for t in tensors:
         if t.device.type != "cuda":
             raise ReduceError(EARGS, f"bpsr ops need device tensors, got {t.device}")
         if not t.is_contiguous():
             raise ReduceError(EARGS, "bpsr ops need contiguous tensors")
+
+
+def _check_cast(half: torch.Tensor, wide: torch.Tensor, wire=torch.float16) -> int:
+    """Operands of a cast: ``half`` of the wire dtype (fp16 unless named),
+    ``wide`` f32 / f64 / the other 2-byte float, as many elements, one device,
+    contiguous.  Returns the element count."""
+    _check_on_device(half, wide)
     if half.dtype != wire:
         raise ReduceError(EDTYPE, f"the compressed tensor must be {str(wire)[len('torch.'):]}, "
                                   f"got {half.dtype}")
@@ -145,82 +149,18 @@ def _check_cast(half: torch.Tensor, wide: torch.Tensor, wire=torch.float16) -> i
     return wide.numel()
 
 
-@torch.library.custom_op("bpsr::compress_fp16_out", mutates_args=("dst",), device_types="cuda")
-def compress_fp16_out(dst: torch.Tensor, src: torch.Tensor) -> None:
-    n = _check_cast(dst, src)
-    _red().compress_fp16(dst, src, n, from_torch(src.dtype), stream=_stream(dst))
-
-
-@torch.library.custom_op("bpsr::compress_fp16", mutates_args=(), device_types="cuda")
-def compress_fp16(src: torch.Tensor) -> torch.Tensor:
-    out = torch.empty(src.shape, dtype=torch.float16, device=src.device)
-    n = _check_cast(out, src)
-    _red().compress_fp16(out, src, n, from_torch(src.dtype), stream=_stream(out))
-    return out
-
-
-@torch.library.custom_op("bpsr::decompress_fp16_out", mutates_args=("dst",),
-                         device_types="cuda")
-def decompress_fp16_out(dst: torch.Tensor, src: torch.Tensor, divisor: int = 1) -> None:
-    n = _check_cast(src, dst)
-    if divisor < 1:
-        raise ReduceError(EARGS, f"divisor {divisor} < 1")
-    _red().decompress_fp16(dst, src, n, from_torch(dst.dtype), divisor, stream=_stream(dst))
-
-
-@torch.library.custom_op("bpsr::compress_bf16_out", mutates_args=("dst",), device_types="cuda")
-def compress_bf16_out(dst: torch.Tensor, src: torch.Tensor) -> None:
-    n = _check_cast(dst, src, torch.bfloat16)
-    _red().compress(dst, src, n, from_torch(src.dtype), DType.BFLOAT16, stream=_stream(dst))
-
-
-@torch.library.custom_op("bpsr::compress_bf16", mutates_args=(), device_types="cuda")
-def compress_bf16(src: torch.Tensor) -> torch.Tensor:
-    out = torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
-    n = _check_cast(out, src, torch.bfloat16)
-    _red().compress(out, src, n, from_torch(src.dtype), DType.BFLOAT16, stream=_stream(out))
-    return out
-
-
-@torch.library.custom_op("bpsr::decompress_bf16_out", mutates_args=("dst",),
-                         device_types="cuda")
-def decompress_bf16_out(dst: torch.Tensor, src: torch.Tensor, divisor: int = 1) -> None:
-    n = _check_cast(src, dst, torch.bfloat16)
-    if divisor < 1:
-        raise ReduceError(EARGS, f"divisor {divisor} < 1")
-    _red().decompress(dst, src, n, from_torch(dst.dtype), DType.BFLOAT16, divisor,
-                      stream=_stream(dst))
-
-
 def _check_cast_ef(dst: torch.Tensor, resid: torch.Tensor, src: torch.Tensor, wire) -> int:
     """Operands of an error-feedback compress: ``_check_cast`` with an f32
     ``src`` and an f32 ``resid`` of its size and device."""
     n = _check_cast(dst, src, wire)
     if src.dtype != torch.float32:
         raise ReduceError(EDTYPE, f"error-feedback compression of {src.dtype} (float32 only)")
-    if resid.device.type != "cuda":
-        raise ReduceError(EARGS, f"bpsr ops need device tensors, got {resid.device}")
-    if not resid.is_contiguous():
-        raise ReduceError(EARGS, "bpsr ops need contiguous tensors")
+    _check_on_device(resid)
     if resid.dtype != torch.float32:
         raise ReduceError(EDTYPE, f"the residual must be float32, got {resid.dtype}")
     if resid.numel() != n or resid.device != src.device:
         raise ReduceError(EARGS, "bpsr ops need tensors of one size and device")
     return n
-
-
-@torch.library.custom_op("bpsr::compress_fp16_ef_out", mutates_args=("dst", "resid"),
-                         device_types="cuda")
-def compress_fp16_ef_out(dst: torch.Tensor, resid: torch.Tensor, src: torch.Tensor) -> None:
-    n = _check_cast_ef(dst, resid, src, torch.float16)
-    _red().compress_ef(dst, resid, src, n, DType.FLOAT32, DType.FLOAT16, stream=_stream(dst))
-
-
-@torch.library.custom_op("bpsr::compress_bf16_ef_out", mutates_args=("dst", "resid"),
-                         device_types="cuda")
-def compress_bf16_ef_out(dst: torch.Tensor, resid: torch.Tensor, src: torch.Tensor) -> None:
-    n = _check_cast_ef(dst, resid, src, torch.bfloat16)
-    _red().compress_ef(dst, resid, src, n, DType.FLOAT32, DType.BFLOAT16, stream=_stream(dst))
 
 
 def _check_cast_sr(dst: torch.Tensor, src: torch.Tensor, wire) -> int:
@@ -232,68 +172,56 @@ def _check_cast_sr(dst: torch.Tensor, src: torch.Tensor, wire) -> int:
     return n
 
 
-@torch.library.custom_op("bpsr::compress_fp16_sr_out", mutates_args=("dst",),
-                         device_types="cuda")
-def compress_fp16_sr_out(dst: torch.Tensor, src: torch.Tensor, key: int, step: int) -> None:
-    n = _check_cast_sr(dst, src, torch.float16)
-    _red().compress_sr(dst, src, n, key, step, DType.FLOAT16, stream=_stream(dst))
+def _cast_ops(wire, name: str) -> dict:
+    """Registers the cast ops of one wire format, ``bpsr::compress_<name>`` and
+    the rest, with their fakes; returns them by op name."""
+    wire_id = from_torch(wire)
+
+    def compress_out(dst: torch.Tensor, src: torch.Tensor) -> None:
+        n = _check_cast(dst, src, wire)
+        _red().compress(dst, src, n, from_torch(src.dtype), wire_id, stream=_stream(dst))
+
+    def compress(src: torch.Tensor) -> torch.Tensor:
+        out = torch.empty(src.shape, dtype=wire, device=src.device)
+        compress_out(out, src)
+        return out
+
+    def decompress_out(dst: torch.Tensor, src: torch.Tensor, divisor: int = 1) -> None:
+        n = _check_cast(src, dst, wire)
+        if divisor < 1:
+            raise ReduceError(EARGS, f"divisor {divisor} < 1")
+        _red().decompress(dst, src, n, from_torch(dst.dtype), wire_id, divisor,
+                          stream=_stream(dst))
+
+    def compress_ef_out(dst: torch.Tensor, resid: torch.Tensor, src: torch.Tensor) -> None:
+        n = _check_cast_ef(dst, resid, src, wire)
+        _red().compress_ef(dst, resid, src, n, DType.FLOAT32, wire_id, stream=_stream(dst))
+
+    def compress_sr_out(dst: torch.Tensor, src: torch.Tensor, key: int, step: int) -> None:
+        n = _check_cast_sr(dst, src, wire)
+        _red().compress_sr(dst, src, n, key, step, wire_id, stream=_stream(dst))
+
+    def no_output(*args, **kwargs):
+        return None
+
+    ops = {}
+    for op, fn, mutates, fake in (
+            (f"compress_{name}_out", compress_out, ("dst",), no_output),
+            (f"compress_{name}", compress, (),
+             lambda src: torch.empty(src.shape, dtype=wire, device=src.device)),
+            (f"decompress_{name}_out", decompress_out, ("dst",), no_output),
+            (f"compress_{name}_ef_out", compress_ef_out, ("dst", "resid"), no_output),
+            (f"compress_{name}_sr_out", compress_sr_out, ("dst",), no_output)):
+        ops[op] = torch.library.custom_op(f"bpsr::{op}", fn, mutates_args=mutates,
+                                          device_types="cuda")
+        ops[op].register_fake(fake)
+    return ops
 
 
-@torch.library.custom_op("bpsr::compress_bf16_sr_out", mutates_args=("dst",),
-                         device_types="cuda")
-def compress_bf16_sr_out(dst: torch.Tensor, src: torch.Tensor, key: int, step: int) -> None:
-    n = _check_cast_sr(dst, src, torch.bfloat16)
-    _red().compress_sr(dst, src, n, key, step, DType.BFLOAT16, stream=_stream(dst))
-
-
-@compress_fp16_sr_out.register_fake
-def _(dst, src, key, step):
-    return None
-
-
-@compress_bf16_sr_out.register_fake
-def _(dst, src, key, step):
-    return None
-
-
-@compress_fp16_ef_out.register_fake
-def _(dst, resid, src):
-    return None
-
-
-@compress_bf16_ef_out.register_fake
-def _(dst, resid, src):
-    return None
-
-
-@compress_bf16_out.register_fake
-def _(dst, src):
-    return None
-
-
-@compress_bf16.register_fake
-def _(src):
-    return torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
-
-
-@decompress_bf16_out.register_fake
-def _(dst, src, divisor=1):
-    return None
-
-
-@compress_fp16_out.register_fake
-def _(dst, src):
-    return None
-
-
-@compress_fp16.register_fake
-def _(src):
-    return torch.empty(src.shape, dtype=torch.float16, device=src.device)
-
-
-@decompress_fp16_out.register_fake
-def _(dst, src, divisor=1):
-    return None
+# compress_fp16, compress_fp16_out, decompress_fp16_out, compress_fp16_ef_out,
+# compress_fp16_sr_out and the same five for bf16, as module-level names
+for _wire, _name in ((torch.float16, "fp16"), (torch.bfloat16, "bf16")):
+    globals().update(_cast_ops(_wire, _name))
 
 
 @sum_.register_fake
