@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import accum_model as am
+import fold_run
 from prophet_amd.dtypes import DType
 from test_blockq_gpu import MIXED, Table
 from test_parity_gpu import ptr, to_dev
@@ -62,27 +63,10 @@ def run_sum_n(red, dev, dt, ins, L, src_offs=None, dst_off=16, inplace=False,
               mode=MODE_ACCUM_F32):
     """sum_n of host byte arrays `ins` placed at byte offsets `src_offs` of
     0xEE-filled buffers, into a 0x5A-prefilled dst at `dst_off` (or into
-    srcs[0]).  Checks the guard bytes around dst and that no source other than
-    an aliased srcs[0] changed; returns dst's L bytes."""
-    src_offs = list(src_offs) if src_offs is not None else [0] * len(ins)
-    bufs = [to_dev(x, dev, offset=o)[0] for x, o in zip(ins, src_offs)]
-    if inplace:
-        dbuf, doff = bufs[0], src_offs[0]
-    else:
-        dbuf, _ = to_dev(np.full(L, 0x5A, np.uint8), dev, offset=dst_off)
-        doff = dst_off
-    red.sum_n(ptr(dbuf, doff), [ptr(b, o) for b, o in zip(bufs, src_offs)], L, dt, mode=mode)
-    torch.cuda.synchronize()
-    whole = dbuf.cpu().numpy()
-    assert bool((whole[:doff] == 0xEE).all()), "bytes before dst changed"
-    assert bool((whole[doff + L:] == 0xEE).all()), "bytes after dst changed"
-    for k, (b, o, x) in enumerate(zip(bufs, src_offs, ins)):
-        if inplace and k == 0:
-            continue
-        h = b.cpu().numpy()
-        assert np.array_equal(h[o:o + len(x)], x), f"source {k} changed"
-        assert bool((h[:o] == 0xEE).all()) and bool((h[o + len(x):] == 0xEE).all())
-    return whole[doff:doff + L]
+    srcs[0]).  Checks the guard bytes around dst and every source and that no
+    source other than an aliased srcs[0] changed (fold_run.Operands); returns
+    dst's L bytes."""
+    return fold_run.run_sum_n(red, dev, dt, ins, L, src_offs, dst_off, inplace, mode)
 
 
 # ------------------------------------------------------------ sum_n, small ----
