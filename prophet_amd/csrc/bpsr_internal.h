@@ -143,6 +143,21 @@ struct BlockqLaunch {
   unsigned long long* ktrace;
 #endif
 };
+// The keyed consumer's stamp hooks: blockq_key_kernel calls key_stamp at tile
+// `tile`'s stage i < 4, its helper key_block_stamp when it forwards block b's
+// word.  Empty in the product; the layout (4 per tile, then one per block) is
+// what tools/dbg/keyed_trace_report.py reads.
+#ifdef BPSR_KEYED_TRACE
+__device__ inline void key_stamp(const BlockqLaunch& Q, uint32_t tile, int i) {
+  if (threadIdx.x == 0) Q.ktrace[4 * (uint64_t)tile + i] = wall_clock64();
+}
+__device__ inline void key_block_stamp(const BlockqLaunch& Q, uint32_t b) {
+  Q.ktrace[4 * (uint64_t)Q.L.tiles + b] = wall_clock64();
+}
+#else
+__device__ inline void key_stamp(const BlockqLaunch&, uint32_t, int) {}
+__device__ inline void key_block_stamp(const BlockqLaunch&, uint32_t) {}
+#endif
 constexpr uint32_t kSeqLast = 8;  // one per XCD: workgroups are dealt round-robin over 8
 inline uint32_t seq_counted(uint32_t grid) { return grid < kSeqLast ? grid : kSeqLast; }
 // One wave on `s`: returns once the counter reaches target (the last

@@ -6,7 +6,31 @@
 //                   round (server.cc:216-250, cpu_reducer.cc:86-91) with a
 //                   single pass: (N+1)*B HBM bytes instead of (3N-1)*B.
 //   batched_kernel  the same over a table of buckets (one Prophet block,
-//                   scheduled_queue.cc:244-296) in one launch.
+//                   scheduled_queue.cc:244-296) in one launch: workgroup b runs
+//                   tile record b.
+//   blockq_kernel   persistent block consumer: resident workgroups sweep the
+//                   whole table's records, a tile waiting until its block and
+//                   every block before it is released for the launch's epoch.
+//   blockq_gate_kernel  the same wait, dispatch-ordered: one record per
+//                   workgroup like batched_kernel (the block queue's default).
+//   blockq_key_kernel   keyed consumer (the PS server's device releases): a
+//                   tile waits for its own block's word, which carries the
+//                   order its sources fold in.
+//
+// Shared pieces, top to bottom:
+//   fold_vector_exact  one vector's exact fold (NaN payload rules), the replay.
+//   fold_tile_body / fold_tile_full_buf  one tile's fast fold: the guarded
+//                   partial tile (flat loads) and the full tile (buffer loads).
+//   fold_elements   the element path of one bucket.
+//   RecRegs, load_record / regs_from_words, run_record  a tile record in
+//                   registers and what it runs: element, full or partial tile,
+//                   sources from registers (n <= 8) or the record's array.
+//   PermSrcs, PermSrcs16  a pointer array in arrival order (keyed consumer,
+//                   which dispatches its own records through them).
+//   with_vpt / with_pol  the launchers' run-time (vpt, policy) as compile-time
+//                   constants; one KernelAttr per instantiated kernel.
+// The keyed consumer's probe stamps (key_stamp, key_block_stamp) are hooks
+// defined beside BlockqLaunch::ktrace in bpsr_internal.h, empty in the product.
 //
 // Design (pure HBM streaming, no reuse, no LDS, no MFMA):
 //   * the vector range is cut into tiles of kBlock*VPT 16-byte vectors; a
@@ -28,6 +52,8 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "bpsr_internal.h"
 #include "bpsr_ops.h"
@@ -105,11 +131,12 @@ __device__ __forceinline__ vec16 fold_vector_exact(const XS& srcs, int n, uint64
 // NaN anywhere in a chain survives to its result, so one has_nan test per
 // vector decides whether the exact NaN-payload rule must be replayed
 // (fold_vector_exact) — a wave-uniform branch never taken on finite data.
-// GUARD: the last, partial tile (vectors past nvec are neither read nor written).
+// This is the guarded form for the last, partial tile: vectors past nvec are
+// neither read nor written.
 // NS > 0: exactly NS sources; NS < 0: at most -NS (<= 8) sources, n at run
 // time, one load group with compile-time indices (so `srcs` may be a register
 // array); NS == 0: any n.  `xsrcs` (memory) serves the exact NaN replay.
-template <class Op, int VPT, int NT, int NS, bool GUARD, class XS = SrcPtrs,
+template <class Op, int VPT, int NT, int NS, class XS = SrcPtrs,
           class SP = const unsigned char* const*>
 __device__ __forceinline__ void fold_tile_body(const SP& srcs, const XS& xsrcs, int n,
                                                unsigned char* dst, uint64_t vec_off,
@@ -122,7 +149,7 @@ __device__ __forceinline__ void fold_tile_body(const SP& srcs, const XS& xsrcs, 
   static_assert(NS >= 0 || G == NSA, "NS < 0 needs one load group");
   bool valid[VPT];
 #pragma unroll
-  for (int j = 0; j < VPT; ++j) valid[j] = !GUARD || (v0 + lane + (uint64_t)j * kBlock < nvec);
+  for (int j = 0; j < VPT; ++j) valid[j] = v0 + lane + (uint64_t)j * kBlock < nvec;
   typename Op::Acc acc[VPT];
   auto group = [&](int k0) __attribute__((always_inline)) {
     vec16 x[G][VPT];
@@ -241,16 +268,6 @@ __device__ __forceinline__ void fold_tile_full_buf(const SP& srcs, const XS& xsr
   }
 }
 
-template <class Op, int VPT, int NT, int NS>
-__device__ __forceinline__ void fold_tile(const unsigned char* const* srcs, int n,
-                                          unsigned char* dst, uint64_t vec_off, uint64_t v0,
-                                          uint64_t nvec, int lane) {
-  if (v0 + (uint64_t)kBlock * VPT <= nvec)
-    fold_tile_full_buf<Op, VPT, NT, NS>(srcs, srcs, n, dst, vec_off + v0 * 16, lane);
-  else
-    fold_tile_body<Op, VPT, NT, NS, true>(srcs, srcs, n, dst, vec_off, v0, nvec, lane);
-}
-
 // Element part: elements [0, head) and [tail_begin, n_elems) plus trailing
 // bytes; elements >= tail_sem_from get the F16C-tail NaN rule (fp16 only).
 // Each element's N loads are issued together (groups of 8) before the fold.
@@ -344,8 +361,8 @@ __global__ __launch_bounds__(kBlock) void fold_kernel(FoldArgs a) {
     fold_tile_full_buf<Op, VPT, NT, NS>(a.srcs, a.srcs, a.n, a.dst,
                                         a.g.vec_off + tile * tile_vecs * 16, threadIdx.x);
   else if (tile * tile_vecs < a.g.nvec)
-    fold_tile_body<Op, VPT, NT, NS, true>(a.srcs, a.srcs, a.n, a.dst, a.g.vec_off,
-                                          tile * tile_vecs, a.g.nvec, threadIdx.x);
+    fold_tile_body<Op, VPT, NT, NS>(a.srcs, a.srcs, a.n, a.dst, a.g.vec_off, tile * tile_vecs,
+                                    a.g.nvec, threadIdx.x);
   if (elem_mode == 2)
     fold_elements<Op>(a.srcs, a.n, a.dst, a.g, a.aligned != 0,
                       (uint64_t)blockIdx.x * kBlock + threadIdx.x, (uint64_t)a.grid * kBlock);
@@ -377,15 +394,14 @@ __device__ __forceinline__ void run_record(const RecRegs& r, const unsigned char
     if (r.kind == kTileFull) {
       fold_tile_full_buf<Op, VPT, NT, -8>(r.p, msrcs, (int)r.n, r.dst, 0, threadIdx.x, mid);
     } else {
-      fold_tile_body<Op, VPT, NT, -8, true>(r.p, msrcs, (int)r.n, r.dst, 0, 0, r.a, threadIdx.x);
+      fold_tile_body<Op, VPT, NT, -8>(r.p, msrcs, (int)r.n, r.dst, 0, 0, r.a, threadIdx.x);
       mid();
     }
   } else {
     if (r.kind == kTileFull) {
       fold_tile_full_buf<Op, VPT, NT, 0>(msrcs, msrcs, (int)r.n, r.dst, 0, threadIdx.x, mid);
     } else {
-      fold_tile_body<Op, VPT, NT, 0, true>(msrcs, msrcs, (int)r.n, r.dst, 0, 0, r.a,
-                                           threadIdx.x);
+      fold_tile_body<Op, VPT, NT, 0>(msrcs, msrcs, (int)r.n, r.dst, 0, 0, r.a, threadIdx.x);
       mid();
     }
   }
@@ -728,9 +744,7 @@ __device__ __forceinline__ void forward_host_keys(const BlockqLaunch& Q) {
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           __hip_atomic_store(Q.kwords + (uint64_t)b * kKeyWordStride, h, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
-#ifdef BPSR_KEYED_TRACE
-          Q.ktrace[4 * (uint64_t)Q.L.tiles + b] = wall_clock64();
-#endif
+          key_block_stamp(Q, b);
         } else {
           pending = true;
         }
@@ -801,10 +815,7 @@ __global__ __launch_bounds__(kBlock) void blockq_key_kernel(BlockqLaunch Q) {
     return;
   }
   const uint32_t t = blockIdx.x - Q.helper;
-#ifdef BPSR_KEYED_TRACE
-  unsigned long long* kt = Q.ktrace + 4 * (uint64_t)t;
-  if (threadIdx.x == 0) kt[0] = wall_clock64();
-#endif
+  key_stamp(Q, t, 0);  // entry
   const unsigned char* rec = Q.L.recs + (uint64_t)t * Q.L.rec_stride;
   const RecRegs r = load_record(rec);
   const uint32_t blk = reinterpret_cast<const TileHead*>(rec)->block;
@@ -830,9 +841,7 @@ __global__ __launch_bounds__(kBlock) void blockq_key_kernel(BlockqLaunch Q) {
     // per waiting tile would invalidate the XCD's L2 each time
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   }
-#ifdef BPSR_KEYED_TRACE
-  if (threadIdx.x == 0) kt[1] = wall_clock64();
-#endif
+  key_stamp(Q, t, 1);  // word seen
   const uint32_t perm = (uint32_t)(w >> 32);
   if (perm == kKeySkip) {
     keep_prefetch(pf);
@@ -866,8 +875,8 @@ __global__ __launch_bounds__(kBlock) void blockq_key_kernel(BlockqLaunch Q) {
       fold_tile_full_buf<Op, VPT, NT, 0, NoMid, PermSrcs16>(ps, ps, (int)r.n, r.dst, 0,
                                                             threadIdx.x);
     } else {
-      fold_tile_body<Op, VPT, NT, 0, true, PermSrcs16>(ps, ps, (int)r.n, r.dst, 0, 0, r.a,
-                                                        threadIdx.x);
+      fold_tile_body<Op, VPT, NT, 0, PermSrcs16>(ps, ps, (int)r.n, r.dst, 0, 0, r.a,
+                                                  threadIdx.x);
     }
     keep_prefetch(pf);
     key_tile_done<NT>(Q, blk, r.kind == kTileFull && NT == kPolWt);
@@ -894,17 +903,12 @@ __global__ __launch_bounds__(kBlock) void blockq_key_kernel(BlockqLaunch Q) {
     fold_tile_full_buf<Op, VPT, NT, -8, NoMid, PermSrcs>(q, xs, (int)r.n, r.dst, 0,
                                                          threadIdx.x);
   } else {
-    fold_tile_body<Op, VPT, NT, -8, true, PermSrcs>(q, xs, (int)r.n, r.dst, 0, 0, r.a,
-                                                     threadIdx.x);
+    fold_tile_body<Op, VPT, NT, -8, PermSrcs>(q, xs, (int)r.n, r.dst, 0, 0, r.a, threadIdx.x);
   }
   keep_prefetch(pf);
-#ifdef BPSR_KEYED_TRACE
-  if (threadIdx.x == 0) kt[2] = wall_clock64();
-#endif
+  key_stamp(Q, t, 2);  // folded
   key_tile_done<NT>(Q, blk, r.kind == kTileFull && NT == kPolWt);
-#ifdef BPSR_KEYED_TRACE
-  if (threadIdx.x == 0) kt[3] = wall_clock64();
-#endif
+  key_stamp(Q, t, 3);  // counted
 }
 
 // ------------------------------------------------------------- launchers ----
@@ -921,6 +925,30 @@ static hipError_t launch_with_stop(K kernel, uint32_t grid, size_t lds, hipStrea
   return hipGetLastError();
 }
 
+// The launch ladder: a launcher's run-time tile size and cache policy as
+// compile-time constants, f(std::integral_constant<int, VPT or NT>).  Every
+// kernel family is instantiated for exactly these 3 x 3 values.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+
+template <class F>
+static hipError_t with_vpt(int vpt, F&& f) {
+  switch (vpt) {
+    case 1: return f(IntC<1>{});
+    case 4: return f(IntC<4>{});
+    default: return f(IntC<2>{});
+  }
+}
+
+template <class F>
+static hipError_t with_pol(int pol, F&& f) {
+  switch (pol) {
+    case kPolNt: return f(IntC<kPolNt>{});
+    case kPolWt: return f(IntC<kPolWt>{});
+    default: return f(IntC<kPolPlain>{});
+  }
+}
+
 template <class Op, int VPT, int NT, int NS>
 static hipError_t launch_fold_ns(const FoldArgs& a, const Tuning& tu, hipStream_t s) {
   static KernelAttr attr;
@@ -932,25 +960,6 @@ static hipError_t launch_fold_ns(const FoldArgs& a, const Tuning& tu, hipStream_
   hipLaunchKernelGGL((fold_kernel<Op, VPT, NT, NS>), dim3(b.grid), dim3(kBlock),
                      occ_lds_bytes(launch_occ(tu, b.grid, false)), s, b);
   return hipGetLastError();
-}
-
-template <class Op, int VPT, int NT>
-static hipError_t launch_fold_vpt(const FoldArgs& a, const Tuning& tu, hipStream_t s) {
-  switch (a.n) {  // compile-time source counts for the common worker counts
-    case 2: return launch_fold_ns<Op, VPT, NT, 2>(a, tu, s);
-    case 8: return launch_fold_ns<Op, VPT, NT, 8>(a, tu, s);
-    case 16: return launch_fold_ns<Op, VPT, NT, 16>(a, tu, s);
-    default: return launch_fold_ns<Op, VPT, NT, 0>(a, tu, s);
-  }
-}
-
-template <class Op, int NT>
-static hipError_t launch_fold_pol(const FoldArgs& a, int vpt, const Tuning& tu, hipStream_t s) {
-  switch (vpt) {
-    case 1: return launch_fold_vpt<Op, 1, NT>(a, tu, s);
-    case 4: return launch_fold_vpt<Op, 4, NT>(a, tu, s);
-    default: return launch_fold_vpt<Op, 2, NT>(a, tu, s);
-  }
 }
 
 template <class Op>
@@ -965,42 +974,45 @@ static hipError_t launch_fold_op(const FoldArgs& a, const Tuning& tu, hipStream_
     vpt = 1;
     t.occ = 2;
   }
-  switch (pol) {
-    case kPolNt: return launch_fold_pol<Op, kPolNt>(a, vpt, t, s);
-    case kPolWt: return launch_fold_pol<Op, kPolWt>(a, vpt, t, s);
-    default: return launch_fold_pol<Op, kPolPlain>(a, vpt, t, s);
-  }
+  return with_pol(pol, [&](auto P) {
+    return with_vpt(vpt, [&](auto V) {
+      constexpr int VPT = decltype(V)::value, NT = decltype(P)::value;
+      switch (a.n) {  // compile-time source counts for the common worker counts
+        case 2: return launch_fold_ns<Op, VPT, NT, 2>(a, t, s);
+        case 8: return launch_fold_ns<Op, VPT, NT, 8>(a, t, s);
+        case 16: return launch_fold_ns<Op, VPT, NT, 16>(a, t, s);
+        default: return launch_fold_ns<Op, VPT, NT, 0>(a, t, s);
+      }
+    });
+  });
 }
 
-template <class Op, int VPT>
-static hipError_t launch_batched_vpt(const BatchLaunch& L, const Tuning& tu, hipStream_t s) {
-  static KernelAttr attr[3];
-  const void* k[3] = {reinterpret_cast<const void*>(&batched_kernel<Op, VPT, kPolPlain>),
-                      reinterpret_cast<const void*>(&batched_kernel<Op, VPT, kPolNt>),
-                      reinterpret_cast<const void*>(&batched_kernel<Op, VPT, kPolWt>)};
-  note_where("batched: allow_lds");
-  for (int i = 0; i < 3; ++i) {
-    const hipError_t ok = allow_lds(attr[i], k[i]);
-    if (ok != hipSuccess) return ok;
-  }
-  note_where("batched: launch");
-  if (L.tiles == 0) return hipSuccess;
-  const size_t lds = occ_lds_bytes(launch_occ(tu, L.tiles, true));
-  switch (cache_pol(tu, (uint64_t)L.tiles * VPT * kBlock * 16)) {
-    case kPolNt: return launch_with_stop(batched_kernel<Op, VPT, kPolNt>, L.tiles, lds, s, L.stop, L);
-    case kPolWt: return launch_with_stop(batched_kernel<Op, VPT, kPolWt>, L.tiles, lds, s, L.stop, L);
-    default: return launch_with_stop(batched_kernel<Op, VPT, kPolPlain>, L.tiles, lds, s, L.stop, L);
-  }
+template <class Op, int VPT, int NT>
+static hipError_t allow_batched() {
+  static KernelAttr attr;
+  return allow_lds(attr, reinterpret_cast<const void*>(&batched_kernel<Op, VPT, NT>));
 }
 
 template <class Op>
 static hipError_t launch_batched_op(const BatchLaunch& L, int vpt, const Tuning& tu,
                                     hipStream_t s) {
-  switch (vpt) {
-    case 1: return launch_batched_vpt<Op, 1>(L, tu, s);
-    case 4: return launch_batched_vpt<Op, 4>(L, tu, s);
-    default: return launch_batched_vpt<Op, 2>(L, tu, s);
-  }
+  return with_vpt(vpt, [&](auto V) {
+    constexpr int VPT = decltype(V)::value;
+    // the policy follows the table's size, launch by launch: the kernels of
+    // all three are allowed their LDS before any is launched
+    note_where("batched: allow_lds");
+    hipError_t ok = allow_batched<Op, VPT, kPolPlain>();
+    if (ok == hipSuccess) ok = allow_batched<Op, VPT, kPolNt>();
+    if (ok == hipSuccess) ok = allow_batched<Op, VPT, kPolWt>();
+    if (ok != hipSuccess) return ok;
+    note_where("batched: launch");
+    if (L.tiles == 0) return hipSuccess;
+    const size_t lds = occ_lds_bytes(launch_occ(tu, L.tiles, true));
+    return with_pol(cache_pol(tu, (uint64_t)L.tiles * VPT * kBlock * 16), [&](auto P) {
+      return launch_with_stop(batched_kernel<Op, VPT, decltype(P)::value>, L.tiles, lds, s,
+                              L.stop, L);
+    });
+  });
 }
 
 template <class Op, int VPT, int NT>
@@ -1028,25 +1040,15 @@ static hipError_t launch_blockq_k(const BlockqLaunch& Q, size_t lds, bool gated,
   return launch_with_stop(blockq_kernel<Op, VPT, NT>, Q.grid, lds, s, Q.L.stop, Q);
 }
 
-template <class Op, int VPT>
-static hipError_t launch_blockq_vpt(const BlockqLaunch& Q, int pol, size_t lds, bool gated,
-                                    hipStream_t s) {
-  switch (pol) {
-    case kPolNt: return launch_blockq_k<Op, VPT, kPolNt>(Q, lds, gated, s);
-    case kPolWt: return launch_blockq_k<Op, VPT, kPolWt>(Q, lds, gated, s);
-    default: return launch_blockq_k<Op, VPT, kPolPlain>(Q, lds, gated, s);
-  }
-}
-
 template <class Op>
 static hipError_t launch_blockq_op(const BlockqLaunch& Q, int vpt, int pol, size_t lds,
                                    bool gated, hipStream_t s) {
   if (Q.grid == 0) return hipSuccess;
-  switch (vpt) {
-    case 1: return launch_blockq_vpt<Op, 1>(Q, pol, lds, gated, s);
-    case 4: return launch_blockq_vpt<Op, 4>(Q, pol, lds, gated, s);
-    default: return launch_blockq_vpt<Op, 2>(Q, pol, lds, gated, s);
-  }
+  return with_vpt(vpt, [&](auto V) {
+    return with_pol(pol, [&](auto P) {
+      return launch_blockq_k<Op, decltype(V)::value, decltype(P)::value>(Q, lds, gated, s);
+    });
+  });
 }
 
 }  // namespace bpsr

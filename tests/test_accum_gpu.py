@@ -13,7 +13,7 @@ result holds a NaN).
 Geometry: a tile is 256 threads x VPT 16-byte vectors.  At the small sizes
 fold_vpt (bpsr_internal.h) picks VPT 1, so a tile holds 2,048 16-bit elements;
 SMALL is 3 full tiles (fold_tile_full_buf), a guarded partial tile
-(fold_tile_body<GUARD>) and a ragged element tail (fold_elements).
+(fold_tile_body) and a ragged element tail (fold_elements).
 """
 import numpy as np
 import pytest

@@ -7,8 +7,8 @@ raw bytes against oracle.oracle.PortReducer, with no tolerance.
 What only a tile of more than one vector per lane can get wrong:
   * fold_tile_full_buf replays slot j at byte0 + voff + j * kBlock * 16: a
     replay that re-read slot 0 is correct at VPT 1;
-  * fold_tile_body<GUARD> replays at off0 + j * kStep and carries valid[j]
-    per slot: in V2's partial tile slot 1 is valid on lanes 0..43 only, in
+  * fold_tile_body (the guarded partial tile) replays at off0 + j * kStep
+    and carries valid[j] per slot: in V2's partial tile slot 1 is valid on lanes 0..43 only, in
     V4's slot 2 on lanes 0..187 and slot 3 nowhere;
   * NS = 16 at VPT 4 takes two load groups (G = 8);
   * the f64, i8 / u8, i32 and i64 instantiations at VPT 2 and 4.
