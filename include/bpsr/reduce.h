@@ -69,7 +69,11 @@ extern "C" {
  *                       stochastic-rounding compression)
  *    additive, still 5: byteps_reduce_cast_plan_decompress_stats (the
  *                       decompress that also reports each segment's sum of
- *                       squares and non-finite count) */
+ *                       squares and non-finite count)
+ *    additive, still 5: byteps_reduce_cast_plan_measure / byteps_reduce_clip_record /
+ *                       byteps_reduce_cast_plan_decompress_scaled
+ *                       (byteps_clip_record: clip by global norm and unscale
+ *                       inside the decompress) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -519,6 +523,58 @@ int byteps_reduce_cast_plan_compress_sr(byteps_reduce_cast_plan* plan, uint32_t 
  *   launches of one plan must not run concurrently. */
 int byteps_reduce_cast_plan_decompress_stats(byteps_reduce_cast_plan* plan, int divisor,
                                              double* stats, void* stream);
+
+/* Clip by global norm and unscale inside the decompress: three launches that
+ * compose on one stream, with no host synchronisation between them.
+ *
+ * _cast_plan_measure: the statistics of _cast_plan_decompress_stats — the same
+ *   rows, bit for bit, of the values the plain decompress WOULD write — from a
+ *   launch that reads the 2-byte side only and never touches `wide`.  `stats`,
+ *   the errors, the partials and the no-concurrency rule are those of
+ *   _cast_plan_decompress_stats.
+ *
+ * byteps_reduce_clip_record: one small kernel (one workgroup, no atomics) over
+ *   `rows`, device memory of 2 * nrows doubles — any concatenation of plans'
+ *   statistics rows {sumsq_s, nonfinite_s}.  All f64 unless said:
+ *     sumsq     = the sum of rows[s].sumsq, in an order nrows alone fixes
+ *     nonfinite = the sum of rows[s].nonfinite, exact
+ *     inv       = (double)*inv_scale, or 1.0 for a null inv_scale
+ *     norm      = sqrt(sumsq) * inv     (the unscaled gradients' L2 norm over
+ *                                        their finite values)
+ *     c         = min(1.0, max_norm / (norm + eps))
+ *     coef      = (float)c
+ *     mult      = (float)(c * inv)
+ *   Non-finite values do not enter the norm: they are counted, and the caller
+ *   skips the step (GradScaler's found_inf).  nrows == 0 gives sumsq 0, coef 1.
+ *   `inv_scale`: device memory, one f32, or null.  `out`: device memory, 32
+ *   bytes, 8-byte aligned.  EARGS before any launch: null rows with nrows > 0,
+ *   nrows < 0, null or misaligned out, max_norm not > 0 or not finite, eps < 0
+ *   (or NaN).
+ *
+ * _cast_plan_decompress_scaled: _cast_plan_decompress with every written value
+ *   v (divided on the 2-byte value, rounded to the wire format, widened)
+ *   multiplied by m = *mult, one rounding per wide dtype:
+ *     FLOAT32            v * m in f32 (subnormals kept)
+ *     BFLOAT16, FLOAT16  the f32 product f32(v) * m, rounded to nearest even
+ *     FLOAT64            (double)v * (double)m, which is exact
+ *   NaN stays NaN and +-inf stays +-inf for a finite positive m; NaN payloads
+ *   are not pinned.  `mult`: device memory, one f32, read by the launch
+ *   (typically &record->mult).  EARGS before any launch: a null plan, divisor
+ *   < 1, a null mult, one that is not 4-byte aligned or that lies inside any
+ *   byte range of the plan's segments.  Any plan, as for _decompress. */
+typedef struct byteps_clip_record {
+  double sumsq;
+  double nonfinite;
+  double norm;
+  float coef;
+  float mult;
+} byteps_clip_record;
+int byteps_reduce_cast_plan_measure(byteps_reduce_cast_plan* plan, int divisor, double* stats,
+                                    void* stream);
+int byteps_reduce_clip_record(const double* rows, int nrows, double max_norm, double eps,
+                              const float* inv_scale, byteps_clip_record* out, void* stream);
+int byteps_reduce_cast_plan_decompress_scaled(byteps_reduce_cast_plan* plan, int divisor,
+                                              const float* mult, void* stream);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

@@ -97,6 +97,18 @@ additions is the implementation's.  Device tensors go through the cast plan's
 hold them, then a small kernel that adds each tensor's partial sums up.  The
 rows land in a float64 device tensor in stream order; nothing synchronises
 with the host.
+
+``decompress_many_into(..., clip_norm=, clip_eps=, unscale=)`` clips by the
+global norm and unscales INSIDE the decompress, in three
+launches on one stream: ``measure_many_with`` takes the statistics of the
+values the decompress would write and writes none of them
+(``byteps_reduce_cast_plan_measure``: the 2-byte side is read, the gradients are
+not touched), ``GpuReducer.clip_record`` turns the rows into the norm and the
+multipliers (:func:`clip_record` below is the definition), and
+``decompress_many_with(..., scale=)`` writes every value times ``mult``
+(``byteps_reduce_cast_plan_decompress_scaled``) — so an unclipped gradient is
+never written and no pass reads the gradients again.  The record is returned;
+for device tensors it stays on the device.
 """
 from __future__ import annotations
 
@@ -160,6 +172,61 @@ def decompress_stats(out):
         x = out.reshape(-1).astype(np.float64)
     fin = np.isfinite(x)
     return float(np.square(x[fin]).sum()), int(np.count_nonzero(~fin))
+
+
+class ClipValues:
+    """A clip record on the host (:func:`clip_record`): ``sumsq``,
+    ``nonfinite``, ``norm`` as float64, ``coef``, ``mult`` as float32;
+    ``found_inf`` is ``nonfinite``."""
+
+    def __init__(self, sumsq, nonfinite, norm, coef, mult):
+        self.sumsq, self.nonfinite, self.norm = sumsq, nonfinite, norm
+        self.coef, self.mult = coef, mult
+        self.found_inf = nonfinite
+
+
+def clip_record(rows, max_norm: float, eps: float = 1e-6, inv_scale=None) -> ClipValues:
+    """The clip record of statistics rows, the pinned definition
+    (``byteps_reduce_clip_record``): ``rows`` is float64 ``[n, 2]`` (or ``2 n``)
+    of ``(sumsq, nonfinite)`` on the host, ``inv_scale`` a number or None (1).
+    The order of the additions of ``sumsq`` is the implementation's."""
+    if not max_norm > 0 or not np.isfinite(max_norm):
+        raise ValueError(f"max_norm {max_norm} is not a finite positive number")
+    if not eps >= 0:
+        raise ValueError(f"eps {eps} < 0")
+    if _is_torch(rows):
+        rows = rows.detach().numpy()
+    r = np.asarray(rows, dtype=np.float64).reshape(-1, 2)
+    sumsq = np.float64(r[:, 0].sum())
+    nonfinite = np.float64(r[:, 1].sum())
+    inv = np.float64(1.0) if inv_scale is None else np.float64(np.float32(inv_scale))
+    norm = np.sqrt(sumsq) * inv
+    with np.errstate(divide="ignore"):    # all-zero gradients, eps 0: +inf, c = 1
+        q = np.float64(max_norm) / (norm + np.float64(eps))
+    c = q if q < 1.0 else np.float64(1.0)
+    return ClipValues(sumsq, nonfinite, norm, np.float32(c), np.float32(c * inv))
+
+
+def _scale_host_(out, m) -> None:
+    """``out *= m`` on the host under the scaled decompress's rounding: the
+    f32 product for f32 and, before the cast back, for the 2-byte types; the
+    f64 product for f64."""
+    import torch
+    t = _as_host_tensor(out)
+    m32 = torch.tensor(float(np.float32(m)), dtype=torch.float32)
+    if t.dtype == torch.float64:
+        t.mul_(m32.to(torch.float64))
+    elif t.dtype == torch.float32:
+        t.mul_(m32)
+    else:
+        t.copy_((t.to(torch.float32) * m32).to(t.dtype))
+
+
+def _empty_like(x):
+    if _is_torch(x):
+        import torch
+        return torch.empty_like(x)
+    return np.empty_like(x)
 
 
 def _check_stats(stats, shape) -> None:
@@ -231,7 +298,7 @@ def _new_plan(wide_dtype: int, pairs, wire_dtype: int = 2):
 
 
 def _cast_many(comp, pairs, compress: bool, divisor: int, plans, extras=None, step=None,
-               stats=None) -> None:
+               stats=None, measure: bool = False, scale=None) -> None:
     """``pairs`` of ``(wide, half)`` tensors or arrays cast by compressor
     ``comp``: the device ones as one plan launch per (device, wide dtype, wire
     dtype), the host ones one by one.  ``extras`` (one per pair, as a cast
@@ -242,9 +309,17 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, extras=None, st
     through the same plan.  ``stats`` (decompress only): float64
     ``[len(pairs), 2]``, row i the statistics of pair i — a device pair's row
     lives on its device, a host pair's on the host; each plan writes its own
-    rows, which are copied to their places in stream order."""
+    rows, which are copied to their places in stream order.  ``measure``
+    (decompress, with ``stats``): the statistics alone, no wide side is
+    written.  ``scale`` (decompress, without ``stats``): every value written is
+    multiplied by it — a 1-element float32 device tensor for device pairs, a
+    number for host pairs."""
     if int(divisor) < 1:
         raise ValueError(f"divisor {divisor} < 1")
+    if measure and (compress or stats is None):
+        raise ValueError("measure is a decompress with stats")
+    if scale is not None and (compress or stats is not None):
+        raise ValueError("scale is a decompress without stats")
     if stats is not None:
         _check_stats(stats, (len(pairs), 2))
     groups: dict = {}
@@ -257,14 +332,21 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, extras=None, st
             else:
                 if stats is not None and _on_device(stats):
                     raise ValueError(f"stats is on {stats.device}, tensor {i} on the host")
-                comp.decompress_into(wide, half, divisor,
+                if scale is not None and _is_torch(scale) and _on_device(scale):
+                    raise ValueError(f"scale is on {scale.device}, tensor {i} on the host")
+                comp.decompress_into(_empty_like(wide) if measure else wide, half, divisor,
                                      **({} if stats is None else {"stats": stats[i]}))
+                if scale is not None:
+                    _scale_host_(wide, scale.item() if _is_torch(scale) else scale)
             continue
         comp._check_segment(half, wide, extra)
         seg = (wide.reshape(-1), half.reshape(-1)) + (
             () if extra is None else (extra.reshape(-1) if _is_torch(extra) else extra,))
         if stats is not None and (not _on_device(stats) or stats.device != wide.device):
             raise ValueError(f"stats is on {getattr(stats, 'device', 'the host')}, "
+                             f"tensor {i} on {wide.device}")
+        if scale is not None and (not _on_device(scale) or scale.device != wide.device):
+            raise ValueError(f"scale is on {getattr(scale, 'device', 'the host')}, "
                              f"tensor {i} on {wide.device}")
         key = (wide.device, wide.dtype, comp.wire_torch_dtype())
         groups.setdefault(key, []).append(seg)
@@ -282,13 +364,16 @@ def _cast_many(comp, pairs, compress: bool, divisor: int, plans, extras=None, st
                 if compress:
                     plan.compress(stream=stream, step=step)
                 elif stats is None:
-                    plan.decompress(int(divisor), stream=stream)
+                    plan.decompress(int(divisor), stream=stream, scale=scale)
                 else:
                     idx = rows[(device, dtype, wire)]
                     whole = idx == list(range(len(pairs))) and stats.is_contiguous()
                     buf = stats.reshape(-1) if whole else \
                         torch.empty(2 * len(idx), dtype=torch.float64, device=device)
-                    plan.decompress(int(divisor), stream=stream, stats=buf)
+                    if measure:
+                        plan.measure(int(divisor), stream=stream, stats=buf)
+                    else:
+                        plan.decompress(int(divisor), stream=stream, stats=buf)
                     if not whole:         # the plan's rows to the caller's order, run by run
                         got, a = buf.view(-1, 2), 0
                         while a < len(idx):
@@ -465,13 +550,76 @@ class _CastCompressor(Compressor):
 
     @classmethod
     def decompress_many_into(cls, outs, compressed, divisor: int = 1,
-                             plans: CastPlanCache | None = None, stats=None):
+                             plans: CastPlanCache | None = None, stats=None,
+                             clip_norm=None, clip_eps: float = 1e-6, unscale=None):
         """``decompress_into(outs[i], compressed[i], divisor)`` for every i,
         the device tensors as one cast-plan launch per (device, dtype);
         returns ``outs``.  ``stats``: a float64 tensor or array of shape
         ``(len(outs), 2)`` where the outputs live; row i receives
-        ``decompress_stats(outs[i])``."""
-        return cls.decompress_many_with(outs, compressed, None, divisor, plans, stats)
+        ``decompress_stats(outs[i])``.
+
+        With ``clip_norm`` the outputs are clipped to that global L2 norm and
+        multiplied by ``unscale`` (a number, or a 1-element float32 device
+        tensor: GradScaler's inverse scale) inside the decompress: measure,
+        ``clip_record(rows, clip_norm, clip_eps, unscale)``, then the decompress
+        times the record's ``mult``, one rounding an element.  The record is
+        returned (a ``reducer.ClipRecord`` on the outputs' device — they share
+        one — or :class:`ClipValues` for host outputs); ``stats`` then
+        receives the statistics BEFORE the clip: those of the values a plain
+        decompress would have written."""
+        if clip_norm is None:
+            if unscale is not None:
+                raise ValueError("unscale goes with clip_norm")
+            return cls.decompress_many_with(outs, compressed, None, divisor, plans, stats)
+        return cls._decompress_many_clipped(outs, compressed, None, divisor, plans, stats,
+                                            clip_norm, clip_eps, unscale)
+
+    @classmethod
+    def _decompress_many_clipped(cls, outs, compressed, extras, divisor, plans, stats, clip_norm,
+                                 clip_eps, unscale):
+        """measure, clip record, scaled decompress over the same cached plans;
+        returns the record."""
+        n = len(outs)
+        if len(compressed) != n:
+            raise ValueError("decompress_many_into: as many outputs as compressed tensors")
+        if stats is not None:
+            _check_stats(stats, (n, 2))
+        if not clip_norm > 0 or not np.isfinite(clip_norm):
+            raise ValueError(f"clip_norm {clip_norm} is not a finite positive number")
+        if not clip_eps >= 0:
+            raise ValueError(f"clip_eps {clip_eps} < 0")
+        devices = {o.device if _on_device(o) else None for o in outs}
+        if len(devices) > 1:
+            raise ValueError("clip_norm: the outputs live in one place, a device or the host")
+        if devices in (set(), {None}):
+            if _is_torch(unscale) and _on_device(unscale):
+                raise ValueError(f"unscale is on {unscale.device}, the outputs on the host")
+            rows = stats if stats is not None else np.empty((n, 2), dtype=np.float64)
+            cls.measure_many_with(outs, compressed, extras, divisor, plans, rows)
+            rec = clip_record(rows, clip_norm, clip_eps,
+                              unscale.item() if _is_torch(unscale) else unscale)
+            cls.decompress_many_with(outs, compressed, extras, divisor, plans, scale=rec.mult)
+            return rec
+        import torch
+        from .torch_ops import _red
+        device = next(iter(devices))
+        cache = CastPlanCache(4) if plans is None else plans
+        try:
+            whole = stats is not None and stats.is_contiguous()
+            rows = stats if whole else torch.empty((n, 2), dtype=torch.float64, device=device)
+            inv = unscale
+            if inv is not None and not _is_torch(inv):
+                inv = torch.tensor([float(inv)], dtype=torch.float32, device=device)
+            cls.measure_many_with(outs, compressed, extras, divisor, cache, rows)
+            if stats is not None and not whole:
+                stats.copy_(rows)
+            with torch.cuda.device(device):
+                rec = _red().clip_record(rows, clip_norm, clip_eps, inv)
+            cls.decompress_many_with(outs, compressed, extras, divisor, cache, scale=rec.mult)
+        finally:
+            if plans is None:
+                cache.close()             # waits for the launches
+        return rec
 
     # The forms that take the scheme's per-tensor operand — an error-feedback
     # residual, a stochastic-rounding SrKey, None for the plain cast — as cast
@@ -504,16 +652,34 @@ class _CastCompressor(Compressor):
 
     @classmethod
     def decompress_many_with(cls, outs, compressed, extras, divisor: int = 1,
-                             plans: CastPlanCache | None = None, stats=None):
+                             plans: CastPlanCache | None = None, stats=None, scale=None):
         """``decompress_many_into``; ``extras`` (those of the compress over the
         same tensors, or None) only name the plan: every scheme's decompress is
         the plain one, so one cached plan serves both directions, and residuals
-        are not touched."""
+        are not touched.  ``scale``: every value written is multiplied by it
+        (a 1-element float32 device tensor for device outputs, a number for
+        host ones), rounded once to the output's dtype; it excludes
+        ``stats``."""
         if len(outs) != len(compressed):
             raise ValueError("decompress_many_into: as many outputs as compressed tensors")
         _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans, extras=extras,
-                   stats=stats)
+                   stats=stats, scale=scale)
         return outs
+
+    @classmethod
+    def measure_many_with(cls, outs, compressed, extras, divisor: int = 1,
+                          plans: CastPlanCache | None = None, stats=None):
+        """The statistics ``decompress_many_with(..., stats=stats)`` would
+        report, through the same cached plans, WITHOUT the decompress: nothing
+        is written to ``outs`` (device outputs: the 2-byte side alone is read;
+        host outputs: the definition on a scratch copy).  Returns ``stats``."""
+        if len(outs) != len(compressed):
+            raise ValueError("measure_many_with: as many outputs as compressed tensors")
+        if stats is None:
+            raise ValueError("measure_many_with needs stats")
+        _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans, extras=extras,
+                   stats=stats, measure=True)
+        return stats
 
 
 class FP16Compressor(_CastCompressor):
@@ -632,14 +798,19 @@ class _ErrorFeedback:
 
     @classmethod
     def decompress_many_into(cls, outs, compressed, divisor: int = 1,
-                             plans: CastPlanCache | None = None, residuals=None, stats=None):
-        """The inherited decompress, ``stats`` included.  ``residuals`` (those given to
+                             plans: CastPlanCache | None = None, residuals=None, stats=None,
+                             clip_norm=None, clip_eps: float = 1e-6, unscale=None):
+        """The inherited decompress, ``stats`` and ``clip_norm`` included.  ``residuals`` (those given to
         ``compress_many_ef_into`` over the same tensors) only names the plan:
         the error-feedback plan's own decompress is the plain one, so one
         cached plan serves both directions; the residuals are not touched."""
-        return cls.decompress_many_with(outs, compressed,
-                                        None if residuals is None else list(residuals),
-                                        divisor, plans, stats)
+        extras = None if residuals is None else list(residuals)
+        if clip_norm is None:
+            if unscale is not None:
+                raise ValueError("unscale goes with clip_norm")
+            return cls.decompress_many_with(outs, compressed, extras, divisor, plans, stats)
+        return cls._decompress_many_clipped(outs, compressed, extras, divisor, plans, stats,
+                                            clip_norm, clip_eps, unscale)
 
 
 class FP16EFCompressor(_ErrorFeedback, FP16Compressor):
@@ -736,13 +907,19 @@ class _StochasticRounding:
 
     @classmethod
     def decompress_many_into(cls, outs, compressed, divisor: int = 1,
-                             plans: CastPlanCache | None = None, keys=None, stats=None):
-        """The inherited decompress, ``stats`` included.  ``keys`` (those given to
+                             plans: CastPlanCache | None = None, keys=None, stats=None,
+                             clip_norm=None, clip_eps: float = 1e-6, unscale=None):
+        """The inherited decompress, ``stats`` and ``clip_norm`` included.  ``keys`` (those given to
         ``compress_many_sr_into`` over the same tensors) only names the plan:
         the stochastic-rounding plan's own decompress is the plain one, so one
         cached plan serves both directions."""
-        return cls.decompress_many_with(outs, compressed, None if keys is None else _sr_keys(keys),
-                                        divisor, plans, stats)
+        extras = None if keys is None else _sr_keys(keys)
+        if clip_norm is None:
+            if unscale is not None:
+                raise ValueError("unscale goes with clip_norm")
+            return cls.decompress_many_with(outs, compressed, extras, divisor, plans, stats)
+        return cls._decompress_many_clipped(outs, compressed, extras, divisor, plans, stats,
+                                            clip_norm, clip_eps, unscale)
 
 
 class FP16SRCompressor(_StochasticRounding, FP16Compressor):
@@ -767,4 +944,4 @@ class Compression:
 
 __all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
            "FP16EFCompressor", "BF16EFCompressor", "FP16SRCompressor", "BF16SRCompressor",
-           "Compression", "CastPlanCache", "decompress_stats"]
+           "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]

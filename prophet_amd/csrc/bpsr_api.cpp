@@ -5,6 +5,7 @@
 // status plus a thread-local message.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -452,14 +453,17 @@ struct CastWire {
   decltype(launch_cast_plan_ef)* plan_ef;
   decltype(launch_cast_plan_sr)* plan_sr;
   decltype(launch_cast_plan_stats)* plan_stats;
+  decltype(launch_cast_plan_measure)* plan_measure;
+  decltype(launch_cast_plan_scaled)* plan_scaled;
 };
 static const CastWire kCastWires[] = {
     {kFloat16, launch_compress_fp16, launch_decompress_fp16, launch_compress_ef,
      launch_compress_sr, launch_cast_plan, launch_cast_plan_ef, launch_cast_plan_sr,
-     launch_cast_plan_stats},
+     launch_cast_plan_stats, launch_cast_plan_measure, launch_cast_plan_scaled},
     {kBFloat16, launch_compress_bf16, launch_decompress_bf16, launch_compress_ef_bf16,
      launch_compress_sr_bf16, launch_cast_plan_bf16, launch_cast_plan_ef_bf16,
-     launch_cast_plan_sr_bf16, launch_cast_plan_stats_bf16},
+     launch_cast_plan_sr_bf16, launch_cast_plan_stats_bf16, launch_cast_plan_measure_bf16,
+     launch_cast_plan_scaled_bf16},
 };
 
 // The row of a wire format; null, with the dtype error set, for any other.
@@ -587,9 +591,11 @@ static int cast_plan_create(CastScheme scheme, const D* segs, int nsegs, int wid
 // The plan's one launch, by direction and scheme (validated by the callers;
 // the plan has records): a compress is its scheme's — `step` for stochastic
 // rounding — a decompress the plain one for every scheme, with the statistics'
-// partials where `part` is not null.
+// partials where `part` is not null — without the stores where `measure` is
+// set — and times *mult where `mult` is not null.
 static int cast_plan_launch(byteps_reduce_cast_plan* p, bool compress, int divisor, uint32_t step,
-                            void* part, void* stream) {
+                            void* part, void* stream, bool measure = false,
+                            const float* mult = nullptr) {
   const CastRec* table = static_cast<const CastRec*>(p->dev[p->kTable]);
   void* side = p->dev[p->kSide];
   const uint32_t n = p->ti.records;
@@ -598,7 +604,11 @@ static int cast_plan_launch(byteps_reduce_cast_plan* p, bool compress, int divis
   const Tuning tu = tuning();
   hipStream_t s = to_stream(stream);
   hipError_t e;
-  if (!compress)
+  if (!compress && mult)
+    e = p->wire->plan_scaled(table, n, p->dtype, divisor, u, wide_bytes, mult, tu, s);
+  else if (!compress && measure)
+    e = p->wire->plan_measure(table, n, p->dtype, divisor, u, part, tu, s);
+  else if (!compress)
     e = part ? p->wire->plan_stats(table, n, p->dtype, divisor, u, wide_bytes, part, tu, s)
              : p->wire->plan(false, table, n, p->dtype, divisor, u, wide_bytes, tu, s);
   else if (p->scheme == kCastEf)  // 2 + 4 bytes written an element
@@ -707,8 +717,10 @@ int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* p, int divisor, 
   return cast_plan_launch(p, false, divisor, 0, nullptr, stream);
 }
 
-int byteps_reduce_cast_plan_decompress_stats(byteps_reduce_cast_plan* p, int divisor,
-                                             double* stats, void* stream) {
+// _decompress_stats and _measure: the checks, the partials, the decompress
+// with or without its stores, the finish.
+static int cast_plan_stats(byteps_reduce_cast_plan* p, int divisor, double* stats, void* stream,
+                           bool measure) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
   if (p->nsegs <= 0) return BYTEPS_REDUCE_OK;  // no segment: no row, nothing to write
@@ -727,13 +739,51 @@ int byteps_reduce_cast_plan_decompress_stats(byteps_reduce_cast_plan* p, int div
       hipError_t e = hipMalloc(&part, (size_t)p->ti.records * kStatPartBytes);
       if (e != hipSuccess) return hip_fail(e, "cast plan statistics partials");
     }
-    const int rc = cast_plan_launch(p, false, divisor, 0, part, stream);
+    const int rc = cast_plan_launch(p, false, divisor, 0, part, stream, measure);
     if (rc) return rc;
   }
   const uint32_t* seg = static_cast<const uint32_t*>(p->dev[p->kSeg]);
   hipError_t e = launch_cast_stats_finish(seg, seg + p->nsegs + 1, part, stats, p->nsegs,
                                           to_stream(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "cast plan statistics kernel launch");
+}
+
+int byteps_reduce_cast_plan_decompress_stats(byteps_reduce_cast_plan* p, int divisor,
+                                             double* stats, void* stream) {
+  return cast_plan_stats(p, divisor, stats, stream, false);
+}
+
+int byteps_reduce_cast_plan_measure(byteps_reduce_cast_plan* p, int divisor, double* stats,
+                                    void* stream) {
+  return cast_plan_stats(p, divisor, stats, stream, true);
+}
+
+int byteps_reduce_clip_record(const double* rows, int nrows, double max_norm, double eps,
+                              const float* inv_scale, byteps_clip_record* out, void* stream) {
+  if (nrows < 0) return fail(BYTEPS_REDUCE_EARGS, "nrows %d < 0", nrows);
+  if (!rows && nrows > 0) return fail(BYTEPS_REDUCE_EARGS, "null rows pointer");
+  if (!out) return fail(BYTEPS_REDUCE_EARGS, "null clip record pointer");
+  if ((uintptr_t)out % 8) return fail(BYTEPS_REDUCE_EARGS, "clip record is not 8-byte aligned");
+  if (!(max_norm > 0.0) || !std::isfinite(max_norm))
+    return fail(BYTEPS_REDUCE_EARGS, "max_norm %g is not a finite positive number", max_norm);
+  if (!(eps >= 0.0)) return fail(BYTEPS_REDUCE_EARGS, "eps %g < 0", eps);
+  const hipError_t e =
+      launch_clip_record(rows, nrows, max_norm, eps, inv_scale, out, to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "clip record kernel launch");
+}
+
+int byteps_reduce_cast_plan_decompress_scaled(byteps_reduce_cast_plan* p, int divisor,
+                                              const float* mult, void* stream) {
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  if (!mult) return fail(BYTEPS_REDUCE_EARGS, "null mult pointer");
+  const uintptr_t mb = (uintptr_t)mult;
+  if (mb % sizeof(float)) return fail(BYTEPS_REDUCE_EARGS, "mult is not 4-byte aligned");
+  for (const auto& r : p->ranges)
+    if (mb < r.second && r.first < mb + sizeof(float))
+      return fail(BYTEPS_REDUCE_EARGS, "mult lies inside a segment of the plan");
+  if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
+  return cast_plan_launch(p, false, divisor, 0, nullptr, stream, false, mult);
 }
 
 int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* p) {

@@ -23,6 +23,9 @@ namespace bpsr {
 // Wide-side element: its 16-B vectors per unit, and the exact steps to and
 // from f32 bits.  get/put address element e (0..7) of a unit's vectors.
 // to_f64: the element's value, exactly (the decompress statistics).
+// scale: the element times an f32 multiplier, rounded once to the element's
+// type (the scaled decompress): the f32 product for f32 and,
+// before from_f32's own rounding, for the 2-byte types; the f64 product for f64.
 template <int DT>
 struct Wide;
 
@@ -33,6 +36,7 @@ struct Wide<kFloat32> {
   __device__ static uint32_t to_f32(E x) { return x; }
   __device__ static double to_f64(E x) { return (double)bitcast<float>(x); }
   __device__ static E from_f32(float f) { return bitcast<uint32_t>(f); }
+  __device__ static E scale(E v, float m) { return from_f32(bitcast<float>(v) * m); }
   __device__ static E get(const vec16* x, int e) { return x[e >> 2].w[e & 3]; }
   __device__ static void put(vec16* x, int e, E v) { x[e >> 2].w[e & 3] = v; }
 };
@@ -45,6 +49,10 @@ struct Wide<kFloat64> {
   __device__ static uint32_t to_f32(E x) { return bitcast<uint32_t>((float)bitcast<double>(x)); }
   __device__ static double to_f64(E x) { return bitcast<double>(x); }
   __device__ static E from_f32(float f) { return bitcast<uint64_t>((double)f); }
+  // exact: v has at most 11 significant bits here, m has 24
+  __device__ static E scale(E v, float m) {
+    return bitcast<uint64_t>(bitcast<double>(v) * (double)m);
+  }
   __device__ static E get(const vec16* x, int e) {
     return ((uint64_t)x[e >> 1].w[(e & 1) * 2 + 1] << 32) | x[e >> 1].w[(e & 1) * 2];
   }
@@ -61,6 +69,7 @@ struct Wide<kBFloat16> {
   __device__ static uint32_t to_f32(E x) { return (uint32_t)x << 16; }  // exact
   __device__ static double to_f64(E x) { return (double)bitcast<float>(to_f32(x)); }
   __device__ static E from_f32(float f) { return (E)f32_to_bf16_rne(bitcast<uint32_t>(f)); }
+  __device__ static E scale(E v, float m) { return from_f32(bitcast<float>(to_f32(v)) * m); }
   __device__ static E get(const vec16* x, int e) {
     return (E)(x[0].w[e >> 1] >> ((e & 1) * 16));
   }
@@ -79,6 +88,7 @@ struct Wide<kFloat16> {
   __device__ static uint32_t to_f32(E x) { return bitcast<uint32_t>((float)bitcast<_Float16>(x)); }
   __device__ static double to_f64(E x) { return (double)(float)bitcast<_Float16>(x); }
   __device__ static E from_f32(float f) { return (E)f2h_bits(bitcast<uint32_t>(f)); }
+  __device__ static E scale(E v, float m) { return from_f32(bitcast<float>(to_f32(v)) * m); }
   __device__ static E get(const vec16* x, int e) {
     return (E)(x[0].w[e >> 1] >> ((e & 1) * 16));
   }
@@ -136,11 +146,19 @@ __device__ __forceinline__ typename W::E decompress_elem(uint16_t h, bool div, f
 // count of the others.  A compile-time choice: the tiles below take the
 // accumulator's type, and under StatNone — every compress, every plain
 // decompress — add() is nothing and the code is what it was without it.
+// Two more compile-time answers of an accumulator: kStore —
+// whether the decompress stores what it computed (StatMeasure: no, the
+// statistics of a decompress that writes nothing, each element still
+// classified by the lane that would have stored it) — and kScale — whether
+// the element is multiplied (W::scale) by the accumulator's `m` on its way out
+// (StatScale, the scaled decompress).
 struct StatNone {
+  static constexpr bool kStore = true, kScale = false;
   template <class W>
   __device__ __forceinline__ void add(typename W::E) {}
 };
 struct StatAcc {
+  static constexpr bool kStore = true, kScale = false;
   double sumsq = 0.0;
   uint32_t nonfinite = 0;
   template <class W>
@@ -151,11 +169,24 @@ struct StatAcc {
     nonfinite += fin ? 0u : 1u;
   }
 };
+struct StatMeasure : StatAcc {
+  static constexpr bool kStore = false;
+};
+struct StatScale {
+  static constexpr bool kStore = true, kScale = true;
+  float m;
+  template <class W>
+  __device__ __forceinline__ void add(typename W::E) {}
+};
+// the accumulator's type behind the tiles' forwarding reference
+template <class A>
+using AccOf = std::remove_cv_t<std::remove_reference_t<A>>;
 
 // decompress_elem, the element shown to the accumulator on its way out
 template <class W, class N, class A>
 __device__ __forceinline__ typename W::E decompress_elem(uint16_t h, bool div, float fd, A& acc) {
-  const typename W::E v = decompress_elem<W, N>(h, div, fd);
+  typename W::E v = decompress_elem<W, N>(h, div, fd);
+  if constexpr (A::kScale) v = W::scale(v, acc.m);
   acc.template add<W>(v);
   return v;
 }
@@ -374,8 +405,9 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
           for (int e = 0; e < EPV; ++e)  // e < EPV: all within the one vector
             W::put(&o, e,
                    decompress_elem<W, N>((uint16_t)(d[e >> 1] >> ((e & 1) * 16)), div, fd, acc));
-          __builtin_amdgcn_raw_buffer_store_b128(
-              bitcast<u4>(o), rd, ((j * kBlock + wave0) * KV + g) * 16, 0, kStAux);
+          if constexpr (AccOf<A>::kStore)
+            __builtin_amdgcn_raw_buffer_store_b128(
+                bitcast<u4>(o), rd, ((j * kBlock + wave0) * KV + g) * 16, 0, kStAux);
         }
       }
       return;
@@ -384,10 +416,12 @@ __device__ __forceinline__ void cast_tile_full(const unsigned char* src, unsigne
     for (int j = 0; j < U; ++j) {
       vec16 o[KV];
       decompress_unit<W, N>(h[j], div, fd, o, acc);
+      if constexpr (AccOf<A>::kStore) {
 #pragma unroll
-      for (int v = 0; v < KV; ++v)
-        __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(o[v]), rd,
-                                               ((j * kBlock + lane) * KV + v) * 16, 0, kStAux);
+        for (int v = 0; v < KV; ++v)
+          __builtin_amdgcn_raw_buffer_store_b128(bitcast<u4>(o[v]), rd,
+                                                 ((j * kBlock + lane) * KV + v) * 16, 0, kStAux);
+      }
     }
   }
 }
@@ -427,8 +461,10 @@ __device__ __forceinline__ void cast_tile_guarded(const unsigned char* src, unsi
     } else {
       vec16 o[KV];
       decompress_unit<W, N>(ld16<true>(src + u * 16), div, fd, o, acc);
+      if constexpr (AccOf<A>::kStore) {
 #pragma unroll
-      for (int v = 0; v < KV; ++v) st16<true>(dst + (u * KV + v) * 16, o[v]);
+        for (int v = 0; v < KV; ++v) st16<true>(dst + (u * KV + v) * 16, o[v]);
+      }
     }
   }
 }
@@ -449,9 +485,11 @@ __device__ __forceinline__ void cast_elements(const CastArgs& a, const typename 
       st_e<uint16_t>(a.dst + e * 2, S::elem(st, ld_e<E>(a.src + e * sizeof(E), al), e, al), al);
     else if constexpr (COMPRESS)
       st_e<uint16_t>(a.dst + e * 2, compress_elem<W, N>(ld_e<E>(a.src + e * sizeof(E), al)), al);
-    else
+    else if constexpr (AccOf<A>::kStore)
       st_e<E>(a.dst + e * sizeof(E),
               decompress_elem<W, N>(ld_e<uint16_t>(a.src + e * 2, al), div, fd, acc), al);
+    else
+      (void)decompress_elem<W, N>(ld_e<uint16_t>(a.src + e * 2, al), div, fd, acc);
   }
 }
 

@@ -5,7 +5,9 @@
 // bpsr_k_cast_plan_bf16.hip; error feedback: bpsr_k_cast_ef*.hip; stochastic
 // rounding: bpsr_k_cast_sr*.hip).  What a plan is and how a record is read:
 // bpsr_k_cast_plan.hip.  The decompress has a STATS variant that also reports
-// each segment's sum of squares and non-finite count.
+// each segment's sum of squares and non-finite count, a
+// MEASURE variant that reports the same and stores nothing, and a SCALED
+// variant that multiplies every value it writes.
 #pragma once
 
 #include "bpsr_cast_impl.h"
@@ -27,12 +29,46 @@ struct PlanStats {
   typename S::Plan plan;
   StatPart* part;
 };
+// The SCALED variant's: the plan and the device-resident multiplier.
+template <class S>
+struct PlanScaled {
+  typename S::Plan plan;
+  const float* mult;
+};
 template <class P>
 __device__ __forceinline__ const P& plan_of(const P& a) { return a; }
 template <class S>
 __device__ __forceinline__ const typename S::Plan& plan_of(const PlanStats<S>& a) {
   return a.plan;
 }
+template <class S>
+__device__ __forceinline__ const typename S::Plan& plan_of(const PlanScaled<S>& a) {
+  return a.plan;
+}
+
+// The decompress's compile-time variants: its kernel argument and the
+// accumulator the tiles take (bpsr_cast_impl.h).
+enum { kPlanPlain = 0, kPlanStats = 1, kPlanMeasure = 2, kPlanScaled = 3 };
+template <class S, int MODE>
+struct PlanMode {
+  using Arg = typename S::Plan;
+  using Acc = StatNone;
+};
+template <class S>
+struct PlanMode<S, kPlanStats> {
+  using Arg = PlanStats<S>;
+  using Acc = StatAcc;
+};
+template <class S>
+struct PlanMode<S, kPlanMeasure> {
+  using Arg = PlanStats<S>;
+  using Acc = StatMeasure;
+};
+template <class S>
+struct PlanMode<S, kPlanScaled> {
+  using Arg = PlanScaled<S>;
+  using Acc = StatScale;
+};
 
 // Lane l's 64 bits from lane `from / 4`: the two halves through ds_bpermute.
 __device__ __forceinline__ uint64_t stat_from_lane(uint64_t b, int from) {
@@ -59,17 +95,23 @@ __device__ __forceinline__ void stat_wave_sum(double& x, C& n) {
 // STATS (decompress only): every lane also squares and classifies the
 // elements it writes (StatAcc), each wave adds its 64 lanes up and one lane
 // stores the wave's partial — no LDS, no barrier, no atomics.  A template
-// parameter: with STATS false the argument is S::Plan itself and the
-// accumulator is StatNone, which is no code.
-template <class S, class W, bool COMPRESS, int U, int POL, bool STATS = false>
-__global__ __launch_bounds__(kBlock) void cast_plan_kernel(
-    std::conditional_t<STATS, PlanStats<S>, typename S::Plan> arg) {
-  static_assert(!(STATS && COMPRESS), "statistics are the decompress's");
+// parameter: under kPlanPlain the argument is S::Plan itself and the
+// accumulator is StatNone, which is no code.  MEASURE is STATS without the
+// stores to the wide side: the same lanes classify the same values, so the
+// partials, and with them a plan's rows, are STATS's bit for bit.  SCALED
+// reads its multiplier once, a wave-uniform (scalar) load beside the record's,
+// and the tiles multiply every element on its way out (W::scale).
+template <class S, class W, bool COMPRESS, int U, int POL, int MODE = kPlanPlain>
+__global__ __launch_bounds__(kBlock) void cast_plan_kernel(typename PlanMode<S, MODE>::Arg arg) {
+  constexpr bool VARIANT = MODE != kPlanPlain;
+  constexpr bool STATS = MODE == kPlanStats || MODE == kPlanMeasure;
+  static_assert(!(VARIANT && COMPRESS), "the variants are the decompress's");
   const typename S::Plan& p = plan_of(arg);
   // (the plain variant makes the calls below without it, as before: even an
   // empty accumulator passed by reference changed the compiler's choices in
   // the error-feedback and stochastic compresses: a 32-bit for a 64-bit compare)
-  [[maybe_unused]] std::conditional_t<STATS, StatAcc, StatNone> acc;
+  [[maybe_unused]] typename PlanMode<S, MODE>::Acc acc;
+  if constexpr (MODE == kPlanScaled) acc.m = *arg.mult;
   // grid == nrecords (launch_plan_s): no bounds test in front of the record
   // load, nor of the scheme's load from its parallel array (S::state), which
   // would put a second scalar round trip before them
@@ -104,12 +146,12 @@ __global__ __launch_bounds__(kBlock) void cast_plan_kernel(
   const bool div = !COMPRESS && divisor > 1;
   const float fd = (float)divisor;
   if (kind == kTileFull) {
-    if constexpr (STATS)
+    if constexpr (VARIANT)
       cast_tile_full<S, W, COMPRESS, U, POL>(src, dst, st, div, fd, threadIdx.x, acc);
     else
       cast_tile_full<S, W, COMPRESS, U, POL>(src, dst, st, div, fd, threadIdx.x);
   } else if (kind == kTilePartial) {
-    if constexpr (STATS)
+    if constexpr (VARIANT)
       cast_tile_guarded<S, W, COMPRESS, U>(src, dst, st, 0, count, div, fd, threadIdx.x, acc);
     else
       cast_tile_guarded<S, W, COMPRESS, U>(src, dst, st, 0, count, div, fd, threadIdx.x);
@@ -122,8 +164,10 @@ __global__ __launch_bounds__(kBlock) void cast_plan_kernel(
     a.grid = 1;
     a.divisor = divisor;
     a.aligned = (int)aligned;
-    if constexpr (STATS) cast_elements<S, W, COMPRESS>(a, st, div, fd, threadIdx.x, kBlock, acc);
-    else cast_elements<S, W, COMPRESS>(a, st, div, fd, threadIdx.x, kBlock);
+    if constexpr (VARIANT)
+      cast_elements<S, W, COMPRESS>(a, st, div, fd, threadIdx.x, kBlock, acc);
+    else
+      cast_elements<S, W, COMPRESS>(a, st, div, fd, threadIdx.x, kBlock);
   }
   if constexpr (STATS) {
     // every lane is back here, whatever it wrote (a lane that wrote nothing
@@ -171,22 +215,31 @@ static hipError_t launch_plan(bool compress, const CastRec* table, uint32_t nrec
   }
 }
 
-// The plain plan's decompress with statistics: the STATS variant, partials to
-// `part` (kBlock / 64 per record).
-template <class N, int WIDE16>
-static hipError_t launch_plan_stats(const CastRec* table, uint32_t nrecords, int wide_dtype,
-                                    int divisor, int u, uint64_t out_bytes, StatPart* part,
-                                    const Tuning& tu, hipStream_t s) {
+// A variant of the plain plan's decompress under store policy `pol`; `p`: its
+// kernel argument.
+template <class N, int WIDE16, int MODE>
+static hipError_t launch_plan_variant(const typename PlanMode<CastPlain<N>, MODE>::Arg& p,
+                                      int wide_dtype, int u, int pol, const Tuning& tu,
+                                      hipStream_t s) {
   using S = CastPlain<N>;
   if (u != 1 && u != 2 && u != 4) return hipErrorInvalidValue;
-  const PlanStats<S> p{{table, nrecords, divisor}, part};
   auto go = [&](auto w) {
     using W = decltype(w);
-    return cast_dispatch(u, cast_store_pol(tu, out_bytes), [&](auto U, auto POL) {
+    auto launch = [&](auto U, auto POL) {
       return launch_cast_kernel<
-          cast_plan_kernel<S, W, false, decltype(U)::value, decltype(POL)::value, true>>(
-          p, nrecords, tu.occ_min_tiles_batch, tu, s);
-    });
+          cast_plan_kernel<S, W, false, decltype(U)::value, decltype(POL)::value, MODE>>(
+          p, p.plan.nrecords, tu.occ_min_tiles_batch, tu, s);
+    };
+    if constexpr (MODE == kPlanMeasure) {  // no stores: the nt instantiation alone
+      const std::integral_constant<int, kPolNt> nt;
+      switch (u) {
+        case 1: return launch(std::integral_constant<int, 1>{}, nt);
+        case 2: return launch(std::integral_constant<int, 2>{}, nt);
+        default: return launch(std::integral_constant<int, 4>{}, nt);
+      }
+    } else {
+      return cast_dispatch(u, pol, launch);
+    }
   };
   switch (wide_dtype) {
     case kFloat32: return go(Wide<kFloat32>{});
@@ -194,6 +247,37 @@ static hipError_t launch_plan_stats(const CastRec* table, uint32_t nrecords, int
     case WIDE16: return go(Wide<WIDE16>{});
     default: return hipErrorInvalidValue;
   }
+}
+
+// The plain plan's decompress with statistics: the STATS variant, partials to
+// `part` (kBlock / 64 per record).
+template <class N, int WIDE16>
+static hipError_t launch_plan_stats(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                    int divisor, int u, uint64_t out_bytes, StatPart* part,
+                                    const Tuning& tu, hipStream_t s) {
+  return launch_plan_variant<N, WIDE16, kPlanStats>({{table, nrecords, divisor}, part},
+                                                    wide_dtype, u, cast_store_pol(tu, out_bytes),
+                                                    tu, s);
+}
+
+// The statistics alone: the MEASURE variant.  Nothing is stored to the wide
+// side, so the store policy has no meaning: one instantiation.
+template <class N, int WIDE16>
+static hipError_t launch_plan_measure(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                      int divisor, int u, StatPart* part, const Tuning& tu,
+                                      hipStream_t s) {
+  return launch_plan_variant<N, WIDE16, kPlanMeasure>({{table, nrecords, divisor}, part},
+                                                      wide_dtype, u, kPolNt, tu, s);
+}
+
+// The decompress times `*mult` (device memory): the SCALED variant.
+template <class N, int WIDE16>
+static hipError_t launch_plan_scaled(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                     int divisor, int u, uint64_t out_bytes, const float* mult,
+                                     const Tuning& tu, hipStream_t s) {
+  return launch_plan_variant<N, WIDE16, kPlanScaled>({{table, nrecords, divisor}, mult},
+                                                     wide_dtype, u, cast_store_pol(tu, out_bytes),
+                                                     tu, s);
 }
 
 }  // namespace bpsr

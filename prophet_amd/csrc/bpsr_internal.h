@@ -452,6 +452,25 @@ hipError_t launch_cast_plan_stats_bf16(const CastRec* table, uint32_t nrecords, 
 // the records seg_recs[seg_begin[s] .. seg_begin[s + 1]).  Every row is written.
 hipError_t launch_cast_stats_finish(const uint32_t* seg_begin, const uint32_t* seg_recs,
                                     const void* part, double* stats, int nsegs, hipStream_t s);
+// The statistics of a decompress that writes nothing (MEASURE, DESIGN.md
+// §11.8): the same partials, the wide side not touched; and the decompress
+// whose every written value is multiplied by *mult (SCALED; device memory).
+hipError_t launch_cast_plan_measure(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                    int divisor, int u, void* part, const Tuning& tu,
+                                    hipStream_t s);
+hipError_t launch_cast_plan_measure_bf16(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                         int divisor, int u, void* part, const Tuning& tu,
+                                         hipStream_t s);
+hipError_t launch_cast_plan_scaled(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                   int divisor, int u, uint64_t out_bytes, const float* mult,
+                                   const Tuning& tu, hipStream_t s);
+hipError_t launch_cast_plan_scaled_bf16(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                        int divisor, int u, uint64_t out_bytes,
+                                        const float* mult, const Tuning& tu, hipStream_t s);
+// The clip record of `nrows` statistics rows (byteps_reduce_clip_record): one
+// workgroup, operands validated by the caller.
+hipError_t launch_clip_record(const double* rows, int nrows, double max_norm, double eps,
+                              const float* inv_scale, byteps_clip_record* out, hipStream_t s);
 // Error-feedback compress (bpsr_cast_ef.h; bpsr_k_cast_ef.hip: fp16 wire,
 // bpsr_k_cast_ef_bf16.hip: bf16 wire): nelem f32 ELEMENTS of src plus the f32
 // residual to the wire format at dst, the residual updated in place.  Operands

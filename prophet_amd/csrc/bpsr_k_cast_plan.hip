@@ -35,6 +35,20 @@ hipError_t launch_cast_plan_stats(const CastRec* table, uint32_t nrecords, int w
                                                  out_bytes, static_cast<StatPart*>(part), tu, s);
 }
 
+hipError_t launch_cast_plan_measure(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                    int divisor, int u, void* part, const Tuning& tu,
+                                    hipStream_t s) {
+  return launch_plan_measure<NarrowF16, kBFloat16>(table, nrecords, wide_dtype, divisor, u,
+                                                   static_cast<StatPart*>(part), tu, s);
+}
+
+hipError_t launch_cast_plan_scaled(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                   int divisor, int u, uint64_t out_bytes,
+                                   const float* mult, const Tuning& tu, hipStream_t s) {
+  return launch_plan_scaled<NarrowF16, kBFloat16>(table, nrecords, wide_dtype, divisor, u,
+                                                  out_bytes, mult, tu, s);
+}
+
 // Finishes the statistics, one workgroup per segment, on the stream of the
 // decompress (the kernel boundary makes every XCD's partials visible).  The
 // segment's records — seg_recs[seg_begin[s] .. seg_begin[s + 1]), ascending —
@@ -111,6 +125,56 @@ hipError_t launch_cast_stats_finish(const uint32_t* seg_begin, const uint32_t* s
   if (nsegs <= 0) return hipSuccess;
   hipLaunchKernelGGL(cast_stats_finish_kernel, dim3((uint32_t)nsegs), dim3(kFinishBlock), 0, s,
                      seg_begin, seg_recs, static_cast<const StatPart*>(part), stats);
+  return hipGetLastError();
+}
+
+// The clip record (byteps_reduce_clip_record): one workgroup
+// adds up `nrows` statistics rows — lane t takes rows t, t + kFinishBlock, ...
+// in ascending order, the waves add their lanes up (stat_wave_sum) and lane 0
+// the waves, in wave order: an order nrows alone fixes — and lane 0 derives
+// the norm and the two multipliers in f64.  A row's count is an integer below
+// 2^53 held in a double: added as integers, it stays exact.
+__global__ __launch_bounds__(kFinishBlock) void clip_record_kernel(
+    const double* __restrict__ rows, int nrows, double max_norm, double eps,
+    const float* __restrict__ inv_scale, byteps_clip_record* __restrict__ out) {
+  constexpr uint32_t kFinishWaves = kFinishBlock / 64;
+  __shared__ double wsum[kFinishWaves];
+  __shared__ uint64_t wcnt[kFinishWaves];
+  double sum = 0.0;
+  uint64_t cnt = 0;
+  for (uint32_t r = threadIdx.x; r < (uint32_t)nrows; r += kFinishBlock) {
+    sum += rows[2 * (uint64_t)r];
+    cnt += (uint64_t)rows[2 * (uint64_t)r + 1];
+  }
+  stat_wave_sum(sum, cnt);
+  if ((threadIdx.x & 63) == 0) {
+    wsum[threadIdx.x >> 6] = sum;
+    wcnt[threadIdx.x >> 6] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double total = wsum[0];
+    uint64_t c = wcnt[0];
+    for (uint32_t w = 1; w < kFinishWaves; ++w) {
+      total += wsum[w];
+      c += wcnt[w];
+    }
+    const double inv = inv_scale ? (double)*inv_scale : 1.0;
+    const double norm = __builtin_sqrt(total) * inv;
+    const double q = max_norm / (norm + eps);
+    const double coef = q < 1.0 ? q : 1.0;
+    out->sumsq = total;
+    out->nonfinite = (double)c;
+    out->norm = norm;
+    out->coef = (float)coef;
+    out->mult = (float)(coef * inv);
+  }
+}
+
+hipError_t launch_clip_record(const double* rows, int nrows, double max_norm, double eps,
+                              const float* inv_scale, byteps_clip_record* out, hipStream_t s) {
+  hipLaunchKernelGGL(clip_record_kernel, dim3(1), dim3(kFinishBlock), 0, s, rows, nrows, max_norm,
+                     eps, inv_scale, out);
   return hipGetLastError();
 }
 

@@ -20,4 +20,18 @@ hipError_t launch_cast_plan_stats_bf16(const CastRec* table, uint32_t nrecords, 
                                                  out_bytes, static_cast<StatPart*>(part), tu, s);
 }
 
+hipError_t launch_cast_plan_measure_bf16(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                         int divisor, int u, void* part, const Tuning& tu,
+                                         hipStream_t s) {
+  return launch_plan_measure<NarrowBF16, kFloat16>(table, nrecords, wide_dtype, divisor, u,
+                                                   static_cast<StatPart*>(part), tu, s);
+}
+
+hipError_t launch_cast_plan_scaled_bf16(const CastRec* table, uint32_t nrecords, int wide_dtype,
+                                        int divisor, int u, uint64_t out_bytes,
+                                        const float* mult, const Tuning& tu, hipStream_t s) {
+  return launch_plan_scaled<NarrowBF16, kFloat16>(table, nrecords, wide_dtype, divisor, u,
+                                                  out_bytes, mult, tu, s);
+}
+
 }  // namespace bpsr

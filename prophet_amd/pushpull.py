@@ -63,6 +63,13 @@ sum of squares and the non-finite count of the aggregate just written — the
 global gradient norm and GradScaler's ``found_inf`` without a second sweep.
 For device tensors the rows and everything derived from them stay on the
 device, in stream order.
+
+``push_pull_iteration(..., clip_norm=, clip_eps=, unscale=)`` clips the whole
+iteration's gradients by their global norm and unscales them inside the
+decompress: after the last pull every compressor group is
+measured into one rows tensor, one clip record is made over all rows, and
+every group is decompressed times the record's ``mult``.  It leaves
+``Worker.grad_clip`` (:class:`GradClip`) and ``Worker.grad_stats``.
 """
 from __future__ import annotations
 
@@ -141,9 +148,11 @@ class GradStats:
     the contexts of the call that travel uncompressed and so have no row.
     ``rows`` lives where the outputs live.  For device rows every method
     returns a 0-d device tensor and nothing synchronises with the host: a
-    caller can clip (``torch.clamp(max_norm / (stats.norm() + eps), max=1)``)
-    or skip (``torch.where(stats.nonfinite() > 0, ...)``) on the device in
-    stream order."""
+    caller can skip (``torch.where(stats.nonfinite() > 0, ...)``) on the device
+    in stream order.  To clip by the global norm, do not multiply the
+    gradients afterwards: ``push_pull_iteration(clip_norm=...)`` clips (and
+    unscales) inside the decompress, which writes them anyway
+    (:class:`GradClip`)."""
 
     def __init__(self, names, rows, skipped=()):
         self.names = list(names)
@@ -166,6 +175,74 @@ class GradStats:
         """The global L2 norm of the finite values: ``sqrt(sumsq())``."""
         t = self.sumsq()
         return t.sqrt() if hasattr(t, "data_ptr") else t ** 0.5
+
+
+class GradClip:
+    """The clip record of one ``push_pull_iteration(clip_norm=...)``:
+    ``norm`` — the L2 norm of the unscaled aggregate over its finite values
+    (float64); ``coef`` — ``min(1, clip_norm / (norm + eps))`` and ``mult`` —
+    ``coef * unscale``, what every floating output was multiplied by
+    (float32); ``found_inf`` — the number of non-finite values (float64: skip
+    the step if it is not 0); ``sumsq`` — the sum of squares before the
+    unscale.  ``names`` / ``rows`` — the floating contexts and their
+    statistics rows BEFORE the clip, the compressed ones first (as
+    ``grad_stats``), then the uncompressed; ``skipped`` — the integer
+    contexts, which are left alone.  For device tensors every field is a 0-d
+    device tensor (views of ``record``, a ``reducer.ClipRecord``) and nothing
+    synchronises with the host."""
+
+    def __init__(self, record, names, rows, skipped=()):
+        self.record = record
+        self.norm, self.coef, self.mult = record.norm, record.coef, record.mult
+        self.found_inf, self.sumsq = record.nonfinite, record.sumsq
+        self.names = list(names)
+        self.rows = rows
+        self.skipped = list(skipped)
+
+
+def _finite_row(row, x) -> None:
+    """``row[:] = (sum of squares of the finite values of x in float64, count
+    of the others)``: the decompress statistics' definition, for a tensor that
+    travels uncompressed; on x's device, in stream order."""
+    if hasattr(x, "data_ptr"):
+        import torch
+        v = x.detach().reshape(-1).to(torch.float64)
+        fin = torch.isfinite(v)
+        row[0] = torch.where(fin, v * v, torch.zeros_like(v)).sum()
+        row[1] = (~fin).sum().to(torch.float64)
+        return
+    from .compression import decompress_stats
+    row[0], row[1] = decompress_stats(x)
+
+
+def _scale_(x, mult) -> None:
+    """In-place ``x *= mult`` (float32; a 0-d device tensor for a device x)
+    with one rounding: the f32 product for f32 and the 2-byte types, the f64
+    product for f64."""
+    if hasattr(x, "data_ptr") and x.device.type == "cuda":
+        import torch
+        if x.dtype == torch.float64:
+            x.mul_(mult.to(torch.float64))
+        elif x.dtype == torch.float32:
+            x.mul_(mult)
+        else:
+            x.copy_((x.to(torch.float32) * mult).to(x.dtype))
+        return
+    from .compression import _scale_host_
+    _scale_host_(x, mult)
+
+
+def _place(x):
+    """The device of a device tensor, None for the host."""
+    dev = getattr(x, "device", None) if hasattr(x, "data_ptr") else None
+    return dev if dev is not None and dev.type == "cuda" else None
+
+
+def _is_float(x) -> bool:
+    if hasattr(x, "data_ptr"):
+        return bool(x.is_floating_point())
+    import numpy as np
+    return bool(np.issubdtype(x.dtype, np.floating))
 
 
 def _stat_rows(n: int, like):
@@ -220,6 +297,9 @@ class Worker:
         # the decompress statistics of the last push_pull / push_pull_iteration
         # with stats=True (GradStats); None before the first
         self.grad_stats = None
+        # the clip record of the last push_pull_iteration with clip_norm
+        # (GradClip); None before the first
+        self.grad_clip = None
 
     @property
     def sr_step(self) -> int:
@@ -429,7 +509,8 @@ class Worker:
         return out
 
     def push_pull_iteration(self, tensors: dict, scheduler=None, average: bool = False,
-                            stats: bool = False) -> list:
+                            stats: bool = False, clip_norm=None, clip_eps: float = 1e-6,
+                            unscale=None) -> list:
         """One training iteration: every declared tensor, gradients arriving in
         backward order (highest declared index first).  With a Prophet
         ``scheduler`` (``ProphetPushQueue``) the partitions are pushed in the
@@ -444,9 +525,32 @@ class Worker:
         holds one row per compressed context, grouped by compressor in the
         order the compressors first appear (``grad_stats.names``); the rows
         live where the first compressed tensor lives.
+        ``clip_norm``: clip every floating tensor of the iteration by their
+        global L2 norm, and multiply by ``unscale`` (a number, or a 1-element
+        float32 device tensor: GradScaler's inverse scale), inside the
+        decompress: measure every compressor group, one clip record over all
+        rows, then the scaled decompress per group — on the current stream,
+        nothing synchronises with the host.  Floating tensors that travel
+        uncompressed are divided for ``average`` first, measured by torch
+        under the same finite-only definition and multiplied in place;
+        integer tensors keep the sum they pulled: they are neither divided
+        nor multiplied, and are named in ``grad_clip.skipped``.  Leaves ``grad_clip``
+        (:class:`GradClip`) and ``grad_stats`` (the rows before the clip).
+        All floating tensors live in one place, a device or the host.
         Returns the release groups as lists of (declared key, partition)."""
         from .prophet import PushTask, release_groups
         ctxs = [self.contexts[n] for n in self._declared if n in tensors]
+        if clip_norm is None and unscale is not None:
+            raise ValueError("unscale goes with clip_norm")
+        if clip_norm is not None:         # before anything is pushed
+            if not clip_norm > 0 or clip_norm != clip_norm or clip_norm == float("inf"):
+                raise ValueError(f"clip_norm {clip_norm} is not a finite positive number")
+            if not clip_eps >= 0:
+                raise ValueError(f"clip_eps {clip_eps} < 0")
+            places = {_place(tensors[c.name]) for c in ctxs if _is_float(tensors[c.name])}
+            if len(places) > 1:
+                raise ValueError("clip_norm: the floating tensors live in one place, "
+                                 "a device or the host")
         divisor = 1
         if average:
             divisor = getattr(self.frontend, "size", None)
@@ -483,6 +587,10 @@ class Worker:
         for c in ctxs:
             for key, off, ln in c.parts:
                 self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
+        if clip_norm is not None:
+            self._clip_iteration(ctxs, casts, tensors, divisor, average, clip_norm, clip_eps,
+                                 unscale)
+            return [[(t.grad, t.part) for t in g] for g in groups]
         rows, at = None, 0
         if stats:
             names = [c.name for cs in casts.values() for c in cs]
@@ -502,6 +610,53 @@ class Worker:
                 if c.compressor is None:
                     _divide_(tensors[c.name], divisor)
         return [[(t.grad, t.part) for t in g] for g in groups]
+
+    def _clip_iteration(self, ctxs, casts, tensors, divisor, average, clip_norm, clip_eps,
+                        unscale) -> None:
+        """The end of ``push_pull_iteration(clip_norm=...)``, after the last
+        pull: rows of every floating context (compressor groups measured,
+        uncompressed tensors by torch after their divide), one clip record,
+        the scaled decompress per group and the multiply of the others."""
+        comp_names = [c.name for cs in casts.values() for c in cs]
+        plain = [c for c in ctxs if c.compressor is None and _is_float(tensors[c.name])]
+        skipped = [c.name for c in ctxs
+                   if c.compressor is None and not _is_float(tensors[c.name])]
+        names = comp_names + [c.name for c in plain]
+        first = tensors[names[0]] if names else None
+        on_dev = hasattr(first, "data_ptr") and first.device.type == "cuda"
+        rows = _stat_rows(len(names), first if on_dev else None)
+        at = 0
+        for comp, cs in casts.items():
+            comp.measure_many_with([_contiguous(tensors[c.name]) for c in cs],
+                                   [c.staging for c in cs], [c.extra for c in cs], divisor,
+                                   plans=self._cast_plans, stats=rows[at:at + len(cs)])
+            at += len(cs)
+        for c in plain:
+            if average:
+                _divide_(tensors[c.name], divisor)
+            _finite_row(rows[at], tensors[c.name])
+            at += 1
+        if on_dev:
+            import torch
+            from .torch_ops import _red
+            inv = unscale
+            if inv is not None and not hasattr(inv, "data_ptr"):
+                inv = torch.tensor([float(inv)], dtype=torch.float32, device=first.device)
+            with torch.cuda.device(first.device):
+                rec = _red().clip_record(rows, clip_norm, clip_eps, inv)
+        else:
+            from .compression import clip_record
+            rec = clip_record(rows, clip_norm, clip_eps,
+                              unscale.item() if hasattr(unscale, "data_ptr") else unscale)
+        for comp, cs in casts.items():
+            comp.decompress_many_with([_contiguous(tensors[c.name]) for c in cs],
+                                      [c.staging for c in cs], [c.extra for c in cs], divisor,
+                                      plans=self._cast_plans, scale=rec.mult)
+        for c in plain:
+            _scale_(tensors[c.name], rec.mult)
+        self.grad_stats = GradStats(comp_names, rows[:len(comp_names)],
+                                    [c.name for c in ctxs if c.compressor is None])
+        self.grad_clip = GradClip(rec, names, rows, skipped)
 
 
 def _nbytes(x) -> int:
@@ -553,4 +708,4 @@ def _slice(x, off: int, ln: int):
     return x.reshape(-1).view(np.uint8)[off:off + ln]
 
 
-__all__ = ["ServerFrontend", "Worker", "Context", "GradStats", "K_DEFAULT_PUSH_PULL", "DType", "elem_size"]
+__all__ = ["ServerFrontend", "Worker", "Context", "GradStats", "GradClip", "K_DEFAULT_PUSH_PULL", "DType", "elem_size"]

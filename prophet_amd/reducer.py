@@ -66,6 +66,8 @@ EXPORTS = (
     "byteps_reduce_compress_sr", "byteps_reduce_cast_plan_create_sr",
     "byteps_reduce_cast_plan_compress_sr",
     "byteps_reduce_cast_plan_decompress_stats",
+    "byteps_reduce_cast_plan_measure", "byteps_reduce_clip_record",
+    "byteps_reduce_cast_plan_decompress_scaled",
 )
 
 
@@ -168,6 +170,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                     ctypes.POINTER(_vp)]
     L.byteps_reduce_cast_plan_compress_sr.argtypes = [_vp, ctypes.c_uint32, _vp]
     L.byteps_reduce_cast_plan_decompress_stats.argtypes = [_vp, _int, _vp, _vp]
+    L.byteps_reduce_cast_plan_measure.argtypes = [_vp, _int, _vp, _vp]
+    L.byteps_reduce_clip_record.argtypes = [_vp, _int, ctypes.c_double, ctypes.c_double, _vp,
+                                            _vp, _vp]
+    L.byteps_reduce_cast_plan_decompress_scaled.argtypes = [_vp, _int, _vp, _vp]
     _LIB = L
     return L
 
@@ -339,6 +345,36 @@ class GpuReducer:
         ``decompress`` is the plain one."""
         return CastPlan(self.lib, segments, wide_dtype, wire_dtype)
 
+    def clip_record(self, rows, max_norm: float, eps: float = 1e-6, inv_scale=None, out=None,
+                    stream=None) -> "ClipRecord":
+        """The clip record of statistics rows (byteps_reduce_clip_record; the
+        definition: ``compression.clip_record``): ``rows`` is a contiguous
+        float64 device tensor of ``[n, 2]`` (or ``2 n``) elements — any
+        concatenation of plans' rows — ``inv_scale`` a 1-element float32
+        device tensor or None (1).  One small launch on ``stream``; nothing
+        synchronises with the host.  Returns a :class:`ClipRecord` (``out``
+        if given): 32 bytes on the device with views of its fields.  The
+        record holds ``rows`` and ``inv_scale`` until its next use or until
+        it is dropped: the launch is asynchronous."""
+        import torch
+        if not hasattr(rows, "data_ptr") or rows.dtype != torch.float64:
+            raise ValueError(f"rows must be a float64 device tensor, got "
+                             f"{getattr(rows, 'dtype', type(rows))}")
+        if rows.device.type != "cuda" or not rows.is_contiguous() or rows.numel() % 2:
+            raise ValueError("rows must be a contiguous device tensor of 2 n elements")
+        if inv_scale is not None:
+            _check_scalar_f32(inv_scale, "inv_scale", rows.device)
+        rec = out if out is not None else ClipRecord(rows.device)
+        if not isinstance(rec, ClipRecord):
+            raise ValueError(f"out must be a ClipRecord, got {type(out)!r}")
+        if rec.tensor.device != rows.device:
+            raise ValueError(f"out is on {rec.tensor.device}, rows on {rows.device}")
+        rec._keep = (rows, inv_scale)
+        _check(self.lib.byteps_reduce_clip_record(
+            _ptr(rows), rows.numel() // 2, float(max_norm), float(eps), _ptr(inv_scale),
+            _ptr(rec.tensor), _stream_of(rows, stream)))
+        return rec
+
     def sum_n(self, dst, srcs: Sequence, length: int, dtype: int,
               mode: int = MODE_REFERENCE, stream=None) -> int:
         """Left fold ``dst = ((srcs[0] + srcs[1]) + ...)`` in the given order."""
@@ -448,6 +484,34 @@ _CAST_SCHEMES = {
 }
 
 
+def _check_scalar_f32(x, name: str, device=None) -> None:
+    """``x``: a 1-element float32 device tensor (on ``device`` if given)."""
+    import torch
+    if not hasattr(x, "data_ptr") or x.dtype != torch.float32 or x.numel() != 1:
+        raise ValueError(f"{name} must be a 1-element float32 device tensor, got "
+                         f"{getattr(x, 'dtype', type(x))} of "
+                         f"{x.numel() if hasattr(x, 'numel') else '?'} elements")
+    if x.device.type != "cuda" or (device is not None and x.device != device):
+        raise ValueError(f"{name} is on {x.device}, expected {device or 'a device'}")
+    _fits(4, x)
+
+
+class ClipRecord:
+    """``byteps_clip_record`` on the device: ``tensor`` is its 32 bytes, and
+    ``sumsq``, ``nonfinite``, ``norm`` (float64) and ``coef``, ``mult``
+    (float32) are 0-d views of it, valid in stream order after
+    ``GpuReducer.clip_record``.  ``mult`` is what
+    ``CastPlan.decompress(scale=)`` takes."""
+
+    def __init__(self, device):
+        import torch
+        self.tensor = torch.zeros(32, dtype=torch.uint8, device=device)
+        f64, f32 = self.tensor.view(torch.float64), self.tensor.view(torch.float32)
+        self.sumsq, self.nonfinite, self.norm = f64[0], f64[1], f64[2]
+        self.coef, self.mult = f32[6], f32[7]
+        self._keep = None
+
+
 class CastPlan:
     """``byteps_reduce_cast_plan``: the segments' tile table resident on the
     device.  ``compress`` writes every fp16 side from its wide side,
@@ -514,22 +578,9 @@ class CastPlan:
         _check(self.lib.byteps_reduce_cast_plan_compress(self.handle,
                                                          _stream_of(self.first, stream)))
 
-    def decompress(self, divisor: int = 1, stream=None, stats=None) -> None:
-        """One launch.  With ``stats`` — a contiguous float64 device tensor
-        of ``2 * nsegs`` elements on the plan's device, or a raw pointer to as
-        much — the same bytes are written and ``stats[2 s], stats[2 s + 1]``
-        receive segment ``s``'s sum of the squares of the finite values
-        written (f64) and the count of the non-finite ones
-        (byteps_reduce_cast_plan_decompress_stats; a second, small launch on
-        the same stream).  A tensor is bounds-checked like the other
-        operands, and the plan holds it until its next statistics call or
-        ``close``: the launches are asynchronous.  A plan's first statistics
-        call allocates its partial sums; two statistics launches of one plan
-        must not run concurrently."""
-        if stats is None:
-            _check(self.lib.byteps_reduce_cast_plan_decompress(self.handle, int(divisor),
-                                                               _stream_of(self.first, stream)))
-            return
+    def _check_stats(self, stats) -> None:
+        """A statistics tensor is float64, contiguous, of ``2 * nsegs``
+        elements, on the plan's device."""
         if hasattr(stats, "data_ptr"):
             import torch
             if stats.dtype != torch.float64:
@@ -543,6 +594,51 @@ class CastPlan:
             if stats.device.type != "cuda" or (dev is not None and stats.device != dev):
                 raise ValueError(f"stats is on {stats.device}, the plan on {dev or 'a device'}")
             _fits(16 * self.nsegs, stats)
+
+    def measure(self, divisor: int = 1, stream=None, stats=None) -> None:
+        """The statistics of ``decompress(divisor, stats=stats)`` — the same
+        rows, bit for bit — without the decompress: the 2-byte sides are read
+        and no wide side is written (byteps_reduce_cast_plan_measure).
+        ``stats`` as for ``decompress``."""
+        if stats is None:
+            raise ValueError("measure needs a stats tensor")
+        self._check_stats(stats)
+        self._stats = stats           # held: the launches are asynchronous
+        _check(self.lib.byteps_reduce_cast_plan_measure(
+            self.handle, int(divisor), _ptr(stats), _stream_of(self.first, stream)))
+
+    def decompress(self, divisor: int = 1, stream=None, stats=None, scale=None) -> None:
+        """One launch.  With ``scale`` — a 1-element float32 device tensor,
+        typically a :class:`ClipRecord`'s ``mult`` — every value written is
+        multiplied by it, rounded once to the wide dtype
+        (byteps_reduce_cast_plan_decompress_scaled); the plan holds the tensor
+        until its next scaled launch or ``close``.  ``scale`` excludes
+        ``stats``.  With ``stats`` — a contiguous float64 device tensor
+        of ``2 * nsegs`` elements on the plan's device, or a raw pointer to as
+        much — the same bytes are written and ``stats[2 s], stats[2 s + 1]``
+        receive segment ``s``'s sum of the squares of the finite values
+        written (f64) and the count of the non-finite ones
+        (byteps_reduce_cast_plan_decompress_stats; a second, small launch on
+        the same stream).  A tensor is bounds-checked like the other
+        operands, and the plan holds it until its next statistics call or
+        ``close``: the launches are asynchronous.  A plan's first statistics
+        call allocates its partial sums; two statistics launches of one plan
+        must not run concurrently."""
+        if stats is not None and scale is not None:
+            raise ValueError("decompress: stats and scale exclude each other "
+                             "(measure, then decompress(scale=))")
+        if scale is not None:
+            if hasattr(scale, "data_ptr"):
+                _check_scalar_f32(scale, "scale", getattr(self.first, "device", None))
+            self._scale = scale       # held: the launch is asynchronous
+            _check(self.lib.byteps_reduce_cast_plan_decompress_scaled(
+                self.handle, int(divisor), _ptr(scale), _stream_of(self.first, stream)))
+            return
+        if stats is None:
+            _check(self.lib.byteps_reduce_cast_plan_decompress(self.handle, int(divisor),
+                                                               _stream_of(self.first, stream)))
+            return
+        self._check_stats(stats)
         self._stats = stats           # held: the launches are asynchronous
         _check(self.lib.byteps_reduce_cast_plan_decompress_stats(
             self.handle, int(divisor), _ptr(stats), _stream_of(self.first, stream)))
@@ -553,6 +649,7 @@ class CastPlan:
             self.handle = _vp()
         self._keep = []
         self._stats = None
+        self._scale = None
 
     def __del__(self):
         try:

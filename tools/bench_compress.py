@@ -120,6 +120,28 @@ The statistics are compared with torch's f64 arithmetic on the device first
   plan_stats faster than torch by more than the larger of the two spreads.
 
 ``plan_stats / plan`` is recorded, not gated.
+
+``--clip`` measures clipping by the global norm and unscaling inside the
+decompress by the same method over the same two shapes
+(fp16 wire unless ``--wire bf16``, f32, divisor 8, unscale 2^-7, a max_norm
+that clips):
+
+  clip_fused        byteps_reduce_cast_plan_measure, byteps_reduce_clip_record,
+                    byteps_reduce_cast_plan_decompress_scaled: 2 B read, then
+                    2 B read + 4 B written an element;
+  stats_then_torch  the decompress with statistics, the record's arithmetic
+                    from the rows in torch, torch._foreach_mul_ over the
+                    outputs: 6 + 8 B an element;
+  torch_all         the plain plan decompress, then
+                    torch.nn.utils.clip_grad_norm_(foreach=True) on the
+                    outputs: 6 + 4 + 8 B an element (it does not unscale).
+
+The fused outputs are first compared bit for bit with ``mult`` times the plain
+decompress and the measured rows with the statistics rows.  Gate, at both
+shapes:
+
+  clip_fused faster than the faster of the other two by more than the larger
+  of the two spreads.
 """
 import argparse
 import json
@@ -181,7 +203,13 @@ def main() -> int:
     p.add_argument("--stats", action="store_true",
                    help="the decompress with statistics against the plain decompress and "
                         "torch's norm + isfinite after it; the ResNet-50 table and one segment")
+    p.add_argument("--clip", action="store_true",
+                   help="clip by global norm and unscale inside the decompress against the "
+                        "statistics decompress + torch's multiply and against "
+                        "clip_grad_norm_; the ResNet-50 table and one segment")
     args = p.parse_args()
+    if args.clip:
+        return clip_mode(args)
     if args.stats:
         return stats_mode(args)
     if args.sr:
@@ -938,6 +966,130 @@ def stats_mode(args) -> int:
                 "gate_spread_ms": sp,
                 "plan_stats_over_plan": round(res["plan_stats"]["ms"] / res["plan"]["ms"], 3),
                 "torch_over_plan_stats": round(res["torch"]["ms"] / res["plan_stats"]["ms"], 2)}
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    total_bytes, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    out["iteration"] = shape("table", [(o // 2, ln // 2) for o, ln in rows], total_bytes // 2)
+    torch.cuda.empty_cache()
+    out["big"] = shape("big", [(0, args.elems)], args.elems)
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    ok = all(gates.values()) and all(v for c in checks.values() for k, v in c.items()
+                                     if isinstance(v, bool))
+    return 0 if ok else 1
+
+
+def clip_mode(args) -> int:
+    """Clip by global norm and unscale: measure + record + scaled decompress
+    against the statistics decompress followed by torch's multiply, and
+    against the plain decompress followed by torch's clip_grad_norm_."""
+    import torch
+
+    from prophet_amd.dtypes import DType
+    from prophet_amd.reducer import ClipRecord, GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    F32 = DType.FLOAT32
+    wd, tdt = {"fp16": (DType.FLOAT16, torch.float16),
+               "bf16": (DType.BFLOAT16, torch.bfloat16)}[args.wire]
+    DIV, EPS, INV = 8, 1e-6, 2.0 ** -7
+    out = {"tool": "bench_compress", "mode": "clip by global norm", "wire": args.wire,
+           "divisor": DIV, "unscale": INV, "sets": args.sets, "rounds": args.rounds,
+           "inner": args.inner, "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+
+    def shape(label, nsegs_rows, arena_elems):
+        """One shape: ``nsegs_rows`` = (first element, elements) per segment."""
+        nelem = sum(n for _, n in nsegs_rows)
+        with step(f"setup, {label}", 120):
+            g = torch.Generator(device=dev).manual_seed(7)
+            inv = torch.tensor([INV], dtype=torch.float32, device=dev)
+            sets = []
+            for _ in range(args.sets):
+                half = (torch.randn(arena_elems, device=dev, generator=g) * 64).to(tdt)
+                wide = torch.empty(arena_elems, device=dev)
+                outs = [wide[o:o + n] for o, n in nsegs_rows]
+                params = [torch.nn.Parameter(o, requires_grad=True) for o in outs]
+                for prm, o in zip(params, outs):
+                    prm.grad = o             # clip_grad_norm_ scales the outputs themselves
+                sets.append({"wide": wide, "half": half, "outs": outs, "params": params,
+                             "st": torch.empty(2 * len(outs), dtype=torch.float64, device=dev),
+                             "rec": ClipRecord(dev),
+                             "plan": red.cast_plan([(w, half[o:o + n], n)
+                                                    for w, (o, n) in zip(outs, nsegs_rows)],
+                                                   F32, wd)})
+            for s in sets:                       # the first statistics call allocates
+                s["plan"].decompress(DIV, stats=s["st"])
+            # a max_norm that clips: a third of the unscaled norm
+            max_norm = float(sets[0]["st"].view(-1, 2)[:, 0].sum().sqrt()) * INV / 3
+            torch.cuda.synchronize()
+
+        def fused(k):
+            s = sets[k]
+            s["plan"].measure(DIV, stats=s["st"])
+            red.clip_record(s["st"], max_norm, EPS, inv, out=s["rec"])
+            s["plan"].decompress(DIV, scale=s["rec"].mult)
+
+        def stats_then_torch(k):
+            s = sets[k]
+            s["plan"].decompress(DIV, stats=s["st"])
+            norm = s["st"].view(-1, 2)[:, 0].sum().sqrt() * INV
+            coef = torch.clamp(max_norm / (norm + EPS), max=1.0)
+            torch._foreach_mul_(s["outs"], (coef * INV).to(torch.float32))
+
+        def torch_all(k):
+            s = sets[k]
+            s["plan"].decompress(DIV)
+            torch.nn.utils.clip_grad_norm_(s["params"], max_norm / INV, foreach=True)
+
+        with step(f"check, {label}", 120):
+            s = sets[0]
+            s["plan"].decompress(DIV, stats=s["st"])
+            want_rows = s["st"].clone()
+            plain = s["wide"].clone()
+            s["st"].fill_(float("nan"))
+            s["wide"].fill_(-1.0)
+            fused(0)
+            mult = s["rec"].mult.clone()
+            ref_norm = float(want_rows.view(-1, 2)[:, 0].sum().sqrt()) * INV
+            checks[label] = {
+                "rows_equal_stats": bool(torch.equal(want_rows.view(torch.int64),
+                                                     s["st"].view(torch.int64))),
+                "bytes_equal_mult_times_plain": bool(torch.equal(
+                    (plain * mult).view(torch.int32), s["wide"].view(torch.int32))),
+                "norm_matches": abs(float(s["rec"].norm) - ref_norm) <= 1e-12 * ref_norm,
+                "clips": float(s["rec"].coef) < 1.0,
+                "norm": float(s["rec"].norm), "coef": float(s["rec"].coef),
+                "mult": float(mult), "max_norm": max_norm}
+            del plain, want_rows
+            torch.cuda.synchronize()
+        res = timed_rounds(torch, {
+            "clip_fused": (fused, args.inner),
+            "stats_then_torch": (stats_then_torch, args.inner),
+            "torch_all": (torch_all, args.inner)}, len(sets), args)
+        for name, per in (("clip_fused", 8), ("stats_then_torch", 14), ("torch_all", 18)):
+            res[name]["bytes_per_elem"] = per
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        other = min(("stats_then_torch", "torch_all"), key=lambda k: res[k]["ms"])
+        sp = max(res["clip_fused"]["spread_ms"], res[other]["spread_ms"])
+        gates[f"{label}_clip_fused_beats_the_faster_other"] = \
+            res[other]["ms"] - res["clip_fused"]["ms"] > sp
+        for s in sets:
+            s["plan"].close()
+        return {"segments": len(nsegs_rows), "elems": nelem, "results": res,
+                "faster_other": other, "gate_spread_ms": sp,
+                "other_over_clip_fused": round(res[other]["ms"] / res["clip_fused"]["ms"], 3)}
 
     with step("init", 60):
         red = GpuReducer(device=0)
