@@ -150,7 +150,9 @@ int byteps_reduce_shutdown(void);
 /* CpuReducer::sum(dst, src, len, dtype), cpu_reducer.cc:57-83. */
 int byteps_reduce_sum(void* dst, const void* src, size_t len, int dtype, void* stream);
 
-/* CpuReducer::sum(dst, src1, src2, len, dtype), cpu_reducer.cc:130-162. */
+/* CpuReducer::sum(dst, src1, src2, len, dtype), cpu_reducer.cc:130-162.  When
+ * both operands are NaN the result is src1's, quieted; FLOAT16 gives src2's,
+ * as the compiled reference does. */
 int byteps_reduce_sum3(void* dst, const void* src1, const void* src2, size_t len,
                        int dtype, void* stream);
 

@@ -20,6 +20,8 @@
  *    result = quiet(dst) if dst is NaN, else quiet(src) if src is NaN, else
  *    the x86 default NaN 0xfe00 for inf + -inf.  Payloads are kept
  *    (vcvtph2ps / vcvtps2ph truncate/extend the payload by 13 bits).
+ *    In the 3-operand form (cpu_reducer.cc:173-207) src2 takes dst's place:
+ *    quiet(src2) if src2 is NaN, else quiet(src1).
  *  - fp16, tail elements (cpu_reducer.cc:118-125): every NaN becomes 0x7fff
  *    (HalfBits2Float maps NaN to 0x7fffffff, Float2HalfBits emits 0x7fff).
  *  - fp32/fp64: quiet(dst) if dst NaN, else quiet(src), else x86 default NaN
@@ -199,6 +201,10 @@ int bpsr_oracle_sum(void* dst, const void* src, size_t len, int dtype, int nthre
 
 int bpsr_oracle_sum3(void* dst, const void* src1, const void* src2, size_t len,
                      int dtype, int nthreads) {
+  /* fp16: the compiled reference's 3-operand F16C body keeps src2's NaN when
+   * both operands are NaN (cpu_reducer.cc:183-194), where the in-place body
+   * keeps dst's; everything else about the add is commutative. */
+  if (dtype == ORC_FLOAT16) return sum_into(dst, src2, src1, len, dtype, nthreads);
   return sum_into(dst, src1, src2, len, dtype, nthreads);
 }
 

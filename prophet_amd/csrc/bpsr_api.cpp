@@ -327,7 +327,11 @@ int byteps_reduce_sum3(void* dst, const void* src1, const void* src2, size_t len
   if (!dst || !src1 || !src2) return fail(BYTEPS_REDUCE_EARGS, "null pointer");
   if (overlaps_partially(dst, src1, len) || overlaps_partially(dst, src2, len))
     return fail(BYTEPS_REDUCE_EARGS, "dst partially overlaps a source");
-  const void* srcs[2] = {src1, src2};
+  // fp16: the reference's compiled 3-operand body keeps src2's NaN when both
+  // operands are NaN (the in-place body keeps dst's), so src2 is folded first;
+  // nothing else in the add depends on the operands' order.
+  const bool swap = dtype == BYTEPS_REDUCE_FLOAT16;
+  const void* srcs[2] = {swap ? src2 : src1, swap ? src1 : src2};
   return fold_once(dst, srcs, 2, len, dtype, kModeReference, false, to_stream(stream));
 }
 
