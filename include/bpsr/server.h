@@ -319,7 +319,12 @@ int byteps_server_order_after(byteps_server* s, const uint64_t* keys, int n, voi
  * keyed consumers launched ahead of their epoch and retired because no round
  * began it within 1 ms, out[12] consumer epochs closed with keys not pushed
  * (their rounds went to a later epoch) and out[13] lane epochs (opened by a
- * copied round: no consumer); the first n (<= 14). */
+ * copied round: no consumer).  The keyed queue's table, read-only: out[14] its
+ * tile records (0 while no queue exists), out[15] its tile size in 16-byte
+ * vectors per lane (VPT: 1, 2 or 4; 0 while no queue exists) and out[16] the
+ * cache policy of the most recent consumer launch (0 plain loads and stores,
+ * 1 non-temporal, 2 write-through stores; 0 before the first launch).  The
+ * first n (<= 17). */
 int byteps_server_stats(byteps_server* s, uint64_t* out, int n);
 
 /* Batched calls for a transport that delivers many keys at once (co-located

@@ -281,6 +281,7 @@ struct byteps_reduce_blockq {
   uint32_t* khdone = nullptr;       // pinned host, one completion word per block
   uint32_t* khdone_dev = nullptr;
   uint32_t opened = 0;              // highest epoch a round was released for (keyq_opened)
+  int last_pol = bpsr::kPolPlain;   // cache policy of the latest keyq_launch (keyq_shape)
 #ifdef BPSR_KEYED_TRACE
   unsigned long long* ktrace = nullptr;  // probe builds: kKtraceSlots launches' stamps
   size_t ktrace_per = 0;

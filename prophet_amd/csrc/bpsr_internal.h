@@ -614,5 +614,9 @@ bool keyq_failed(struct byteps_reduce_blockq* q);
 // last tile stored the completion word): a lock-free host read.
 bool keyq_key_done(const struct byteps_reduce_blockq* q, int key, uint32_t epoch);
 std::string keyq_debug(struct byteps_reduce_blockq* q);  // state summary (synchronous copy)
+// The keyed table's tile count and VPT (fixed at keyq_create) and the cache
+// policy of the latest keyq_launch (kPolPlain before the first): lock-free
+// host reads, for telemetry.
+void keyq_shape(const struct byteps_reduce_blockq* q, uint32_t* tiles, int* vpt, int* pol);
 
 }  // namespace bpsr

@@ -88,6 +88,7 @@ int keyq_launch(byteps_reduce_blockq* q, hipEvent_t stop, hipStream_t* stream, u
     e = launch_blockq(Q, q->ti.vpt, pol, kKeyedLds, true, q->dtype, q->mode, own);
   if (e != hipSuccess) return hip_fail(e, "keyed queue launch");
   seq_commit(*D, Q, own);
+  __atomic_store_n(&q->last_pol, pol, __ATOMIC_RELAXED);
   __atomic_store_n(&q->launch_epoch, ep, __ATOMIC_RELEASE);
   if (stream) *stream = own;
   if (epoch) *epoch = ep;
@@ -162,6 +163,12 @@ bool keyq_key_done(const byteps_reduce_blockq* q, int key, uint32_t epoch) {
 
 bool keyq_failed(byteps_reduce_blockq* q) {
   return __atomic_load_n(&q->hctl->err, __ATOMIC_ACQUIRE) != 0;
+}
+
+void keyq_shape(const byteps_reduce_blockq* q, uint32_t* tiles, int* vpt, int* pol) {
+  *tiles = q->ti.tiles;
+  *vpt = q->ti.vpt;
+  *pol = __atomic_load_n(&q->last_pol, __ATOMIC_RELAXED);
 }
 
 std::string keyq_debug(byteps_reduce_blockq* q) {

@@ -1912,13 +1912,19 @@ int byteps_server_stats(byteps_server* s, uint64_t* out, int n) {
     std::lock_guard<std::mutex> g(s->svc_mu);
     svc_launches = bpsr::copysvc_launches(s->svc);
   }
-  const uint64_t v[14] = {s->n_fold_launches.load(), s->n_rounds_folded.load(),
+  // the keyed queue is built once and kept until destroy (kq_tried publishes it)
+  uint32_t kq_tiles = 0;
+  int kq_vpt = 0, kq_pol = 0;
+  if (s->kq_tried.load(std::memory_order_acquire) && s->kq)
+    bpsr::keyq_shape(s->kq, &kq_tiles, &kq_vpt, &kq_pol);
+  const uint64_t v[17] = {s->n_fold_launches.load(), s->n_rounds_folded.load(),
                           s->n_pull_launches.load(), s->n_pulls.load(), s->issuer_ns.load(),
                           s->n_copy_launches.load(), s->n_consumer_launches.load(),
                           s->n_key_releases.load(), s->n_service_pulls.load(), svc_launches,
                           s->n_service_pushes.load(), s->n_consumer_retired.load(),
-                          s->n_epochs_closed.load(), s->n_lane_epochs.load()};
-  for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
+                          s->n_epochs_closed.load(), s->n_lane_epochs.load(),
+                          kq_tiles, (uint64_t)kq_vpt, (uint64_t)kq_pol};
+  for (int i = 0; i < n && i < 17; ++i) out[i] = v[i];
   return BYTEPS_REDUCE_OK;
 }
 

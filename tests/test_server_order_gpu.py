@@ -144,8 +144,8 @@ class Rig:
                 if not np.array_equal(got, want):
                     es = elem_size(dt)
                     m = n // es * es
-                    bad = op.changed(dt, got[:m], want[:m]).nonzero()[0]
-                    U = op.bits_type(dt)
+                    U = np.dtype(f"u{es}")          # (integer dtypes too: server_shapes)
+                    bad = (got[:m].view(U) != want[:m].view(U)).nonzero()[0]
                     raise AssertionError(
                         f"round {rnd} key {k} ({how}), order {order}: {len(bad)} of {m // es} "
                         "elements differ; first " + ", ".join(
