@@ -152,7 +152,18 @@ int byteps_reduce_sum(void* dst, const void* src, size_t len, int dtype, void* s
 
 /* CpuReducer::sum(dst, src1, src2, len, dtype), cpu_reducer.cc:130-162.  When
  * both operands are NaN the result is src1's, quieted; FLOAT16 gives src2's,
- * as the compiled reference does. */
+ * as the compiled reference does.
+ *
+ * Aliases.  The reference's loops are element-wise, so operands that are the
+ * same buffer are legal there, and they are here: byteps_reduce_sum accepts
+ * src == dst (dst doubles), byteps_reduce_sum3 accepts dst == src1,
+ * dst == src2, src1 == src2 and all three equal, and the result is what
+ * separate copies of the same values give.  Only an exact alias is accepted:
+ * a dst that overlaps a source partially is EARGS, and nothing is written.
+ * For FLOAT16 with both operands NaN, byteps_reduce_sum3(dst, dst, b) keeps
+ * b's NaN and byteps_reduce_sum3(dst, a, dst) keeps dst's own: src2's in both,
+ * quieted (elements of the scalar tail, from floor(n / 8) * 8 on, give 0x7fff
+ * for every NaN). */
 int byteps_reduce_sum3(void* dst, const void* src1, const void* src2, size_t len,
                        int dtype, void* stream);
 

@@ -354,6 +354,11 @@ inline int cache_pol(const Tuning& tu, uint64_t bytes_per_src) {
 // written by the same thread) — the in-place owner fold of the shard calls.
 int fold_any_alias(void* dst, const void* const* srcs, int n, size_t len, int dtype, int mode,
                    hipStream_t s);
+// Its operand rules alone, no HIP call: null pointers, a partial overlap of
+// dst with a source, dst aliasing two sources, dst aliasing srcs[k > 0] of
+// more than kMaxSrcs.  The shard calls ask before they move any data, so a
+// refused call leaves every buffer as it was.
+int fold_alias_check(const void* dst, const void* const* srcs, int n, size_t len);
 
 hipError_t launch_copy(void* dst, const void* src, size_t len, const Tuning& tu,
                        hipStream_t s);

@@ -483,12 +483,15 @@ int byteps_shard_reduce_scatter(byteps_shard_comm* c, const void* local, void* c
   if (mine.n())
     for (int r = 0; r < W; ++r)
       if (r != g) ops.push_back({false, r, nullptr, recv_slots[r], mine.n() * es});
+  std::vector<const void*> srcs(W);
+  if (mine.n()) {  // the fold's operand rules, before a receive writes into a slot
+    for (int r = 0; r < W; ++r) srcs[r] = r == g ? at(local, mine.lo * es) : recv_slots[r];
+    if ((rc = fold_alias_check(dst, srcs.data(), W, mine.n() * es))) return rc;
+  }
   if ((rc = use_device(c))) return rc;
   hipStream_t s = to_stream(stream);
   if ((rc = run_group(c, ops, s))) return rc;
   if (!mine.n()) return BYTEPS_REDUCE_OK;
-  std::vector<const void*> srcs(W);
-  for (int r = 0; r < W; ++r) srcs[r] = r == g ? at(local, mine.lo * es) : recv_slots[r];
   return fold_any_alias(dst, srcs.data(), W, mine.n() * es, dtype, mode, s);
 }
 
@@ -568,12 +571,15 @@ int byteps_shard_scatter_reduce(byteps_shard_comm* c, int root, const void* cons
   } else if (mine.n()) {
     for (int k = 0; k < n; ++k) ops.push_back({false, root, nullptr, recv_slots[k], mine.n() * es});
   }
+  std::vector<const void*> srcs(n);
+  if (mine.n()) {
+    for (int k = 0; k < n; ++k) srcs[k] = g == root ? at(pushes[k], mine.lo * es) : recv_slots[k];
+    if ((rc = fold_alias_check(dst, srcs.data(), n, mine.n() * es))) return rc;
+  }
   if ((rc = use_device(c))) return rc;
   hipStream_t s = to_stream(stream);
   if ((rc = run_group(c, ops, s))) return rc;
   if (!mine.n()) return BYTEPS_REDUCE_OK;
-  std::vector<const void*> srcs(n);
-  for (int k = 0; k < n; ++k) srcs[k] = g == root ? at(pushes[k], mine.lo * es) : recv_slots[k];
   return fold_any_alias(dst, srcs.data(), n, mine.n() * es, dtype, mode, s);
 }
 
@@ -601,12 +607,15 @@ int byteps_shard_reduce_root(byteps_shard_comm* c, int root, const void* local,
     for (int r = 0; r < W; ++r)
       if (r != g) ops.push_back({false, r, nullptr, recv_slots[r], bytes});
   }
+  std::vector<const void*> srcs(W);
+  if (g == root) {
+    for (int r = 0; r < W; ++r) srcs[r] = r == g ? local : recv_slots[r];
+    if ((rc = fold_alias_check(dst, srcs.data(), W, bytes))) return rc;
+  }
   if ((rc = use_device(c))) return rc;
   hipStream_t s = to_stream(stream);
   if ((rc = run_group(c, ops, s))) return rc;
   if (g != root) return BYTEPS_REDUCE_OK;
-  std::vector<const void*> srcs(W);
-  for (int r = 0; r < W; ++r) srcs[r] = r == g ? local : recv_slots[r];
   return fold_any_alias(dst, srcs.data(), W, bytes, dtype, mode, s);
 }
 

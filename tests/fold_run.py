@@ -5,7 +5,14 @@ Operands puts every source and dst `offset` bytes past a 256-byte boundary of
 a buffer of its own, filled with 0xEE; dst is prefilled with 0x5A (or is
 srcs[0], in place).  result() returns dst's bytes after checking that the
 guard bytes on both sides of dst and of every source are still 0xEE and that
-no source changed (but srcs[0] when it is dst)."""
+no source changed (but srcs[0] when it is dst).
+
+The operand map says which operands are one buffer: `alias` is the index of
+the source that dst is (None: a buffer of its own; `inplace=True` is alias 0),
+and `same` lists groups of source indices that share one buffer (duplicate
+sources; a group's offsets are its first member's, and load() takes the same
+bytes for every member).  The guarantees hold per distinct buffer: guard bytes
+around each, and every buffer that is not dst's unchanged."""
 import numpy as np
 import pytest
 
@@ -17,13 +24,27 @@ PAD = 256           # guard bytes before and after every operand
 
 class Operands:
     def __init__(self, dev, n_src: int, L: int, src_offs=None, dst_off: int = 16,
-                 inplace: bool = False):
-        self.L, self.inplace = L, inplace
+                 inplace: bool = False, alias=None, same=()):
+        if inplace:
+            assert alias in (None, 0)
+            alias = 0
+        self.L, self.alias, self.inplace = L, alias, alias is not None
         self.src_offs = list(src_offs) if src_offs is not None else [0] * n_src
         assert len(self.src_offs) == n_src
-        self.src_bufs = [self._buffer(dev, o) for o in self.src_offs]
-        self.dst_off = self.src_offs[0] if inplace else dst_off
-        self.dst_buf = self.src_bufs[0] if inplace else self._buffer(dev, dst_off)
+        # first[k]: the source whose buffer source k is
+        self.first = list(range(n_src))
+        for group in same:
+            for k in group:
+                assert self.first[k] == k and k >= group[0]
+                self.first[k] = group[0]
+                self.src_offs[k] = self.src_offs[group[0]]
+        self.src_bufs = []
+        for k, o in enumerate(self.src_offs):
+            self.src_bufs.append(self._buffer(dev, o) if self.first[k] == k
+                                 else self.src_bufs[self.first[k]])
+        assert alias is None or 0 <= alias < n_src
+        self.dst_off = dst_off if alias is None else self.src_offs[alias]
+        self.dst_buf = self._buffer(dev, dst_off) if alias is None else self.src_bufs[alias]
         self.held = None            # host bytes of the sources, as loaded
         for b in self.src_bufs + [self.dst_buf]:
             assert b.data_ptr() % 256 == 0
@@ -62,8 +83,11 @@ class Operands:
         self.held = ins
         if not self.L:
             return self
-        for v, x in zip(self.src_views, ins):
+        for k, (v, x) in enumerate(zip(self.src_views, ins)):
             assert len(x) == self.L
+            if self.first[k] != k:          # a duplicate: its group's one input
+                assert x is ins[self.first[k]], f"sources {self.first[k]} and {k} share a buffer"
+                continue
             v.copy_(x if isinstance(x, torch.Tensor) else torch.from_numpy(x), non_blocking=True)
         if not self.inplace:
             self.dst_view.fill_(FILL)
@@ -75,7 +99,7 @@ class Operands:
         assert bool((whole[:lo] == GUARD).all()), "bytes before dst changed"
         assert bool((whole[lo + self.L:] == GUARD).all()), "bytes after dst changed"
         for k, (b, o, x) in enumerate(zip(self.src_bufs, self.src_offs, self.held)):
-            if self.inplace and k == 0:
+            if b is self.dst_buf or self.first[k] != k:     # dst's buffer; checked with its first
                 continue
             h = b.cpu().numpy()
             x = x.numpy() if isinstance(x, torch.Tensor) else x
@@ -85,10 +109,53 @@ class Operands:
         return whole[lo:lo + self.L]
 
 
-def run_sum_n(red, dev, dt, ins, L, src_offs=None, dst_off=16, inplace=False, mode=0):
+    def untouched(self, what=""):
+        """After a refused call: every buffer, dst's included, holds what
+        load() left — guard bytes, the sources' bytes, 0x5A in a dst of its own."""
+        bufs = [(b, o, x) for k, (b, o, x) in
+                enumerate(zip(self.src_bufs, self.src_offs, self.held)) if self.first[k] == k]
+        if self.alias is None:
+            bufs.append((self.dst_buf, self.dst_off, np.full(self.L, FILL, np.uint8)))
+        for i, (b, o, x) in enumerate(bufs):
+            h = b.cpu().numpy()
+            x = x.numpy() if isinstance(x, torch.Tensor) else x
+            assert np.array_equal(h[PAD + o:PAD + o + self.L], x), f"{what}: buffer {i} changed"
+            assert bool((h[:PAD + o] == GUARD).all()) and bool((h[PAD + o + self.L:] == GUARD).all()), \
+                f"{what}: guard bytes of buffer {i} changed"
+
+
+class Guarded:
+    """One device buffer of L bytes `off` bytes past a 256-byte boundary
+    between 0xEE guard bytes (a rank's whole vector or a receive slot of the
+    shard tests): `ptr`, load(host bytes), and bytes() -> its L bytes after
+    checking the guard bytes."""
+
+    def __init__(self, dev, L: int, off: int = 0):
+        self.L, self.off = L, off
+        self.buf = torch.full((PAD + off + L + PAD,), GUARD, dtype=torch.uint8, device=dev)
+        assert self.buf.data_ptr() % 256 == 0
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr() + PAD + self.off
+
+    def load(self, x):
+        self.buf[PAD + self.off:PAD + self.off + self.L].copy_(torch.from_numpy(x))
+        return self
+
+    def bytes(self, what="") -> np.ndarray:
+        h = self.buf.cpu().numpy()
+        lo = PAD + self.off
+        assert bool((h[:lo] == GUARD).all()) and bool((h[lo + self.L:] == GUARD).all()), \
+            f"{what}: guard bytes changed"
+        return h[lo:lo + self.L]
+
+
+def run_sum_n(red, dev, dt, ins, L, src_offs=None, dst_off=16, inplace=False, mode=0,
+              alias=None, same=()):
     """byteps_reduce_sum_n of host byte arrays `ins` at byte offsets `src_offs`
     into dst at `dst_off` (or into srcs[0]); Operands' checks; dst's L bytes."""
-    ops = Operands(dev, len(ins), L, src_offs, dst_off, inplace).load(ins)
+    ops = Operands(dev, len(ins), L, src_offs, dst_off, inplace, alias, same).load(ins)
     torch.cuda.synchronize()
     red.sum_n(ops.dst, ops.srcs, L, dt, mode=mode)
     torch.cuda.synchronize()

@@ -1,5 +1,6 @@
 """Shapes and inputs of the reference-mode fold tests at the real tile sizes
-(tests/test_fold_tiles_gpu.py, tests/test_fold_policy_gpu.py), and what the
+(tests/test_fold_tiles_gpu.py, tests/test_fold_policy_gpu.py, and with
+operands that are one buffer tests/test_fold_alias_gpu.py), and what the
 launch rules must make of them (tests/test_fold_shapes.py checks that on the
 CPU).  A helper module (pure numpy; no torch, no GPU), not a conftest.
 
@@ -71,9 +72,45 @@ POLICY_BLOCKQ_DTYPES = [_F32, _F16]
 POLICY_BLOCKQ_VPT = 1
 
 
+# Aliased operands (tests/test_fold_alias_gpu.py): (dtype, sources, shape, the
+# source index that dst is or None, groups of source indices in one buffer).
+_DUP_CASES = [(3, "V4"), (8, "V2"), (9, "V2"), (16, "V2")]
+
+
+def _dup_groups(n: int, first: int) -> tuple:
+    """A neighbouring pair from source `first` on; above 8 sources also a
+    pair whose second member lies in the second load group."""
+    return ((first, first + 1),) + (((first + 2, n - 1),) if n > 8 else ())
+
+
+# sum_n(dst, [a, a, b, ...]) and sum_n(a, [a, b, b, ...])
+ALIAS_DUP = [(dt, n, s, alias, _dup_groups(n, 0 if alias is None else 1))
+             for dt in (_F32, _F16, _BF16) for n, s in _DUP_CASES for alias in (None, 0)]
+# dst is srcs[k], k > 0 (fold_any_alias; the shard ABI alone gets there):
+# reduce_scatter in place at world 3 (k = rank), reduce_root in place at
+# world 8 with root 5, and landed pushes folded into one of them, where k lies
+# in the second load group of the tiles and of fold_elements
+ALIAS_SCATTER = [(dt, 3, "V4", k, ()) for dt in (_F32, _F16) for k in (1, 2)]
+ALIAS_ROOT = [(dt, 8, "V2", 5, ()) for dt in (_F16, _BF16, _F64)]
+ALIAS_LANDED = ([(dt, 9, "V2", 8, ()) for dt in (_F32, _F16)]
+                + [(dt, 12, "SMALL", 9, ()) for dt in (_F32, _F16, _BF16)])
+ALIAS = ALIAS_DUP + ALIAS_SCATTER + ALIAS_ROOT + ALIAS_LANDED
+# byteps_reduce_sum3 and byteps_reduce_sum(dst, dst): two sources
+SUM3_DTYPES = [_F32, _F64, _F16, _BF16, _I32, _U8, _I64]
+SUM3_CASES = ([(dt, 2, "V4") for dt in SUM3_DTYPES] + [(dt, 2, "SMALL") for dt in (_F16, _F32)]
+              + [(dt, 2, "SMALL", 8) for dt in (_F16, _F32)])
+DOUBLING = [(dt, 2, "V4") for dt in (_F32, _F16, _I32)]
+
+
 def case_id(case) -> str:
     dt, n, shape = case[:3]
     return f"{DType(dt).name}-n{n}-{shape}" + (f"-off{case[3]}" if len(case) > 3 else "")
+
+
+def alias_id(case) -> str:
+    dt, n, shape, alias, same = case
+    return (case_id((dt, n, shape)) + ("" if alias is None else f"-dst{alias}")
+            + "".join("-same" + "_".join(map(str, g)) for g in same))
 
 
 def ns_kernel(n: int) -> int:
@@ -238,6 +275,57 @@ def fold_case(dt, n_src: int, shape: str, off: int = 0):
     return _KEPT[key]
 
 
+def share(ins: list, same) -> list:
+    """`ins` with every member of a group of `same` replaced by the group's
+    first input, the same array object: duplicates share their input."""
+    out = list(ins)
+    for group in same:
+        for k in group[1:]:
+            out[k] = out[group[0]]
+    return out
+
+
+_ALIAS_WANT: dict = {}
+
+
+def alias_case(case):
+    """(sources, kinds, expected bytes, regions) of a case of ALIAS: fold_case's
+    inputs with the duplicates sharing theirs, and the oracle's fold of that
+    list (which holds the same array twice for a duplicate).  Which source dst
+    is does not enter: the fold is element-wise."""
+    dt, n, shape, _, same = case
+    ins, kind, want, reg = fold_case(dt, n, shape)
+    if not same:
+        return ins, kind, want, reg
+    ins = share(ins, same)
+    key = (int(dt), n, shape, same)
+    if key not in _ALIAS_WANT:
+        _ALIAS_WANT[key] = oracle_fold(dt, ins, len(want))
+    return ins, kind, _ALIAS_WANT[key], reg
+
+
+def scatter_vectors(dt, world: int, shape: str, seed: int):
+    """Every rank's whole vector for a reduce_scatter whose owned slices have
+    `shape` each: (E, per-rank byte arrays, kinds, per-owner byte offset inside
+    the 16-byte line).  E = world * n_elems(shape), so owner q's slice begins
+    at (q * n_elems * element size) % 16: probes are placed per slice, for the
+    head that offset gives (regions)."""
+    es = elem_size(dt)
+    vecs, vpt = SHAPES[shape]
+    per = n_elems(dt, vecs)
+    E = world * per
+    parts, kinds, offs = [], [], []
+    for q in range(world):
+        off = (q * per * es) % 16
+        reg = regions(dt, per, head_elems(dt, off), vpt)
+        ins, kind = probe_inputs(dt, per, world, seed + q, reg)
+        parts.append(ins)
+        kinds.append(kind)
+        offs.append(off)
+    full = [np.concatenate([parts[q][r] for q in range(world)]) for r in range(world)]
+    return E, full, np.concatenate(kinds), offs
+
+
 # ------------------------------------------------------------------- tables ----
 # The ragged table of test_parity_gpu.test_batched_ragged_mixed_table:
 # (elements, sources, byte offsets of dst + sources or None, class of the
@@ -288,15 +376,24 @@ def bucket_regions(dt, n: int, offs, n_src: int, vpt: int) -> dict:
     return regions(dt, n, head, vpt)
 
 
-def table_inputs(dt, spec: list, vpt: int, seed: int):
+# Duplicated sources of the tables (bucket index, in ragged_spec and in the
+# block queue's MIXED alike -> groups): the 8-source bucket of the register
+# path and the 9-source one of the pointer-array path, there across its two
+# load groups.
+TABLE_DUPS = {0: ((0, 1),), 1: ((2, 8),)}
+
+
+def table_inputs(dt, spec: list, vpt: int, seed: int, dups=None):
     """Per bucket of `spec`: (sources, kinds, expected bytes); bucket
-    TRAILING_BUCKET gets 3 trailing bytes per source."""
+    TRAILING_BUCKET gets 3 trailing bytes per source.  `dups`: bucket index ->
+    groups of sources that share one input (share)."""
     out = []
     for i, (ne, n_src, offs, cls) in enumerate(spec):
         reg = bucket_regions(dt, ne, offs, n_src, vpt)
         ins, kind = probe_inputs(dt, ne, n_src, seed + i, reg, cls)
         if i == TRAILING_BUCKET:
             ins = [np.concatenate([x, np.array([k, 7, 9], np.uint8)]) for k, x in enumerate(ins)]
+        ins = share(ins, (dups or {}).get(i, ()))
         out.append((ins, kind, oracle_fold(dt, ins, len(ins[0]))))
     return out
 

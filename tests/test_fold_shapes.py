@@ -35,7 +35,24 @@ def fold_cases():
         out += [((dt, n, "SMALL"), tuning) for dt in ALL_DTYPES for n in fs.POLICY_SMALL_N]
         out += [(c, tuning) for c in fs.POLICY_BIG]
     out += [(c, NT) for c in fs.POLICY_NT_EXTRA]
+    # the aliased folds (tests/test_fold_alias_gpu.py): which operands are one
+    # buffer does not enter the launch rules
+    out += [(c[:3], DEFAULT) for c in fs.ALIAS]
+    out += [(c, DEFAULT) for c in fs.SUM3_CASES + fs.DOUBLING]
     return list(dict.fromkeys(out))
+
+
+SCATTER_WORLD = 3
+
+
+def scatter_slices():
+    """(dtype, elements, byte offset) of every owner's slice of the in-place
+    reduce_scatter of test_fold_alias_gpu (fold_shapes.scatter_vectors)."""
+    out = []
+    for dt in dict.fromkeys(c[0] for c in fs.ALIAS_SCATTER):
+        per = fs.n_elems(dt, fs.SHAPES["V4"][0])
+        out += [(dt, per, (q * per * elem_size(dt)) % 16) for q in range(SCATTER_WORLD)]
+    return out
 
 
 def table_cases():
@@ -90,20 +107,23 @@ def rules(request, tmp_path_factory):
                     os.path.join(ROOT, "prophet_amd", "csrc", "bpsr_table.cpp"),
                     os.path.join(ROOT, "tests", "cpp", "fold_shapes.cpp"), "-o", str(exe)],
                    check=True)
-    folds, tables = fold_cases(), table_cases()
+    folds, tables, slices = fold_cases(), table_cases(), scatter_slices()
     lines = [fold_line(*c) for c in folds]
     for t in tables:
         lines += table_lines(*t)
+    lines += [f"fold {int(dt)} {ne} {SCATTER_WORLD} {off} {DEFAULT[0]} {DEFAULT[1]}"
+              for dt, ne, off in slices]
     r = subprocess.run([str(exe)], input="\n".join(lines) + "\n", capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = r.stdout.splitlines()
-    assert out[-1] == "done" and len(out) == len(folds) + len(tables) + 1, out[-3:]
+    assert out[-1] == "done" and len(out) == len(folds) + len(tables) + len(slices) + 1, out[-3:]
     got_f = {c: parse(x) for c, x in zip(folds, out)}
     got_t = {c: parse(x) for c, x in zip(tables, out[len(folds):])}
-    assert all(w == "fold" for w, _ in got_f.values())
+    got_s = {c: parse(x) for c, x in zip(slices, out[len(folds) + len(tables):])}
+    assert all(w == "fold" for w, _ in list(got_f.values()) + list(got_s.values()))
     assert all(w == "table" for w, _ in got_t.values()), [x for x in out if "error" in x]
-    return {c: v for c, (_, v) in got_f.items()}, {c: v for c, (_, v) in got_t.items()}
+    return tuple({c: v for c, (_, v) in got.items()} for got in (got_f, got_t, got_s))
 
 
 def test_shapes_are_what_they_say():
@@ -122,7 +142,7 @@ def test_shapes_are_what_they_say():
 
 
 def test_every_sum_n_case_gets_its_tile_size_kernel_and_policy(rules):
-    folds, _ = rules
+    folds, _, _ = rules
     seen = set()
     for (case, tuning), got in folds.items():
         dt, n, shape = case[:3]
@@ -164,7 +184,7 @@ def test_every_sum_n_case_gets_its_tile_size_kernel_and_policy(rules):
 
 
 def test_every_table_gets_its_tile_size_policy_and_record_kinds(rules):
-    _, tables = rules
+    _, tables, _ = rules
     for (kind, dt, vpt, tuning), got in tables.items():
         what = (kind, DType(dt).name, vpt, tuning)
         if vpt:
@@ -306,3 +326,82 @@ def test_table_buckets_hold_nan_results(dt, vpt):
             assert (kind >= 0).any()
         else:
             assert (kind < 0).all()
+
+
+# ------------------------------------------------------- aliased operands ----
+
+def test_every_alias_case_gets_its_tile_size_kernel_and_policy(rules):
+    """fold_shapes.ALIAS: the tile size its shape names, the write-through
+    policy, full tiles and a partial one, and between them every kernel
+    (NS 8, 16 and generic with one and with two load groups) with a
+    duplicate and with dst at a later source; the owners' slices of the
+    in-place reduce_scatter keep 2,047 full tiles of VPT 4 behind the heads
+    their byte offsets give, and one of them at least is misaligned."""
+    folds, _, slices = rules
+    seen = set()
+    for case in fs.ALIAS:
+        dt, n, shape, alias, same = case
+        got = folds[(case[:3], DEFAULT)]
+        vecs, vpt = fs.SHAPES[shape]
+        assert (got["vpt"], got["pol"], got["aligned"]) == (vpt, fs.POL_WT, 1), fs.alias_id(case)
+        assert got["full"] == vecs // (fs.K_BLOCK * vpt) and got["partial"] > 0 and got["tail"] > 0
+        assert alias is None or 0 <= alias < n
+        assert all(0 <= k < n for g in same for k in g)
+        assert alias is None or all(alias not in g for g in same), "dst would alias two sources"
+        seen.add((vpt, fs.ns_kernel(n), n > 8, "dup" if same else "later" if alias else "first"))
+    for key in ((4, 0, False, "dup"), (2, 8, False, "dup"), (2, 0, True, "dup"),
+                (2, 16, True, "dup"), (4, 0, False, "later"), (2, 8, False, "later"),
+                (2, 0, True, "later"), (1, 0, True, "later")):
+        assert key in seen, key
+    assert any(a is not None and a >= 8 for _, _, _, a, _ in fs.ALIAS)     # fold_elements' group 2
+    for (dt, ne, off), got in slices.items():
+        assert (got["vpt"], got["pol"], got["aligned"]) == (4, fs.POL_WT, 1), (dt, off)
+        assert got["full"] == 2047 and got["partial"] > 0 and got["tail"] > 0, (dt, off)
+        assert got["head"] == fs.head_elems(dt, off)
+    for dt in dict.fromkeys(s[0] for s in slices):
+        assert any(off for d, _, off in slices if d == dt), "no misaligned slice"
+    # two sources: n <= 4 is tuned to 16 KiB tiles
+    for case in fs.SUM3_CASES + fs.DOUBLING:
+        assert folds[(case, DEFAULT)]["vpt"] == fs.SHAPES[case[2]][1]
+
+
+@pytest.mark.parametrize("case", fs.ALIAS_SCATTER + fs.ALIAS_ROOT + fs.ALIAS_LANDED,
+                         ids=fs.alias_id)
+def test_aliased_source_holds_nans_a_peer_holds_too(case):
+    """dst at srcs[k], k > 0: in every probed range the aliased source holds
+    NaNs at elements where another source holds one too and the result is a
+    NaN, so the exact replay re-reads the source that dst overwrites."""
+    dt, n, shape, alias, _ = case
+    ins, kind, want, reg = fs.alias_case(case)
+    mine = op.is_nan(dt, ins[alias])
+    peer = np.zeros_like(mine)
+    for k in range(n):
+        if k != alias:
+            peer |= op.is_nan(dt, ins[k])
+    both = mine & peer & op.is_nan(dt, want)
+    for name, (lo, hi) in reg.items():
+        assert both[lo:hi].any(), name
+
+
+def test_scatter_vectors_hold_nans_in_every_slice_of_every_rank():
+    world = SCATTER_WORLD
+    for dt in dict.fromkeys(c[0] for c in fs.ALIAS_SCATTER):
+        E, full, kind, offs = fs.scatter_vectors(dt, world, "V4", 77)
+        es = elem_size(dt)
+        assert E % world == 0 and all(len(v) == E * es for v in full) and any(offs)
+        per = E // world
+        nan = [op.is_nan(dt, v) for v in full]
+        for q in range(world):
+            sl = slice(q * per, (q + 1) * per)
+            others = np.logical_or.reduce([nan[r][sl] for r in range(world) if r != q])
+            assert (nan[q][sl] & others).any(), (dt, q)
+
+
+@pytest.mark.parametrize("case", fs.ALIAS_DUP, ids=fs.alias_id)
+def test_duplicates_share_their_input_and_change_the_fold(case):
+    dt, n, shape, _, same = case
+    ins, _, want, _ = fs.alias_case(case)
+    for g in same:
+        assert all(ins[k] is ins[g[0]] for k in g)
+    assert len({id(x) for x in ins}) == n - sum(len(g) - 1 for g in same)
+    assert not np.array_equal(want, fs.fold_case(dt, n, shape)[2])

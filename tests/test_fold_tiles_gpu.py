@@ -97,22 +97,24 @@ def test_sum_n_coaligned_byte_offset(red, dev, case):
 _TABLE_HOST = {}        # (dtype, vpt, seed) -> fold_shapes.table_inputs, shared
 
 
-def table_host(dt, vpt, seed):
-    key = (int(dt), vpt, seed)
+def table_host(dt, vpt, seed, dups=None):
+    key = (int(dt), vpt, seed, bool(dups))
     if key not in _TABLE_HOST:
-        _TABLE_HOST[key] = fs.table_inputs(dt, fs.table_spec(dt, vpt), vpt, seed)
+        _TABLE_HOST[key] = fs.table_inputs(dt, fs.table_spec(dt, vpt), vpt, seed, dups)
     return _TABLE_HOST[key]
 
 
-def check_batched(red, dev, dt, vpt, plan):
+def check_batched(red, dev, dt, vpt, plan, dups=None):
     """The ragged table of fold_shapes.table_spec(dt, vpt) as a one-off launch
-    or as a plan, launched a second time on refilled data."""
+    or as a plan, launched a second time on refilled data.  `dups`: bucket
+    index -> groups of sources that are one buffer (fold_shapes.TABLE_DUPS)."""
     spec = fs.table_spec(dt, vpt)
-    host = table_host(dt, vpt, 300)
+    host = table_host(dt, vpt, 300, dups)
     ops = []
-    for (ne, n, offs, _), (ins, _, want) in zip(spec, host):
+    for i, ((ne, n, offs, _), (ins, _, want)) in enumerate(zip(spec, host)):
         o = fs.bucket_offsets(offs, n)
-        ops.append(Operands(dev, n, len(want), o[1:], o[0]).load(ins))
+        ops.append(Operands(dev, n, len(want), o[1:], o[0],
+                            same=(dups or {}).get(i, ())).load(ins))
     buckets = [o.bucket for o in ops]
 
     def check(host, what):
@@ -129,7 +131,7 @@ def check_batched(red, dev, dt, vpt, plan):
     p.launch()
     torch.cuda.synchronize()
     check(host, "plan")
-    host = table_host(dt, vpt, 900)         # new data at the same addresses
+    host = table_host(dt, vpt, 900, dups)   # new data at the same addresses
     for o, (ins, _, _) in zip(ops, host):
         o.load(ins)
     torch.cuda.synchronize()
@@ -164,15 +166,17 @@ class ProbeTable(Table):
     float buckets (placed for tiles of 256 * vpt vectors) and the oracle's
     fold as the expectation."""
 
-    def __init__(self, dev, dt, blocks, vpt):
+    def __init__(self, dev, dt, blocks, vpt, dups=None):
         self.dt, self.es, self.vpt = dt, elem_size(dt), vpt
+        self.dups = dups or {}      # bucket index -> groups of sources in one buffer
         self.blocks, self.views, self.ops, self.offs = [], [], [], []
         for blk in blocks:
             out = []
             for ne, n, cls in blk:
                 offs = fs.blockq_offsets(dt, ne, n)
                 o = fs.bucket_offsets(offs, n)
-                ops = Operands(dev, n, ne * self.es, o[1:], o[0])
+                ops = Operands(dev, n, ne * self.es, o[1:], o[0],
+                               same=self.dups.get(len(self.ops), ()))
                 out.append(ops.bucket)
                 self.ops.append(ops)
                 self.offs.append(offs)
@@ -180,17 +184,19 @@ class ProbeTable(Table):
             self.blocks.append(out)
 
     def host_inputs(self, seed):
-        key = (int(self.dt), self.vpt, seed)
+        key = (int(self.dt), self.vpt, seed, bool(self.dups))
         if key not in _BQ_HOST:
             rows = []
             for i, ((_, _, L, ne, n, cls), offs) in enumerate(zip(self.views, self.offs)):
                 reg = fs.bucket_regions(self.dt, ne, offs, n, self.vpt)
                 ins, kind = fs.probe_inputs(self.dt, ne, n, seed + i, reg, cls)
+                ins = fs.share(ins, self.dups.get(i, ()))
                 rows.append((ins, kind, fs.oracle_fold(self.dt, ins, L)))
             _BQ_HOST[key] = rows
         rows = _BQ_HOST[key]
         self.kinds = [k for _, k, _ in rows]
-        return ([[torch.from_numpy(x).pin_memory() for x in ins] for ins, _, _ in rows],
+        pinned = [[torch.from_numpy(x).pin_memory() for x in ins] for ins, _, _ in rows]
+        return ([fs.share(ps, self.dups.get(i, ())) for i, ps in enumerate(pinned)],
                 [w for _, _, w in rows])
 
     def upload(self, pushes, stream=None):
@@ -202,9 +208,9 @@ class ProbeTable(Table):
             assert_elements(self.dt, ops.result(), w, self.kinds[i], f"bucket {i}")
 
 
-def check_blockq(red, dev, dt, shape, vpt, iterations):
+def check_blockq(red, dev, dt, shape, vpt, iterations, dups=None):
     """Everything released up front, `iterations` launches on different data."""
-    tab = ProbeTable(dev, dt, MIXED, vpt)
+    tab = ProbeTable(dev, dt, MIXED, vpt, dups)
     q = red.make_blockq(tab.blocks, dt, MODE_REFERENCE)
     q.config(wg_per_cu=shape)
     for it in range(iterations):
