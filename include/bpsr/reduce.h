@@ -73,6 +73,9 @@ extern "C" {
  *    additive, still 5: byteps_reduce_cast_plan_measure / byteps_reduce_clip_record /
  *                       byteps_reduce_cast_plan_decompress_scaled
  *                       (byteps_clip_record: clip by global norm and unscale
+ *                       inside the decompress)
+ *    additive, still 5: byteps_reduce_cast_plan_create_sgd / _cast_plan_apply_sgd
+ *                       (byteps_cast_sgd_desc, byteps_sgd_hyper: the SGD step
  *                       inside the decompress) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
@@ -588,6 +591,65 @@ int byteps_reduce_clip_record(const double* rows, int nrows, double max_norm, do
                               const float* inv_scale, byteps_clip_record* out, void* stream);
 int byteps_reduce_cast_plan_decompress_scaled(byteps_reduce_cast_plan* plan, int divisor,
                                               const float* mult, void* stream);
+
+/* The SGD step inside the decompress: the last pull's result goes straight
+ * into the parameters.  An SGD plan's segments name the f32 parameter, the
+ * 2-byte wire buffer and the f32 momentum buffer; _apply_sgd is ONE launch
+ * that reads all three and writes the parameter and the momentum in place
+ * (2 + 4 + 4 bytes read, 4 + 4 written an element).  The gradient is never
+ * written.  Per element, every line one IEEE f32 operation, rounded to nearest
+ * even, subnormals kept, nothing fused; lr, mu (momentum), wd (weight_decay)
+ * and mult are f32:
+ *
+ *   h  = the wire value; for divisor > 1: wire(f32(h) / divisor), the divide
+ *        of _decompress
+ *   g  = f32(h)                        exact
+ *   g  = g * mult                      only with a record (the rounding of
+ *                                      _cast_plan_decompress_scaled)
+ *   g  = g + wd * p                    only when wd != 0
+ *   m' = mu * m + g
+ *   d  = nesterov ? g + mu * m' : m'
+ *   p' = p - lr * d
+ *
+ * The momentum buffer always exists; zeroed, the first step is torch's
+ * buf = grad, as values.  mu == 0 follows the formula literally.  NaN payloads
+ * are not pinned, NaN-ness is.  Pinned to prophet_amd/sgd.py, which agrees
+ * with torch.optim.SGD wherever every product and sum is exact.
+ *
+ * `rec`: null, or a byteps_clip_record in device memory (typically the one
+ * byteps_reduce_clip_record wrote earlier on the same stream); its mult scales
+ * the gradient.  With skip_nonfinite != 0 and rec->nonfinite != 0 the launch
+ * writes nothing — p and m keep every byte — with no host round trip.
+ *
+ * _create_sgd: the plan is the opaque cast plan, _destroy frees it.
+ *   Parameters and momenta are FLOAT32; wire_dtype is FLOAT16 or BFLOAT16,
+ *   anything else EDTYPE.  All 3 * nsegs byte ranges must be pairwise disjoint
+ *   and a null pointer with nelem > 0 is EARGS.  On an SGD plan every other
+ *   _cast_plan_* call (_compress, _compress_sr, _decompress,
+ *   _decompress_stats, _measure, _decompress_scaled) is EARGS: it would write
+ *   gradients over parameters.  Measure through a plain plan over the same
+ *   wire buffers.
+ * _apply_sgd: asynchronous on `stream`; a plan without records succeeds
+ *   without a launch.  EARGS before any launch, nothing written: a null plan,
+ *   a plan that is not an SGD plan, a null h, divisor < 1, lr not finite,
+ *   momentum not in [0, 1) (or NaN), weight_decay < 0 or not finite, nesterov
+ *   with momentum == 0, skip_nonfinite with a null rec, a rec that is not
+ *   8-byte aligned or that lies inside any byte range of the plan's segments. */
+typedef struct byteps_cast_sgd_desc {
+  void* param;
+  void* half;
+  void* momentum;
+  size_t nelem;
+} byteps_cast_sgd_desc;
+int byteps_reduce_cast_plan_create_sgd(const byteps_cast_sgd_desc* segs, int nsegs, int wire_dtype,
+                                       byteps_reduce_cast_plan** out);
+typedef struct byteps_sgd_hyper {
+  float lr, momentum, weight_decay;
+  int nesterov;
+} byteps_sgd_hyper;
+int byteps_reduce_cast_plan_apply_sgd(byteps_reduce_cast_plan* plan, int divisor,
+                                      const byteps_sgd_hyper* h, const byteps_clip_record* rec,
+                                      int skip_nonfinite, void* stream);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

@@ -109,6 +109,18 @@ multipliers (:func:`clip_record` below is the definition), and
 (``byteps_reduce_cast_plan_decompress_scaled``) — so an unclipped gradient is
 never written and no pass reads the gradients again.  The record is returned;
 for device tensors it stays on the device.
+
+``apply_sgd_many(params, compressed, momenta, divisor, lr=, ...)`` goes one
+step further: the SGD step itself runs inside the
+decompress.  One launch per device reads the wire, the float32 parameter and
+its momentum buffer and writes the last two in place — 18 bytes an element,
+against 6 for the scaled decompress plus 20 for a fused optimizer — and the
+gradient is never written.  ``prophet_amd/sgd.py`` is the definition, bit for
+bit.  With ``record=`` the gradient is multiplied by the clip record's
+``mult`` first, and with ``skip_nonfinite`` a record that counted a
+non-finite value leaves parameters and momenta untouched, decided on the
+device (GradScaler's skipped step with no host synchronisation).  There is no
+``torch.library`` op for it either: an SGD plan owns raw device pointers.
 """
 from __future__ import annotations
 
@@ -285,10 +297,35 @@ class CastPlanCache:
             old.close()                   # waits for its launches in flight
         return plan
 
+    def get_sgd(self, triples, wire_dtype: int = 2):
+        """The SGD plan (``GpuReducer.sgd_plan``) over ``triples`` of flat
+        ``(param, half, momentum)`` device tensors on the current device, built
+        on a miss.  Its key is marked: the error-feedback plan over the same
+        three addresses is another plan."""
+        key = ("sgd", int(wire_dtype)) + tuple(
+            (int(p.data_ptr()), int(h.data_ptr()), int(p.numel()), int(m.data_ptr()))
+            for p, h, m in triples)
+        plan = self._plans.get(key)
+        if plan is not None:
+            self._plans.move_to_end(key)
+            return plan
+        plan = _new_sgd_plan(triples, wire_dtype)
+        self.built += 1
+        self._plans[key] = plan
+        while len(self._plans) > self.capacity:
+            _, old = self._plans.popitem(last=False)
+            old.close()
+        return plan
+
     def close(self) -> None:
         while self._plans:
             _, plan = self._plans.popitem(last=False)
             plan.close()
+
+
+def _new_sgd_plan(triples, wire_dtype: int = 2):
+    from .torch_ops import _red
+    return _red().sgd_plan([(p, h, int(p.numel()), m) for p, h, m in triples], wire_dtype)
 
 
 def _new_plan(wide_dtype: int, pairs, wire_dtype: int = 2):
@@ -680,6 +717,134 @@ class _CastCompressor(Compressor):
         _cast_many(cls, list(zip(outs, compressed)), False, divisor, plans, extras=extras,
                    stats=stats, measure=True)
         return stats
+
+    @classmethod
+    def _check_sgd_segment(cls, i: int, param, half, mom) -> bool:
+        """The operands of one SGD segment; True when they are on a device."""
+        dev = [_on_device(x) for x in (param, half, mom)]
+        if any(dev) != all(dev):
+            raise ValueError(f"apply_sgd: tensor {i}'s parameter, compressed tensor and momentum "
+                             f"live in one place, a device or the host")
+        if not _is_f32(param) or not _is_f32(mom):
+            raise ValueError(f"apply_sgd: tensor {i} needs a float32 parameter and a float32 "
+                             f"momentum buffer, got {param.dtype} and {mom.dtype}")
+        size = (lambda x: int(x.numel()) if _is_torch(x) else int(x.size))
+        for x in (half, mom):
+            if size(x) != size(param):
+                raise ValueError(f"apply_sgd: tensor {i}'s operands differ in size")
+        if dev[0]:
+            if half.dtype != cls.wire_torch_dtype():
+                raise ValueError(f"apply_sgd: the compressed tensor must be {cls.WIRE}, "
+                                 f"got {half.dtype}")
+            if not (param.device == half.device == mom.device):
+                raise ValueError(f"apply_sgd: tensor {i}'s operands are on different devices")
+            if not (param.is_contiguous() and half.is_contiguous() and mom.is_contiguous()):
+                raise ValueError(f"apply_sgd: tensor {i} needs contiguous operands")
+        else:
+            for x in (param, half, mom):
+                ok = x.is_contiguous() if _is_torch(x) else x.flags["C_CONTIGUOUS"]
+                if not ok:
+                    raise ValueError(f"apply_sgd: tensor {i} needs contiguous operands")
+            want = cls.wire_torch_dtype() if _is_torch(half) else cls.NUMPY
+            if half.dtype != want:
+                raise ValueError(f"apply_sgd: the compressed tensor must be {cls.WIRE}, "
+                                 f"got {half.dtype}")
+        return dev[0]
+
+    @classmethod
+    def apply_sgd_many(cls, params, compressed, momenta, divisor: int = 1, *, lr,
+                       momentum: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                       record=None, skip_nonfinite: bool = False,
+                       plans: CastPlanCache | None = None):
+        """The SGD step inside the decompress: ``params[i]`` and
+        ``momenta[i]`` (float32) are updated in place from ``compressed[i]``
+        under ``prophet_amd.sgd.sgd_step`` — the gradient
+        ``decompress_into(_, compressed[i], divisor)`` would write is never
+        written.  Device tensors are grouped by device, each group ONE launch
+        of an SGD plan (``byteps_reduce_cast_plan_apply_sgd``) on the current
+        stream; CPU tensors and numpy arrays go through ``sgd.py``.
+
+        ``record``: a clip record — ``reducer.ClipRecord`` on the tensors'
+        device, or :class:`ClipValues` for host tensors — whose ``mult``
+        scales the gradient as ``decompress_many_with(scale=)`` does.  With
+        ``skip_nonfinite`` a record whose ``nonfinite`` is not 0 leaves every
+        byte of ``params`` and ``momenta``: decided on the device for device
+        tensors, with no host round trip; the host path reads the record.
+        Returns ``params``."""
+        from .sgd import check_hyper, sgd_step
+        n = len(params)
+        if len(compressed) != n or len(momenta) != n:
+            raise ValueError("apply_sgd_many: as many compressed tensors and momenta as parameters")
+        if int(divisor) < 1:
+            raise ValueError(f"divisor {divisor} < 1")
+        check_hyper(lr, momentum, weight_decay, nesterov)
+        if skip_nonfinite and record is None:
+            raise ValueError("skip_nonfinite needs a clip record")
+        groups: dict = {}
+        host = []
+        for i, (p, h, m) in enumerate(zip(params, compressed, momenta)):
+            if cls._check_sgd_segment(i, p, h, m):
+                groups.setdefault(p.device, []).append((p.reshape(-1), h.reshape(-1),
+                                                        m.reshape(-1)))
+            else:
+                host.append((p, h, m))
+        rec_dev = getattr(getattr(record, "tensor", None), "device", None)
+        if host:
+            mult, skip = None, False
+            if record is not None:
+                if rec_dev is not None and rec_dev.type == "cuda" and not groups:
+                    raise ValueError(f"record is on {rec_dev}, the tensors on the host")
+                val = (lambda x: x.item() if _is_torch(x) else x)
+                mult = np.float32(val(record.mult))
+                skip = bool(skip_nonfinite) and float(val(record.nonfinite)) != 0.0
+            for p, h, m in ([] if skip else host):
+                pa = (p.detach().numpy() if _is_torch(p) else p).reshape(-1)
+                ma = (m.detach().numpy() if _is_torch(m) else m).reshape(-1)
+                if _is_torch(h):
+                    import torch
+                    ha = h.detach().reshape(-1).view(torch.int16).numpy().view(np.uint16)
+                else:
+                    ha = h.reshape(-1).view(np.uint16)
+                pn, mn = sgd_step(pa, ma, ha, cls.NAME, divisor, lr=lr, momentum=momentum,
+                                  weight_decay=weight_decay, nesterov=nesterov, mult=mult)
+                pa[:], ma[:] = pn, mn
+        if not groups:
+            return params
+        import torch
+        from .dtypes import from_torch
+        from .reducer import ClipRecord
+        if record is not None and not isinstance(record, ClipRecord):
+            raise ValueError("apply_sgd_many: device tensors take a reducer.ClipRecord")
+        wire = from_torch(cls.wire_torch_dtype())
+        for device, segs in groups.items():
+            if record is not None and record.tensor.device != device:
+                raise ValueError(f"record is on {record.tensor.device}, tensors on {device}")
+            with torch.cuda.device(device):
+                plan = plans.get_sgd(segs, wire) if plans is not None \
+                    else _new_sgd_plan(segs, wire)
+                try:
+                    plan.apply(int(divisor), lr=lr, momentum=momentum,
+                               weight_decay=weight_decay, nesterov=nesterov, record=record,
+                               skip_nonfinite=skip_nonfinite,
+                               stream=torch.cuda.current_stream(device))
+                finally:
+                    if plans is None:
+                        plan.close()      # waits for the launch
+        return params
+
+    @classmethod
+    def apply_sgd_into(cls, param, compressed, momentum_buf, divisor: int = 1, *, lr,
+                       momentum: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                       record=None, skip_nonfinite: bool = False,
+                       plans: CastPlanCache | None = None):
+        """``apply_sgd_many`` of one tensor: a device tensor goes through a
+        one-segment SGD plan (from ``plans`` if given, else built and destroyed
+        here, which waits for the launch), as ``decompress_into(stats=)``
+        does.  Returns ``param``."""
+        cls.apply_sgd_many([param], [compressed], [momentum_buf], divisor, lr=lr,
+                           momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
+                           record=record, skip_nonfinite=skip_nonfinite, plans=plans)
+        return param
 
 
 class FP16Compressor(_CastCompressor):

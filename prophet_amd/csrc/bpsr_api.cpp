@@ -469,15 +469,17 @@ struct CastWire {
   decltype(launch_cast_plan_stats)* plan_stats;
   decltype(launch_cast_plan_measure)* plan_measure;
   decltype(launch_cast_plan_scaled)* plan_scaled;
+  decltype(launch_cast_plan_sgd)* plan_sgd;
 };
 static const CastWire kCastWires[] = {
     {kFloat16, launch_compress_fp16, launch_decompress_fp16, launch_compress_ef,
      launch_compress_sr, launch_cast_plan, launch_cast_plan_ef, launch_cast_plan_sr,
-     launch_cast_plan_stats, launch_cast_plan_measure, launch_cast_plan_scaled},
+     launch_cast_plan_stats, launch_cast_plan_measure, launch_cast_plan_scaled,
+     launch_cast_plan_sgd},
     {kBFloat16, launch_compress_bf16, launch_decompress_bf16, launch_compress_ef_bf16,
      launch_compress_sr_bf16, launch_cast_plan_bf16, launch_cast_plan_ef_bf16,
      launch_cast_plan_sr_bf16, launch_cast_plan_stats_bf16, launch_cast_plan_measure_bf16,
-     launch_cast_plan_scaled_bf16},
+     launch_cast_plan_scaled_bf16, launch_cast_plan_sgd_bf16},
 };
 
 // The row of a wire format; null, with the dtype error set, for any other.
@@ -511,8 +513,9 @@ struct byteps_reduce_cast_plan {
   // (_decompress_stats) the segments' record lists, seg_begin[nsegs + 1] then
   // seg_recs[records], uploaded with the table, and the (record, wave)
   // partials, made by the first statistics call; and the scheme's array of one
-  // entry per record — a residual pointer (error feedback) or a CastSrRec
-  // (stochastic rounding).
+  // entry per record — a residual pointer (error feedback), a CastSrRec
+  // (stochastic rounding) or a momentum pointer (an SGD plan, whose wide side
+  // is the parameter).
   enum { kTable, kSeg, kPart, kSide, kDevArrays };
   void* dev[kDevArrays] = {};
   // the segments' byte ranges, which the statistics' output must stay clear of
@@ -555,6 +558,20 @@ static int cast_plan_table(const byteps_cast_sr_desc* segs, int nsegs, int dtype
                            std::vector<char>& out, std::vector<CastSrRec>& side, CastTableInfo* ti,
                            CastSegList* lists) {
   return build_cast_table_sr(segs, nsegs, dtype, copy_vpt, out, side, ti, lists);
+}
+
+// An SGD plan's table is an error-feedback plan's, unchanged: wide = the
+// parameter, resid = the momentum buffer (cast_cut_ef's co-alignment rule, the
+// 3 * nsegs disjoint ranges and the parallel pointer array are what it needs).
+static int cast_plan_table(const byteps_cast_sgd_desc* segs, int nsegs, int dtype, int copy_vpt,
+                           std::vector<char>& out, std::vector<unsigned char*>& side,
+                           CastTableInfo* ti, CastSegList* lists) {
+  if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
+  std::vector<byteps_cast_ef_desc> ef((size_t)nsegs);
+  for (int i = 0; i < nsegs; ++i)
+    ef[(size_t)i] = byteps_cast_ef_desc{segs[i].param, segs[i].half, segs[i].momentum,
+                                        segs[i].nelem};
+  return build_cast_table_ef(ef.data(), nsegs, dtype, copy_vpt, out, side, ti, lists);
 }
 
 // A new plan of `scheme`: build the table (and the scheme's array, of `Side`
@@ -600,6 +617,15 @@ static int cast_plan_create(CastScheme scheme, const D* segs, int nsegs, int wid
   }
   *out = p;
   return BYTEPS_REDUCE_OK;
+}
+
+// Every plan call but _apply_sgd and _destroy refuses an SGD plan: its wide
+// side is the parameter, which a decompress would overwrite with gradients.
+static int refuse_sgd(const byteps_reduce_cast_plan* p, const char* what) {
+  if (p->scheme != kCastSgd) return BYTEPS_REDUCE_OK;
+  return fail(BYTEPS_REDUCE_EARGS,
+              "%s on an SGD plan: its wide side is the parameter "
+              "(byteps_reduce_cast_plan_apply_sgd)", what);
 }
 
 // The plan's one launch, by direction and scheme (validated by the callers;
@@ -708,6 +734,7 @@ int byteps_reduce_cast_plan_create_sr(const byteps_cast_sr_desc* segs, int nsegs
 
 int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* p, void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (const int rc = refuse_sgd(p, "compress")) return rc;
   if (p->scheme == kCastSr)
     return fail(BYTEPS_REDUCE_EARGS,
                 "a stochastic-rounding plan is compressed with a step "
@@ -718,6 +745,7 @@ int byteps_reduce_cast_plan_compress(byteps_reduce_cast_plan* p, void* stream) {
 
 int byteps_reduce_cast_plan_compress_sr(byteps_reduce_cast_plan* p, uint32_t step, void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (const int rc = refuse_sgd(p, "compress_sr")) return rc;
   if (p->scheme != kCastSr)
     return fail(BYTEPS_REDUCE_EARGS, "the plan carries no keys (byteps_reduce_cast_plan_create_sr)");
   if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
@@ -726,6 +754,7 @@ int byteps_reduce_cast_plan_compress_sr(byteps_reduce_cast_plan* p, uint32_t ste
 
 int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* p, int divisor, void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (const int rc = refuse_sgd(p, "decompress")) return rc;
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
   if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
   return cast_plan_launch(p, false, divisor, 0, nullptr, stream);
@@ -736,6 +765,7 @@ int byteps_reduce_cast_plan_decompress(byteps_reduce_cast_plan* p, int divisor, 
 static int cast_plan_stats(byteps_reduce_cast_plan* p, int divisor, double* stats, void* stream,
                            bool measure) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (const int rc = refuse_sgd(p, measure ? "measure" : "decompress_stats")) return rc;
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
   if (p->nsegs <= 0) return BYTEPS_REDUCE_OK;  // no segment: no row, nothing to write
   if (!stats) return fail(BYTEPS_REDUCE_EARGS, "null stats pointer");
@@ -789,6 +819,7 @@ int byteps_reduce_clip_record(const double* rows, int nrows, double max_norm, do
 int byteps_reduce_cast_plan_decompress_scaled(byteps_reduce_cast_plan* p, int divisor,
                                               const float* mult, void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (const int rc = refuse_sgd(p, "decompress_scaled")) return rc;
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
   if (!mult) return fail(BYTEPS_REDUCE_EARGS, "null mult pointer");
   const uintptr_t mb = (uintptr_t)mult;
@@ -798,6 +829,45 @@ int byteps_reduce_cast_plan_decompress_scaled(byteps_reduce_cast_plan* p, int di
       return fail(BYTEPS_REDUCE_EARGS, "mult lies inside a segment of the plan");
   if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
   return cast_plan_launch(p, false, divisor, 0, nullptr, stream, false, mult);
+}
+
+int byteps_reduce_cast_plan_create_sgd(const byteps_cast_sgd_desc* segs, int nsegs, int wire_dtype,
+                                       byteps_reduce_cast_plan** out) {
+  return cast_plan_create<unsigned char*>(kCastSgd, segs, nsegs, kFloat32, wire_dtype, out);
+}
+
+int byteps_reduce_cast_plan_apply_sgd(byteps_reduce_cast_plan* p, int divisor,
+                                      const byteps_sgd_hyper* h, const byteps_clip_record* rec,
+                                      int skip_nonfinite, void* stream) {
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (p->scheme != kCastSgd)
+    return fail(BYTEPS_REDUCE_EARGS,
+                "the plan is not an SGD plan (byteps_reduce_cast_plan_create_sgd)");
+  if (!h) return fail(BYTEPS_REDUCE_EARGS, "null hyper-parameters");
+  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  if (!std::isfinite(h->lr)) return fail(BYTEPS_REDUCE_EARGS, "lr %g is not finite", h->lr);
+  if (!(h->momentum >= 0.0f && h->momentum < 1.0f))
+    return fail(BYTEPS_REDUCE_EARGS, "momentum %g is not in [0, 1)", h->momentum);
+  if (!(h->weight_decay >= 0.0f) || !std::isfinite(h->weight_decay))
+    return fail(BYTEPS_REDUCE_EARGS, "weight_decay %g is not a finite number >= 0",
+                h->weight_decay);
+  if (h->nesterov && h->momentum == 0.0f)
+    return fail(BYTEPS_REDUCE_EARGS, "nesterov needs a momentum above 0");
+  if (skip_nonfinite && !rec)
+    return fail(BYTEPS_REDUCE_EARGS, "skip_nonfinite needs a clip record");
+  if (rec) {
+    const uintptr_t rb = (uintptr_t)rec;
+    if (rb % 8) return fail(BYTEPS_REDUCE_EARGS, "clip record is not 8-byte aligned");
+    for (const auto& r : p->ranges)
+      if (rb < r.second && r.first < rb + sizeof(byteps_clip_record))
+        return fail(BYTEPS_REDUCE_EARGS, "clip record lies inside a segment of the plan");
+  }
+  if (p->ti.records == 0) return BYTEPS_REDUCE_OK;
+  const hipError_t e = p->wire->plan_sgd(
+      static_cast<const CastRec*>(p->dev[p->kTable]),
+      static_cast<unsigned char* const*>(p->dev[p->kSide]), p->ti.records, divisor, *h, rec,
+      skip_nonfinite ? 1 : 0, p->ti.u, p->ti.nelem * 8, tuning(), to_stream(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "SGD plan kernel launch");
 }
 
 int byteps_reduce_cast_plan_destroy(byteps_reduce_cast_plan* p) {

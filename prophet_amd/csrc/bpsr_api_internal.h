@@ -92,8 +92,9 @@ struct CastTableInfo {
 };
 
 // The rounding scheme of a cast: what a single compress, a plan and its table
-// are made for.
-enum CastScheme { kCastPlain = 0, kCastEf = 1, kCastSr = 2 };
+// are made for.  kCastSgd: a plan alone (byteps_reduce_cast_plan_create_sgd),
+// whose table is an error-feedback plan's over (parameter, wire, momentum).
+enum CastScheme { kCastPlain = 0, kCastEf = 1, kCastSr = 2, kCastSgd = 3 };
 
 // Which wide dtypes travel in which 2-byte wire format, per scheme: fp16
 // carries f32, f64 and bf16, bf16 carries f32, f64 and fp16; error feedback

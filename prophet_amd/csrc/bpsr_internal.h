@@ -493,6 +493,20 @@ hipError_t launch_cast_plan_ef(const CastRec* table, unsigned char* const* rtab,
 hipError_t launch_cast_plan_ef_bf16(const CastRec* table, unsigned char* const* rtab,
                                     uint32_t nrecords, int u, uint64_t out_bytes,
                                     const Tuning& tu, hipStream_t s);
+// The SGD step inside the decompress (bpsr_cast_sgd.h; bpsr_k_cast_sgd.hip:
+// fp16 wire, bpsr_k_cast_sgd_bf16.hip: bf16 wire) over an EF-shaped table whose
+// wide operand is the f32 parameter: `mtab[b]` is the momentum pointer of
+// record b; `rec` is null or the device-resident clip record, whose mult
+// scales the gradient and whose nonfinite != 0 skips the launch under `skip`;
+// `out_bytes` is what the launch writes, 8 an element.
+hipError_t launch_cast_plan_sgd(const CastRec* table, unsigned char* const* mtab,
+                                uint32_t nrecords, int divisor, const byteps_sgd_hyper& h,
+                                const byteps_clip_record* rec, int skip, int u,
+                                uint64_t out_bytes, const Tuning& tu, hipStream_t s);
+hipError_t launch_cast_plan_sgd_bf16(const CastRec* table, unsigned char* const* mtab,
+                                     uint32_t nrecords, int divisor, const byteps_sgd_hyper& h,
+                                     const byteps_clip_record* rec, int skip, int u,
+                                     uint64_t out_bytes, const Tuning& tu, hipStream_t s);
 // Stochastic-rounding compress (bpsr_cast_sr.h; bpsr_k_cast_sr.hip: fp16 wire,
 // bpsr_k_cast_sr_bf16.hip: bf16 wire): nelem f32 ELEMENTS of src to the wire
 // format at dst, element i rounded under 16 bits of Philox2x32-10(i >> 2,

@@ -70,6 +70,17 @@ decompress: after the last pull every compressor group is
 measured into one rows tensor, one clip record is made over all rows, and
 every group is decompressed times the record's ``mult``.  It leaves
 ``Worker.grad_clip`` (:class:`GradClip`) and ``Worker.grad_stats``.
+
+``push_pull_iteration(..., apply=SgdStep(params, lr, ...))`` ends the
+iteration in the parameters instead: after the last pull
+every compressor group runs ``apply_sgd_many`` — one launch per device that
+reads the pulled wire aggregate, the parameter and the context's momentum
+buffer and updates the last two in place — and the gradients in ``tensors``
+are not written at all.  With ``clip_norm`` the groups are measured and the
+one clip record made as above, and the step multiplies by its ``mult``; with
+``SgdStep(skip_nonfinite=True)`` an overflowed iteration leaves parameters
+and momenta untouched, decided on the device.  ``Worker.momentum`` /
+``reset_momentum`` read and zero a context's momentum buffer.
 """
 from __future__ import annotations
 
@@ -126,6 +137,9 @@ class Context:
     # kind, device and element count; stochastic rounding (Compression.*_sr) —
     # the context's Philox key, an SrKey; None otherwise
     extra: object = None
+    # push_pull_iteration(apply=SgdStep): the f32 momentum buffer, zeroed on
+    # first use where the parameter lives; None before
+    momentum: object = None
     init_lock: threading.Lock = field(default_factory=threading.Lock)
 
     @property
@@ -198,6 +212,23 @@ class GradClip:
         self.names = list(names)
         self.rows = rows
         self.skipped = list(skipped)
+
+
+@dataclass
+class SgdStep:
+    """``push_pull_iteration(apply=...)``: SGD with momentum and weight decay
+    as the end of the iteration (``prophet_amd.sgd`` is the arithmetic).
+    ``params`` maps every floating context's name to its float32 parameter,
+    of the gradient's size and in the gradient's place; it is updated in
+    place.  ``skip_nonfinite`` (with ``clip_norm``): an iteration whose
+    aggregate holds a non-finite value leaves parameters and momenta as they
+    were."""
+    params: dict
+    lr: float
+    momentum: float = 0.0
+    weight_decay: float = 0.0
+    nesterov: bool = False
+    skip_nonfinite: bool = False
 
 
 def _finite_row(row, x) -> None:
@@ -510,7 +541,7 @@ class Worker:
 
     def push_pull_iteration(self, tensors: dict, scheduler=None, average: bool = False,
                             stats: bool = False, clip_norm=None, clip_eps: float = 1e-6,
-                            unscale=None) -> list:
+                            unscale=None, apply: "SgdStep | None" = None) -> list:
         """One training iteration: every declared tensor, gradients arriving in
         backward order (highest declared index first).  With a Prophet
         ``scheduler`` (``ProphetPushQueue``) the partitions are pushed in the
@@ -537,6 +568,18 @@ class Worker:
         nor multiplied, and are named in ``grad_clip.skipped``.  Leaves ``grad_clip``
         (:class:`GradClip`) and ``grad_stats`` (the rows before the clip).
         All floating tensors live in one place, a device or the host.
+        ``apply`` (:class:`SgdStep`): after the last pull the SGD step runs
+        inside the decompress — ``apply_sgd_many`` per compressor group in
+        place of the decompress — on ``apply.params`` and the contexts'
+        momentum buffers; ``tensors``' floating entries, the gradients, are
+        not written.  ``clip_norm`` measures and makes the one record as
+        above and the step takes its ``mult`` (and, with
+        ``apply.skip_nonfinite``, its skip); ``stats`` without ``clip_norm``
+        measures into ``grad_stats``.  Every floating context must be
+        compressed, float32 and named in ``apply.params`` by a float32
+        parameter of its size and place (``ValueError`` before anything is
+        pushed); integer tensors keep the sum they pulled and are named in
+        ``grad_stats.skipped`` / ``grad_clip.skipped``.
         Returns the release groups as lists of (declared key, partition)."""
         from .prophet import PushTask, release_groups
         ctxs = [self.contexts[n] for n in self._declared if n in tensors]
@@ -551,6 +594,8 @@ class Worker:
             if len(places) > 1:
                 raise ValueError("clip_norm: the floating tensors live in one place, "
                                  "a device or the host")
+        if apply is not None:             # before anything is pushed
+            self._check_apply(ctxs, tensors, apply, clip_norm)
         divisor = 1
         if average:
             divisor = getattr(self.frontend, "size", None)
@@ -587,6 +632,10 @@ class Worker:
         for c in ctxs:
             for key, off, ln in c.parts:
                 self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
+        if apply is not None:
+            self._apply_iteration(ctxs, casts, tensors, divisor, stats, clip_norm, clip_eps,
+                                  unscale, apply)
+            return [[(t.grad, t.part) for t in g] for g in groups]
         if clip_norm is not None:
             self._clip_iteration(ctxs, casts, tensors, divisor, average, clip_norm, clip_eps,
                                  unscale)
@@ -610,6 +659,105 @@ class Worker:
                 if c.compressor is None:
                     _divide_(tensors[c.name], divisor)
         return [[(t.grad, t.part) for t in g] for g in groups]
+
+    def _check_apply(self, ctxs, tensors, apply, clip_norm) -> None:
+        """What ``push_pull_iteration(apply=)`` asks of its contexts."""
+        from .compression import _is_f32
+        from .sgd import check_hyper
+        check_hyper(apply.lr, apply.momentum, apply.weight_decay, apply.nesterov)
+        if apply.skip_nonfinite and clip_norm is None:
+            raise ValueError("apply: skip_nonfinite goes with clip_norm (the clip record "
+                             "counts the non-finite values)")
+        for c in ctxs:
+            g = tensors[c.name]
+            if not _is_float(g):
+                continue
+            if c.compressor is None:
+                raise ValueError(f"apply: {c.name} is a floating context that is not compressed")
+            if not _is_f32(g):
+                raise ValueError(f"apply: {c.name} is {g.dtype}, the step needs float32")
+            p = apply.params.get(c.name)
+            if p is None:
+                raise ValueError(f"apply: no parameter for {c.name}")
+            if not _is_f32(p) or _nbytes(p) != _nbytes(g) or _place(p) != _place(g) or \
+                    hasattr(p, "data_ptr") != hasattr(g, "data_ptr"):
+                raise ValueError(f"apply: the parameter of {c.name} differs from its gradient "
+                                 f"in dtype, size or place")
+            _contiguous(p)
+
+    def _momentum_of(self, ctx: Context, param):
+        """The context's momentum buffer: flat f32 zeros where ``param`` lives,
+        made on first use."""
+        m = ctx.momentum
+        if m is None or _place(m) != _place(param) or \
+                hasattr(m, "data_ptr") != hasattr(param, "data_ptr"):
+            if hasattr(param, "data_ptr"):
+                import torch
+                m = torch.zeros(param.numel(), dtype=torch.float32, device=param.device)
+            else:
+                import numpy as np
+                m = np.zeros(param.size, dtype=np.float32)
+            ctx.momentum = m
+        return m
+
+    def momentum(self, name: str):
+        """The momentum buffer of a context that went through
+        ``push_pull_iteration(apply=)`` (flat f32, the live buffer), or
+        ``None`` before the first."""
+        return self.contexts[name].momentum
+
+    def reset_momentum(self, name: str) -> None:
+        """Zero the momentum buffer; nothing to do for a context without one."""
+        m = self.contexts[name].momentum
+        if m is None:
+            return
+        if hasattr(m, "data_ptr"):
+            m.zero_()
+        else:
+            m.fill(0)
+
+    def _apply_iteration(self, ctxs, casts, tensors, divisor, stats, clip_norm, clip_eps, unscale,
+                         apply) -> None:
+        """The end of ``push_pull_iteration(apply=...)``, after the last pull:
+        the compressor groups measured where ``clip_norm`` or ``stats`` asks,
+        the one clip record, then the SGD step per group from the staging
+        buffers.  No gradient is written."""
+        names = [c.name for cs in casts.values() for c in cs]
+        skipped = [c.name for c in ctxs if c.compressor is None]
+        first = tensors[names[0]] if names else None
+        on_dev = _place(first) is not None
+        rec = None
+        if clip_norm is not None or stats:
+            rows = _stat_rows(len(names), first if on_dev else None)
+            at = 0
+            for comp, cs in casts.items():
+                comp.measure_many_with([_contiguous(tensors[c.name]) for c in cs],
+                                       [c.staging for c in cs], [c.extra for c in cs], divisor,
+                                       plans=self._cast_plans, stats=rows[at:at + len(cs)])
+                at += len(cs)
+            self.grad_stats = GradStats(names, rows, skipped)
+        if clip_norm is not None:
+            if on_dev:
+                import torch
+                from .torch_ops import _red
+                inv = unscale
+                if inv is not None and not hasattr(inv, "data_ptr"):
+                    inv = torch.tensor([float(inv)], dtype=torch.float32, device=first.device)
+                with torch.cuda.device(first.device):
+                    rec = _red().clip_record(rows, clip_norm, clip_eps, inv)
+            else:
+                from .compression import clip_record
+                rec = clip_record(rows, clip_norm, clip_eps,
+                                  unscale.item() if hasattr(unscale, "data_ptr") else unscale)
+            self.grad_clip = GradClip(rec, names, rows, skipped)
+        for comp, cs in casts.items():
+            params = [apply.params[c.name] for c in cs]
+            comp.apply_sgd_many(params, [c.staging for c in cs],
+                                [self._momentum_of(c, p) for c, p in zip(cs, params)], divisor,
+                                lr=apply.lr, momentum=apply.momentum,
+                                weight_decay=apply.weight_decay, nesterov=apply.nesterov,
+                                record=rec, skip_nonfinite=apply.skip_nonfinite,
+                                plans=self._cast_plans)
 
     def _clip_iteration(self, ctxs, casts, tensors, divisor, average, clip_norm, clip_eps,
                         unscale) -> None:
@@ -708,4 +856,4 @@ def _slice(x, off: int, ln: int):
     return x.reshape(-1).view(np.uint8)[off:off + ln]
 
 
-__all__ = ["ServerFrontend", "Worker", "Context", "GradStats", "GradClip", "K_DEFAULT_PUSH_PULL", "DType", "elem_size"]
+__all__ = ["ServerFrontend", "Worker", "Context", "GradStats", "GradClip", "SgdStep", "K_DEFAULT_PUSH_PULL", "DType", "elem_size"]

@@ -68,6 +68,7 @@ EXPORTS = (
     "byteps_reduce_cast_plan_decompress_stats",
     "byteps_reduce_cast_plan_measure", "byteps_reduce_clip_record",
     "byteps_reduce_cast_plan_decompress_scaled",
+    "byteps_reduce_cast_plan_create_sgd", "byteps_reduce_cast_plan_apply_sgd",
 )
 
 
@@ -90,6 +91,17 @@ class CastEfDesc(ctypes.Structure):
 class CastSrDesc(ctypes.Structure):
     """``byteps_cast_sr_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("wide", _vp), ("half", _vp), ("nelem", _sz), ("key", ctypes.c_uint32)]
+
+
+class CastSgdDesc(ctypes.Structure):
+    """``byteps_cast_sgd_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("param", _vp), ("half", _vp), ("momentum", _vp), ("nelem", _sz)]
+
+
+class SgdHyper(ctypes.Structure):
+    """``byteps_sgd_hyper`` (include/bpsr/reduce.h)."""
+    _fields_ = [("lr", ctypes.c_float), ("momentum", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("nesterov", _int)]
 
 
 class SrKey(int):
@@ -174,6 +186,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_clip_record.argtypes = [_vp, _int, ctypes.c_double, ctypes.c_double, _vp,
                                             _vp, _vp]
     L.byteps_reduce_cast_plan_decompress_scaled.argtypes = [_vp, _int, _vp, _vp]
+    L.byteps_reduce_cast_plan_create_sgd.argtypes = [ctypes.POINTER(CastSgdDesc), _int, _int,
+                                                     ctypes.POINTER(_vp)]
+    L.byteps_reduce_cast_plan_apply_sgd.argtypes = [_vp, _int, ctypes.POINTER(SgdHyper), _vp,
+                                                    _int, _vp]
     _LIB = L
     return L
 
@@ -344,6 +360,16 @@ class GpuReducer:
         segment the bytes of ``compress_sr`` under the segment's key,
         ``decompress`` is the plain one."""
         return CastPlan(self.lib, segments, wide_dtype, wire_dtype)
+
+    def sgd_plan(self, segments: Sequence[tuple],
+                 wire_dtype: int = DType.FLOAT16) -> "SgdPlan":
+        """The SGD step inside the decompress
+        (byteps_reduce_cast_plan_create_sgd): ``segments`` are ``(param, half,
+        nelem, momentum)`` of tensors or raw pointers — float32 parameters
+        and momentum buffers, 2-byte sides of ``wire_dtype``.
+        :meth:`SgdPlan.apply` is ONE launch that updates every parameter and
+        momentum buffer in place from the wire; no gradient is written."""
+        return SgdPlan(self.lib, segments, wire_dtype)
 
     def clip_record(self, rows, max_norm: float, eps: float = 1e-6, inv_scale=None, out=None,
                     stream=None) -> "ClipRecord":
@@ -650,6 +676,74 @@ class CastPlan:
         self._keep = []
         self._stats = None
         self._scale = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SgdPlan:
+    """An SGD plan (``byteps_reduce_cast_plan_create_sgd``): per segment the
+    float32 parameter, the 2-byte wire buffer and the float32 momentum buffer.
+    ``apply`` is one launch; per element the arithmetic is
+    ``prophet_amd.sgd.sgd_step``'s, bit for bit.  Tensor operands are
+    bounds-checked before the library sees them and held until ``close``, as
+    a :class:`CastPlan` holds its own.  The library refuses every other cast
+    plan call on this plan: a decompress would write gradients over the
+    parameters."""
+
+    def __init__(self, lib, segments, wire_dtype=DType.FLOAT16):
+        self.lib = lib
+        self.wire_dtype = int(wire_dtype)
+        self.handle = _vp()
+        segments = [tuple(s) for s in segments]
+        for s in segments:
+            if len(s) != 4:
+                raise ValueError(f"sgd plan: a segment of {len(s)} items")
+            _fits_cast(s[2], s[1], s[0], DType.FLOAT32)
+            _fits(int(s[2]) * 4, s[3])
+        self._keep = segments         # keep the tensors alive, the momenta too
+        self._rec = None
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (CastSgdDesc * max(1, len(segments)))()
+        for d, s in zip(descs, segments):
+            d.param, d.half, d.nelem, d.momentum = _ptr(s[0]), _ptr(s[1]), int(s[2]), _ptr(s[3])
+        _check(lib.byteps_reduce_cast_plan_create_sgd(descs, len(segments), self.wire_dtype,
+                                                      ctypes.byref(self.handle)))
+
+    def apply(self, divisor: int = 1, *, lr: float, momentum: float = 0.0,
+              weight_decay: float = 0.0, nesterov: bool = False, record=None,
+              skip_nonfinite: bool = False, stream=None) -> None:
+        """One launch (byteps_reduce_cast_plan_apply_sgd).  ``record``: a
+        :class:`ClipRecord` on the plan's device (or a raw pointer to one),
+        whose ``mult`` scales the gradient; with ``skip_nonfinite`` a record
+        whose ``nonfinite`` is not 0 leaves every parameter and momentum byte
+        as it was, decided on the device.  The plan holds the record until its
+        next launch or ``close``."""
+        rec = record
+        if isinstance(record, ClipRecord):
+            dev = getattr(self.first, "device", None)
+            if dev is not None and record.tensor.device != dev:
+                raise ValueError(f"record is on {record.tensor.device}, the plan on {dev}")
+            _fits(32, record.tensor)
+            rec = record.tensor
+        elif record is not None and not isinstance(record, int):
+            raise ValueError(f"record must be a ClipRecord, got {type(record)!r}")
+        self._rec = record            # held: the launch is asynchronous
+        h = SgdHyper(float(lr), float(momentum), float(weight_decay), 1 if nesterov else 0)
+        _check(self.lib.byteps_reduce_cast_plan_apply_sgd(
+            self.handle, int(divisor), ctypes.byref(h), _ptr(rec), 1 if skip_nonfinite else 0,
+            _stream_of(self.first, stream)))
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.byteps_reduce_cast_plan_destroy(self.handle)
+            self.handle = _vp()
+        self._keep = []
+        self._rec = None
 
     def __del__(self):
         try:

@@ -142,6 +142,26 @@ shapes:
 
   clip_fused faster than the faster of the other two by more than the larger
   of the two spreads.
+
+``--sgd`` measures the SGD step inside the decompress by the
+same method over the same two shapes (f32, divisor 8, unscale 2^-7, a max_norm
+that clips, lr 1e-3, momentum 0.9, weight decay 1e-4, nesterov).  Every
+candidate ends with updated parameters and momenta, each on its own:
+
+  apply           measure, clip record, byteps_reduce_cast_plan_apply_sgd with
+                  the record and skip_nonfinite: 2 + 18 B an element;
+  scaled_fused    measure, clip record, the scaled decompress into the
+                  gradients, torch.optim.SGD(fused=True).step(): 2 + 6 + 20 B;
+  scaled_foreach  the same with foreach=True;
+  apply_only, scaled_fused_only   the last launch of ``apply`` (18 B) and the
+                  last two of ``scaled_fused`` (26 B) alone, the record given.
+
+The parameters and momenta after ``apply`` are first compared bit for bit with
+the definition evaluated by torch one op at a time on the scaled decompress's
+output.  Gate, at both shapes:
+
+  apply faster than the faster of scaled_fused and scaled_foreach by more than
+  the larger of the two spreads.
 """
 import argparse
 import json
@@ -207,7 +227,13 @@ def main() -> int:
                    help="clip by global norm and unscale inside the decompress against the "
                         "statistics decompress + torch's multiply and against "
                         "clip_grad_norm_; the ResNet-50 table and one segment")
+    p.add_argument("--sgd", action="store_true",
+                   help="the SGD step inside the decompress against the scaled decompress "
+                        "followed by torch's fused and foreach SGD; the ResNet-50 table and "
+                        "one segment")
     args = p.parse_args()
+    if args.sgd:
+        return sgd_mode(args)
     if args.clip:
         return clip_mode(args)
     if args.stats:
@@ -1090,6 +1116,166 @@ def clip_mode(args) -> int:
         return {"segments": len(nsegs_rows), "elems": nelem, "results": res,
                 "faster_other": other, "gate_spread_ms": sp,
                 "other_over_clip_fused": round(res[other]["ms"] / res["clip_fused"]["ms"], 3)}
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    total_bytes, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    out["iteration"] = shape("table", [(o // 2, ln // 2) for o, ln in rows], total_bytes // 2)
+    torch.cuda.empty_cache()
+    out["big"] = shape("big", [(0, args.elems)], args.elems)
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    ok = all(gates.values()) and all(v for c in checks.values() for k, v in c.items()
+                                     if isinstance(v, bool))
+    return 0 if ok else 1
+
+
+def sgd_mode(args) -> int:
+    """The SGD step inside the decompress: measure + record + apply_sgd
+    against measure + record + scaled decompress + torch.optim.SGD (fused,
+    foreach); and apply_sgd alone against the scaled decompress + the fused
+    step.  Every candidate ends with updated parameters and momenta and owns
+    its parameters and momenta."""
+    import torch
+
+    from prophet_amd.dtypes import DType
+    from prophet_amd.reducer import ClipRecord, GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    F32 = DType.FLOAT32
+    wd_id, tdt = {"fp16": (DType.FLOAT16, torch.float16),
+                  "bf16": (DType.BFLOAT16, torch.bfloat16)}[args.wire]
+    DIV, EPS, INV = 8, 1e-6, 2.0 ** -7
+    LR, MU, WD = 1e-3, 0.9, 1e-4
+    out = {"tool": "bench_compress", "mode": "sgd step inside the decompress", "wire": args.wire,
+           "divisor": DIV, "unscale": INV, "lr": LR, "momentum": MU, "weight_decay": WD,
+           "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+
+    def shape(label, seg_rows, arena_elems):
+        """One shape: ``seg_rows`` = (first element, elements) per segment."""
+        nelem = sum(n for _, n in seg_rows)
+        with step(f"setup, {label}", 180):
+            g = torch.Generator(device=dev).manual_seed(7)
+            inv = torch.tensor([INV], dtype=torch.float32, device=dev)
+            sets = []
+            for _ in range(args.sets):
+                half = (torch.randn(arena_elems, device=dev, generator=g) * 64).to(tdt)
+                grad = torch.zeros(arena_elems, device=dev)
+                p0 = torch.randn(arena_elems, device=dev, generator=g)
+                s = {"half": half, "grad": grad, "p0": p0, "rec": ClipRecord(dev),
+                     "st": torch.empty(2 * len(seg_rows), dtype=torch.float64, device=dev)}
+                cut = lambda t: [t[o:o + n] for o, n in seg_rows]      # noqa: E731
+                # apply: its own parameters and momenta
+                s["pa"], s["ma"] = p0.clone(), torch.zeros(arena_elems, device=dev)
+                s["plain"] = red.cast_plan([(w, h, n) for w, h, (_, n) in
+                                            zip(cut(grad), cut(half), seg_rows)], F32, wd_id)
+                s["sgd"] = red.sgd_plan([(p, h, n, m) for p, h, m, (_, n) in
+                                         zip(cut(s["pa"]), cut(half), cut(s["ma"]), seg_rows)],
+                                        wd_id)
+                # torch: parameters whose .grad is the decompress's output
+                for kind in ("fused", "foreach"):
+                    arena = p0.clone()
+                    prm = [torch.nn.Parameter(o, requires_grad=True) for o in cut(arena)]
+                    for q, o in zip(prm, cut(grad)):
+                        q.grad = o
+                    s["p_" + kind] = arena
+                    s["opt_" + kind] = torch.optim.SGD(prm, lr=LR, momentum=MU, weight_decay=WD,
+                                                       nesterov=True, **{kind: True})
+                sets.append(s)
+            for s in sets:                       # the first statistics call allocates
+                s["plain"].measure(DIV, stats=s["st"])
+            max_norm = float(sets[0]["st"].view(-1, 2)[:, 0].sum().sqrt()) * INV / 3
+            torch.cuda.synchronize()
+
+        def record(s):
+            s["plain"].measure(DIV, stats=s["st"])
+            red.clip_record(s["st"], max_norm, EPS, inv, out=s["rec"])
+
+        def apply_only(k):
+            s = sets[k]
+            s["sgd"].apply(DIV, lr=LR, momentum=MU, weight_decay=WD, nesterov=True,
+                           record=s["rec"], skip_nonfinite=True)
+
+        def apply(k):
+            record(sets[k])
+            apply_only(k)
+
+        def scaled_only(kind):
+            def run(k):
+                s = sets[k]
+                s["plain"].decompress(DIV, scale=s["rec"].mult)
+                s["opt_" + kind].step()
+            return run
+
+        def scaled(kind):
+            only = scaled_only(kind)
+
+            def run(k):
+                record(sets[k])
+                only(k)
+            return run
+
+        with step(f"check, {label}", 180):
+            s = sets[0]
+            record(s)
+            s["plain"].decompress(DIV, scale=s["rec"].mult)
+            # the definition, one rounding per torch op, from a zero momentum
+            gr, p = s["grad"], s["p0"]
+            gr = gr + WD * p
+            mn = MU * torch.zeros_like(p) + gr
+            want_p = p - LR * (gr + MU * mn)
+            apply_only(0)
+            scaled_only("fused")(0)
+            torch.cuda.synchronize()
+
+            def cover(t):
+                """The segments' elements of an arena (the table has gaps)."""
+                return torch.cat([t[o:o + n] for o, n in seg_rows])
+            close = torch.allclose(cover(s["p_fused"]), cover(want_p), rtol=1e-5, atol=1e-6)
+            checks[label] = {
+                "apply_params_equal_definition": bool(torch.equal(
+                    cover(s["pa"]).view(torch.int32), cover(want_p).view(torch.int32))),
+                "apply_momenta_equal_definition": bool(torch.equal(
+                    cover(s["ma"]).view(torch.int32), cover(mn).view(torch.int32))),
+                "torch_fused_close_to_definition": bool(close),
+                "found_inf": float(s["rec"].nonfinite), "mult": float(s["rec"].mult),
+                "max_norm": max_norm}
+            del gr, mn, want_p
+            torch.cuda.synchronize()
+        res = timed_rounds(torch, {
+            "apply": (apply, args.inner),
+            "scaled_fused": (scaled("fused"), args.inner),
+            "scaled_foreach": (scaled("foreach"), args.inner),
+            "apply_only": (apply_only, args.inner),
+            "scaled_fused_only": (scaled_only("fused"), args.inner)}, len(sets), args)
+        # bytes an element each must move: measure 2, apply 18, scaled decompress 6, step 20
+        for name, per in (("apply", 20), ("scaled_fused", 28), ("scaled_foreach", 28),
+                          ("apply_only", 18), ("scaled_fused_only", 26)):
+            res[name]["bytes_per_elem"] = per
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        other = min(("scaled_fused", "scaled_foreach"), key=lambda k: res[k]["ms"])
+        sp = max(res["apply"]["spread_ms"], res[other]["spread_ms"])
+        gates[f"{label}_apply_beats_the_faster_torch"] = res[other]["ms"] - res["apply"]["ms"] > sp
+        for s in sets:
+            s["plain"].close()
+            s["sgd"].close()
+        return {"segments": len(seg_rows), "elems": nelem, "results": res,
+                "faster_torch": other, "gate_spread_ms": sp,
+                "torch_over_apply": round(res[other]["ms"] / res["apply"]["ms"], 3),
+                "only_torch_over_apply": round(res["scaled_fused_only"]["ms"] /
+                                               res["apply_only"]["ms"], 3)}
 
     with step("init", 60):
         red = GpuReducer(device=0)
