@@ -76,7 +76,10 @@ extern "C" {
  *                       inside the decompress)
  *    additive, still 5: byteps_reduce_cast_plan_create_sgd / _cast_plan_apply_sgd
  *                       (byteps_cast_sgd_desc, byteps_sgd_hyper: the SGD step
- *                       inside the decompress) */
+ *                       inside the decompress)
+ *    additive, still 5: byteps_reduce_onebit_* (byteps_onebit_desc,
+ *                       byteps_onebit_fold_desc: 1-bit sign compression with
+ *                       error feedback) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -650,6 +653,59 @@ typedef struct byteps_sgd_hyper {
 int byteps_reduce_cast_plan_apply_sgd(byteps_reduce_cast_plan* plan, int divisor,
                                       const byteps_sgd_hyper* h, const byteps_clip_record* rec,
                                       int skip_nonfinite, void* stream);
+
+/* 1-bit sign compression with error feedback: one bit an
+ * element and one f32 scale a tensor, 32x smaller than f32.  For one tensor of
+ * n FLOAT32 elements g with its FLOAT32 residual r, pinned to
+ * prophet_amd/onebit.py:
+ *
+ *   c_i   = g_i + r_i                           one IEEE f32 add
+ *   scale = f32((sum_i f64(|c_i|)) / f64(n))    f64 sum, one f64 divide, one
+ *                                               rounding; the order of the sum
+ *                                               is the plan's, deterministic
+ *   b_i   = c_i < 0                             -0.0, +0.0 and NaN give 0
+ *   r'_i  = c_i - (b_i ? -scale : scale)        one IEEE f32 subtract; replaces r_i
+ *
+ * The payload, little endian, 16-byte aligned: the header {f32 scale, u32
+ * n_lo, u32 n_hi, u32 0}, then ceil(n / 64) u64 words, bit k of word w being
+ * b_(64 w + k), the bits past n zero: _payload_bytes(n) = 16 + 8 ceil(n / 64).
+ * n == 0 is a header with scale 0.
+ *
+ * Plans over many tensors are the only form (one tensor: one segment).
+ * _plan_compress is three launches on `stream` with no host synchronisation.
+ *
+ * The fold decodes nsrc payloads of the same n (d_ki = b_ki ? -scale_k :
+ * scale_k) and adds them in argument order, an f32 left fold:
+ *   out_i = ((d_0i + d_1i) + ...) + d_(nsrc-1)i,  then / f32(divisor) when
+ * divisor > 1; nsrc == 1 is the plain decompress.  One launch.  Sizes come
+ * from the plan: a payload's header is read for its scale alone.
+ *
+ * EARGS before any launch, every buffer untouched: a null pointer with nelem >
+ * 0, a payload that is not 16-byte aligned, more than 2^37 elements a segment,
+ * nsrc outside 1..16, divisor < 1, any two byte ranges of a plan's operands
+ * overlapping (sources included), a fold launch on a compress plan or a
+ * compress on a fold plan.  _plan_destroy frees either kind. */
+typedef struct byteps_onebit_desc {
+  const void* grad;
+  void* resid;
+  void* payload;
+  uint64_t nelem;
+} byteps_onebit_desc;
+typedef struct byteps_onebit_fold_desc {
+  void* out;
+  const void* const* payloads; /* nsrc of them; read by _fold_plan_create alone */
+  uint64_t nelem;
+} byteps_onebit_fold_desc;
+typedef struct byteps_reduce_onebit_plan byteps_reduce_onebit_plan;
+uint64_t byteps_reduce_onebit_payload_bytes(uint64_t nelem);
+int byteps_reduce_onebit_plan_create(const byteps_onebit_desc* segs, int nsegs,
+                                     byteps_reduce_onebit_plan** out);
+int byteps_reduce_onebit_plan_compress(byteps_reduce_onebit_plan* plan, void* stream);
+int byteps_reduce_onebit_fold_plan_create(const byteps_onebit_fold_desc* segs, int nsegs, int nsrc,
+                                          byteps_reduce_onebit_plan** out);
+int byteps_reduce_onebit_fold_plan_launch(byteps_reduce_onebit_plan* plan, int divisor,
+                                          void* stream);
+int byteps_reduce_onebit_plan_destroy(byteps_reduce_onebit_plan* plan);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

@@ -121,6 +121,15 @@ bit.  With ``record=`` the gradient is multiplied by the clip record's
 non-finite value leaves parameters and momenta untouched, decided on the
 device (GradScaler's skipped step with no host synchronisation).  There is no
 ``torch.library`` op for it either: an SGD plan owns raw device pointers.
+
+``Compression.onebit_ef`` leaves the 2-byte wires behind:
+a float32 tensor travels as one bit an element plus one float32 scale, the
+mean of ``|tensor + residual|``, 32x smaller than float32, with error
+feedback.  ``prophet_amd/onebit.py`` is the definition.  A payload is a flat
+uint8 buffer (``payload_like``); ``compress_many_ef_into`` is three launches
+per device, ``fold_many_into`` decodes up to 16 payloads per output and adds
+them in order in one.  The PS server cannot fold a packed payload, so
+``Worker.init_tensor`` refuses this compressor.
 """
 from __future__ import annotations
 
@@ -285,11 +294,15 @@ class CastPlanCache:
             (int(p[0].data_ptr()), int(p[1].data_ptr()), int(p[0].numel()))
             + tuple(("sr", int(r)) if isinstance(r, SrKey) else int(r.data_ptr()) for r in p[2:])
             for p in pairs)
+        return self._get(key, lambda: _new_plan(wide_dtype, pairs, wire_dtype))
+
+    def _get(self, key, build):
+        """The plan under ``key``, made by ``build()`` on a miss."""
         plan = self._plans.get(key)
         if plan is not None:
             self._plans.move_to_end(key)
             return plan
-        plan = _new_plan(wide_dtype, pairs, wire_dtype)
+        plan = build()
         self.built += 1
         self._plans[key] = plan
         while len(self._plans) > self.capacity:
@@ -305,22 +318,38 @@ class CastPlanCache:
         key = ("sgd", int(wire_dtype)) + tuple(
             (int(p.data_ptr()), int(h.data_ptr()), int(p.numel()), int(m.data_ptr()))
             for p, h, m in triples)
-        plan = self._plans.get(key)
-        if plan is not None:
-            self._plans.move_to_end(key)
-            return plan
-        plan = _new_sgd_plan(triples, wire_dtype)
-        self.built += 1
-        self._plans[key] = plan
-        while len(self._plans) > self.capacity:
-            _, old = self._plans.popitem(last=False)
-            old.close()
-        return plan
+        return self._get(key, lambda: _new_sgd_plan(triples, wire_dtype))
+
+    def get_onebit(self, segs):
+        """The 1-bit compress plan (``GpuReducer.onebit_plan``) over ``segs`` of
+        flat ``(grad, resid, payload)`` device tensors on the current device."""
+        key = ("onebit",) + tuple(
+            (int(g.data_ptr()), int(r.data_ptr()), int(p.data_ptr()), int(g.numel()))
+            for g, r, p in segs)
+        return self._get(key, lambda: _new_onebit_plan(segs))
+
+    def get_onebit_fold(self, segs, nsrc: int):
+        """The 1-bit fold plan (``GpuReducer.onebit_fold_plan``) over ``segs`` of
+        ``(out, payloads)`` device tensors on the current device."""
+        key = ("onebit_fold", int(nsrc)) + tuple(
+            (int(o.data_ptr()), int(o.numel())) + tuple(int(p.data_ptr()) for p in ps)
+            for o, ps in segs)
+        return self._get(key, lambda: _new_onebit_fold_plan(segs, nsrc))
 
     def close(self) -> None:
         while self._plans:
             _, plan = self._plans.popitem(last=False)
             plan.close()
+
+
+def _new_onebit_plan(segs):
+    from .torch_ops import _red
+    return _red().onebit_plan([(g, r, p, int(g.numel())) for g, r, p in segs])
+
+
+def _new_onebit_fold_plan(segs, nsrc: int):
+    from .torch_ops import _red
+    return _red().onebit_fold_plan([(o, ps, int(o.numel())) for o, ps in segs], nsrc)
 
 
 def _new_sgd_plan(triples, wire_dtype: int = 2):
@@ -437,6 +466,7 @@ class Compressor:
 
     ERROR_FEEDBACK = False                # compress_ef_into and a residual per tensor
     STOCHASTIC = False                    # compress_sr_into under a key and a step
+    PACKED = False                        # the wire is no element-wise dtype (onebit_ef)
 
     @staticmethod
     def compresses(tensor) -> bool:
@@ -1095,6 +1125,182 @@ class BF16SRCompressor(_StochasticRounding, BF16Compressor):
     """float32 tensors travel as bf16, stochastically rounded."""
 
 
+def _payload_array(x):
+    """A host payload (uint8 CPU tensor or numpy array) as a flat numpy view."""
+    a = x.detach().numpy() if _is_torch(x) else x
+    if a.dtype != np.uint8:
+        raise ValueError(f"a payload is uint8, got {a.dtype}")
+    return a.reshape(-1)
+
+
+class OneBitEFCompressor(Compressor):
+    """float32 tensors travel as one bit an element plus one float32 scale,
+    with error feedback (``prophet_amd/onebit.py`` is the definition): 32x
+    smaller than float32.  A payload is a flat uint8 buffer of
+    ``onebit.payload_bytes(n)`` bytes, on the device 16-byte aligned.  Device
+    tensors go through 1-bit plans (``byteps_reduce_onebit_*``,
+    ``prophet_amd/csrc/bpsr_k_onebit.hip``): a compress of many tensors is
+    three launches per device, a fold of many is one; CPU tensors and numpy
+    arrays go through ``onebit.py``.  Everything but float32 passes through.
+
+    A payload is no element-wise dtype, so the PS server cannot fold it:
+    ``Worker.init_tensor`` refuses this compressor.  ``fold_many_into`` is what
+    a worker that gathered every worker's payload computes."""
+
+    ERROR_FEEDBACK = True
+    PACKED = True
+
+    @classmethod
+    def compresses(cls, tensor) -> bool:
+        return _is_f32(tensor)
+
+    @classmethod
+    def payload_like(cls, x):
+        """An uninitialised payload buffer for x, of x's kind and device."""
+        from .onebit import payload_bytes
+        n = int(x.numel()) if _is_torch(x) else int(x.size)
+        if _is_torch(x):
+            import torch
+            return torch.empty(payload_bytes(n), dtype=torch.uint8, device=x.device)
+        return np.empty(payload_bytes(n), dtype=np.uint8)
+
+    residual_like = classmethod(_ErrorFeedback.residual_like.__func__)
+
+    @classmethod
+    def compress(cls, tensor):
+        """The stateless form: one step from a zero residual, which is
+        dropped.  ``ctx`` is ``(dtype, shape)``."""
+        ctx = (tensor.dtype, tuple(tensor.shape))
+        if not cls.compresses(tensor):
+            return tensor, ctx
+        flat = tensor.contiguous() if _is_torch(tensor) else np.ascontiguousarray(tensor)
+        return cls.compress_ef_into(cls.payload_like(flat), cls.residual_like(flat), flat), ctx
+
+    @classmethod
+    def decompress(cls, payload, ctx):
+        dtype, shape = ctx
+        if payload.dtype == dtype:
+            return payload
+        if _is_torch(payload):
+            import torch
+            out = torch.empty(shape, dtype=dtype, device=payload.device)
+        else:
+            out = np.empty(shape, dtype=dtype)
+        return cls.decompress_into(out, payload)
+
+    @classmethod
+    def compress_ef_into(cls, payload, residual, tensor, plans: CastPlanCache | None = None):
+        """``payload, residual = onebit.compress(tensor, residual)``, the
+        residual in place; returns ``payload``."""
+        cls.compress_many_ef_into([payload], [residual], [tensor], plans)
+        return payload
+
+    @classmethod
+    def compress_many_ef_into(cls, payloads, residuals, tensors,
+                              plans: CastPlanCache | None = None):
+        """``compress_ef_into`` for every i, the device tensors as one 1-bit
+        plan per device (three launches); returns ``payloads``."""
+        from . import onebit
+        if len(payloads) != len(tensors) or len(residuals) != len(tensors):
+            raise ValueError("compress_many_ef_into: as many payloads and residuals as tensors")
+        groups: dict = {}
+        for i, (p, r, t) in enumerate(zip(payloads, residuals, tensors)):
+            if not cls.compresses(t) or not _is_f32(r):
+                raise ValueError("onebit_ef needs float32 tensors and float32 residuals")
+            dev = [_on_device(x) for x in (p, r, t)]
+            if any(dev) != all(dev):
+                raise ValueError(f"onebit_ef: tensor {i}'s operands live in one place, a device "
+                                 f"or the host")
+            if dev[0]:
+                cls._check_device_segment(i, t, r, payload=p)
+                groups.setdefault(t.device, []).append((t.reshape(-1), r.reshape(-1), p))
+                continue
+            ra = (r.detach().numpy() if _is_torch(r) else r).reshape(-1)
+            ga = t.detach().numpy() if _is_torch(t) else t
+            pa = _payload_array(p)
+            if ra.size != ga.size or pa.size != onebit.payload_bytes(ga.size):
+                raise ValueError(f"onebit_ef: tensor {i}'s operands differ in size")
+            pa[:], ra[:] = onebit.compress(ga, ra)
+        cls._run(groups, plans, lambda cache, segs: cache.get_onebit(segs),
+                 lambda plan, stream: plan.compress(stream=stream))
+        return payloads
+
+    @classmethod
+    def decompress_into(cls, out, payload, divisor: int = 1, plans: CastPlanCache | None = None):
+        """``out = onebit.decode(payload)`` (divided by ``divisor`` above 1):
+        the one-source fold; returns ``out``."""
+        cls.fold_many_into([out], [[payload]], divisor, plans)
+        return out
+
+    @classmethod
+    def fold_many_into(cls, outs, payload_lists, divisor: int = 1,
+                       plans: CastPlanCache | None = None):
+        """``outs[i] = onebit.fold(payload_lists[i], outs[i].size, divisor)``
+        for every i — every list of the same length N, 1..16 — the device
+        tensors as one 1-bit fold plan per device (ONE launch); returns
+        ``outs``."""
+        from . import onebit
+        if len(outs) != len(payload_lists):
+            raise ValueError("fold_many_into: as many payload lists as outputs")
+        if int(divisor) < 1:
+            raise ValueError(f"divisor {divisor} < 1")
+        nsrc = len(payload_lists[0]) if payload_lists else 1
+        if not 1 <= nsrc <= onebit.MAX_SRCS or any(len(ps) != nsrc for ps in payload_lists):
+            raise ValueError(f"fold_many_into: every output takes the same 1..{onebit.MAX_SRCS} "
+                             f"payloads")
+        groups: dict = {}
+        for i, (o, ps) in enumerate(zip(outs, payload_lists)):
+            if not _is_f32(o):
+                raise ValueError(f"onebit_ef: output {i} must be float32, got {o.dtype}")
+            dev = [_on_device(x) for x in [o] + list(ps)]
+            if any(dev) != all(dev):
+                raise ValueError(f"onebit_ef: output {i} and its payloads live in one place, a "
+                                 f"device or the host")
+            if dev[0]:
+                for p in ps:
+                    cls._check_device_segment(i, o, payload=p)
+                groups.setdefault(o.device, []).append((o.reshape(-1), list(ps)))
+                continue
+            oa = (o.detach().numpy() if _is_torch(o) else o).reshape(-1)
+            oa[:] = onebit.fold([_payload_array(p) for p in ps], oa.size, divisor)
+        cls._run(groups, plans, lambda cache, segs: cache.get_onebit_fold(segs, nsrc),
+                 lambda plan, stream: plan.launch(int(divisor), stream=stream))
+        return outs
+
+    @staticmethod
+    def _check_device_segment(i: int, tensor, resid=None, payload=None) -> None:
+        """One device segment: contiguous float32 operands of one size and a
+        flat uint8 payload of the payload's size, all on one device."""
+        import torch
+        from .onebit import payload_bytes
+        for x in (tensor, resid):
+            if x is not None and (not x.is_contiguous() or x.device != tensor.device
+                                  or x.numel() != tensor.numel()):
+                raise ValueError(f"onebit_ef: tensor {i} needs contiguous operands of one size "
+                                 f"on one device")
+        if payload.dtype != torch.uint8 or not payload.is_contiguous() or payload.dim() != 1 \
+                or payload.device != tensor.device \
+                or payload.numel() != payload_bytes(tensor.numel()):
+            raise ValueError(f"onebit_ef: tensor {i}'s payload must be a flat uint8 tensor of "
+                             f"{payload_bytes(tensor.numel())} bytes on {tensor.device}")
+
+    @staticmethod
+    def _run(groups, plans, get, launch) -> None:
+        """Per device: the plan (from ``plans``, else built and destroyed here,
+        which waits for the launch) and its launch on the current stream."""
+        if not groups:
+            return
+        import torch
+        for device, segs in groups.items():
+            with torch.cuda.device(device):
+                cache = plans if plans is not None else CastPlanCache(1)
+                try:
+                    launch(get(cache, segs), torch.cuda.current_stream(device))
+                finally:
+                    if plans is None:
+                        cache.close()
+
+
 class Compression:
     """Optional gradient compression used during push_pull."""
 
@@ -1105,8 +1311,9 @@ class Compression:
     bf16_ef = BF16EFCompressor
     fp16_sr = FP16SRCompressor
     bf16_sr = BF16SRCompressor
+    onebit_ef = OneBitEFCompressor
 
 
 __all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
            "FP16EFCompressor", "BF16EFCompressor", "FP16SRCompressor", "BF16SRCompressor",
-           "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]
+           "OneBitEFCompressor", "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]

@@ -1,0 +1,128 @@
+"""1-bit sign compression with error feedback: the host definition.
+
+BytePS's sign compressor: a tensor travels as one bit an element plus one
+float32 scale, 32x smaller than float32, and a per-tensor float32 residual
+``r`` gives back what the bit could not carry.  The HIP kernels
+(``prophet_amd/csrc/bpsr_k_onebit.hip``, ``byteps_reduce_onebit_*``) are
+pinned to the numpy lines below; host tensors and numpy arrays go through
+them.  For one tensor of ``n`` float32 elements ``g``::
+
+    c_i   = g_i + r_i                           one IEEE float32 add
+    scale = f32((sum_i f64(|c_i|)) / f64(n))    f64 sum, one f64 divide, one rounding
+    b_i   = 1 if c_i < 0 else 0                 -0.0, +0.0 and NaN give 0
+    r'_i  = c_i - (-scale if b_i else scale)    one IEEE float32 subtract
+    decode_i = -scale if b_i else scale
+
+The order of the float64 sum is the implementation's (here ``math.fsum``, the
+exact sum rounded once; on the device per-wave partials and a finish kernel,
+deterministic for a given plan): on inputs whose ``|c_i|`` are multiples of
+one power of two with a total below 2^53 of it every order gives the same
+bits, on general inputs ``scale`` is within one float32 neighbour.
+
+The payload, little endian: a 16-byte header ``{f32 scale, u32 n_lo, u32 n_hi,
+u32 0}``, then ``ceil(n / 64)`` uint64 words, bit ``k`` of word ``w`` being
+``b_(64 w + k)``, the bits past ``n`` zero.  ``n == 0`` is a header with scale 0.
+
+``fold`` decodes N payloads of the same ``n`` and adds them in argument order,
+a float32 left fold, then divides by ``f32(divisor)`` when ``divisor > 1``.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+HEADER_BYTES = 16
+MAX_SRCS = 16
+
+
+def payload_bytes(n: int) -> int:
+    """Bytes of the payload of ``n`` elements."""
+    if int(n) < 0:
+        raise ValueError(f"negative element count {n}")
+    return HEADER_BYTES + 8 * ((int(n) + 63) // 64)
+
+
+def _f32(x):
+    return np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+
+
+def mean_abs(c) -> np.float32:
+    """``scale`` of the float32 array ``c``: the exact sum, one divide, one
+    rounding."""
+    c = _f32(c)
+    if c.size == 0:
+        return np.float32(0.0)
+    with np.errstate(all="ignore"):
+        a = np.abs(c).astype(np.float64)
+        total = math.fsum(a) if np.isfinite(a).all() else float(a.sum())
+        return np.float32(np.float64(total) / np.float64(c.size))
+
+
+def sign_scale(bits, scale):
+    """``decode``: ``-scale`` where ``bits`` is set, else ``scale`` (float32)."""
+    s = np.float32(scale)
+    return np.where(np.asarray(bits, dtype=bool), -s, s).astype(np.float32)
+
+
+def compress(g, r, scale=None):
+    """One step: ``(payload, r')`` — the payload as a new uint8 array, the new
+    residual as a new float32 array — from the float32 arrays ``g`` and ``r``.
+    ``scale``: the float32 scale to use in place of ``mean_abs(c)`` (a test
+    that read the device's own scale back from a header)."""
+    g, r = _f32(g), _f32(r)
+    if g.size != r.size:
+        raise ValueError(f"onebit: {g.size} elements, {r.size} residuals")
+    n = g.size
+    with np.errstate(all="ignore"):
+        c = g + r
+        s = mean_abs(c) if scale is None else np.float32(scale)
+        b = c < 0
+        rn = c - sign_scale(b, s)
+    payload = np.zeros(payload_bytes(n), dtype=np.uint8)
+    payload[0:4] = np.array([s], dtype="<f4").view(np.uint8)
+    payload[4:12] = np.array([n], dtype="<u8").view(np.uint8)
+    padded = np.zeros(((n + 63) // 64) * 64, dtype=np.uint8)
+    padded[:n] = b
+    payload[HEADER_BYTES:] = np.packbits(padded, bitorder="little")
+    return payload, rn.astype(np.float32)
+
+
+def header(payload):
+    """``(scale, n)`` of a payload (uint8 array)."""
+    p = np.ascontiguousarray(payload).reshape(-1).view(np.uint8)
+    return np.float32(p[0:4].view("<f4")[0]), int(p[4:12].view("<u8")[0])
+
+
+def bits(payload, n: int):
+    """The ``n`` sign bits of a payload, as a bool array.  ``n`` is the
+    caller's: a header is not trusted for sizes."""
+    p = np.ascontiguousarray(payload).reshape(-1).view(np.uint8)
+    if p.size < payload_bytes(n):
+        raise ValueError(f"onebit: a {p.size}-byte payload for {n} elements")
+    return np.unpackbits(p[HEADER_BYTES:payload_bytes(n)], bitorder="little")[:n].astype(bool)
+
+
+def decode(payload, n: int):
+    """``decode`` of one payload: a new float32 array of ``n`` elements."""
+    return sign_scale(bits(payload, n), header(payload)[0])
+
+
+def fold(payloads, n: int, divisor: int = 1):
+    """The N-way decode: the float32 left fold of ``decode(p, n)`` over
+    ``payloads`` in order, divided by ``f32(divisor)`` when ``divisor > 1``."""
+    if not 1 <= len(payloads) <= MAX_SRCS:
+        raise ValueError(f"onebit: {len(payloads)} sources outside 1..{MAX_SRCS}")
+    if int(divisor) < 1:
+        raise ValueError(f"divisor {divisor} < 1")
+    with np.errstate(all="ignore"):
+        out = decode(payloads[0], n)
+        for p in payloads[1:]:
+            out = out + decode(p, n)
+        if int(divisor) > 1:
+            out = out / np.float32(int(divisor))
+    return out.astype(np.float32)
+
+
+__all__ = ["HEADER_BYTES", "MAX_SRCS", "payload_bytes", "mean_abs", "sign_scale", "compress",
+           "header", "bits", "decode", "fold"]

@@ -373,6 +373,11 @@ class Worker:
         ``Compression.bf16``: as bf16 — the keys, partitions and request dtype
         are the compressed tensor's; integers and tensors already of the wire
         dtype pass through as with ``Compression.none``)."""
+        if getattr(compression, "PACKED", False):
+            # the server folds element-wise by dtype; a packed payload needs a
+            # round type of its own (DESIGN.md §11.10)
+            raise ValueError(f"{name}: {compression.__name__} payloads do not travel through "
+                             f"push_pull yet; gather them and use fold_many_into")
         self.declare(name)
         ctx = self.contexts[name]
         size = _nbytes(data)

@@ -69,6 +69,9 @@ EXPORTS = (
     "byteps_reduce_cast_plan_measure", "byteps_reduce_clip_record",
     "byteps_reduce_cast_plan_decompress_scaled",
     "byteps_reduce_cast_plan_create_sgd", "byteps_reduce_cast_plan_apply_sgd",
+    "byteps_reduce_onebit_payload_bytes", "byteps_reduce_onebit_plan_create",
+    "byteps_reduce_onebit_plan_compress", "byteps_reduce_onebit_fold_plan_create",
+    "byteps_reduce_onebit_fold_plan_launch", "byteps_reduce_onebit_plan_destroy",
 )
 
 
@@ -102,6 +105,16 @@ class SgdHyper(ctypes.Structure):
     """``byteps_sgd_hyper`` (include/bpsr/reduce.h)."""
     _fields_ = [("lr", ctypes.c_float), ("momentum", ctypes.c_float),
                 ("weight_decay", ctypes.c_float), ("nesterov", _int)]
+
+
+class OneBitDesc(ctypes.Structure):
+    """``byteps_onebit_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("grad", _vp), ("resid", _vp), ("payload", _vp), ("nelem", ctypes.c_uint64)]
+
+
+class OneBitFoldDesc(ctypes.Structure):
+    """``byteps_onebit_fold_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64)]
 
 
 class SrKey(int):
@@ -190,6 +203,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                      ctypes.POINTER(_vp)]
     L.byteps_reduce_cast_plan_apply_sgd.argtypes = [_vp, _int, ctypes.POINTER(SgdHyper), _vp,
                                                     _int, _vp]
+    L.byteps_reduce_onebit_payload_bytes.argtypes = [ctypes.c_uint64]
+    L.byteps_reduce_onebit_payload_bytes.restype = ctypes.c_uint64
+    L.byteps_reduce_onebit_plan_create.argtypes = [ctypes.POINTER(OneBitDesc), _int,
+                                                   ctypes.POINTER(_vp)]
+    L.byteps_reduce_onebit_plan_compress.argtypes = [_vp, _vp]
+    L.byteps_reduce_onebit_fold_plan_create.argtypes = [ctypes.POINTER(OneBitFoldDesc), _int, _int,
+                                                        ctypes.POINTER(_vp)]
+    L.byteps_reduce_onebit_fold_plan_launch.argtypes = [_vp, _int, _vp]
+    L.byteps_reduce_onebit_plan_destroy.argtypes = [_vp]
     _LIB = L
     return L
 
@@ -370,6 +392,24 @@ class GpuReducer:
         :meth:`SgdPlan.apply` is ONE launch that updates every parameter and
         momentum buffer in place from the wire; no gradient is written."""
         return SgdPlan(self.lib, segments, wire_dtype)
+
+    def onebit_plan(self, segments: Sequence[tuple]) -> "OneBitPlan":
+        """1-bit sign compression with error feedback
+        (byteps_reduce_onebit_plan_create): ``segments`` are ``(grad, resid,
+        payload, nelem)`` of tensors or raw pointers — float32 gradients and
+        residuals, payloads of ``onebit.payload_bytes(nelem)`` bytes, 16-byte
+        aligned.  :meth:`OneBitPlan.compress` is three launches on one stream:
+        every residual is updated in place and every payload written, bit for
+        bit ``prophet_amd.onebit.compress`` given the scale."""
+        return OneBitPlan(self.lib, segments)
+
+    def onebit_fold_plan(self, segments: Sequence[tuple], nsrc: int) -> "OneBitFoldPlan":
+        """The N-way decode (byteps_reduce_onebit_fold_plan_create):
+        ``segments`` are ``(out, payloads, nelem)`` — a float32 output and
+        ``nsrc`` payloads of ``nelem`` elements each, in fold order.
+        :meth:`OneBitFoldPlan.launch` is ONE launch: ``prophet_amd.onebit.fold``
+        bit for bit; ``nsrc == 1`` is the plain decompress."""
+        return OneBitFoldPlan(self.lib, segments, nsrc)
 
     def clip_record(self, rows, max_norm: float, eps: float = 1e-6, inv_scale=None, out=None,
                     stream=None) -> "ClipRecord":
@@ -750,6 +790,94 @@ class SgdPlan:
             self.close()
         except Exception:
             pass
+
+
+def _payload_bytes(nelem: int) -> int:
+    return 16 + 8 * ((int(nelem) + 63) // 64)
+
+
+class _OneBitPlanBase:
+    """What the two 1-bit plans share: the handle, the tensors held until
+    ``close`` (a launch is asynchronous), the stream's device."""
+
+    def __init__(self, lib):
+        self.lib = lib
+        self.handle = _vp()
+        self._keep = []
+        self.first = None
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.byteps_reduce_onebit_plan_destroy(self.handle)
+            self.handle = _vp()
+        self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OneBitPlan(_OneBitPlanBase):
+    """A 1-bit compress plan (``byteps_reduce_onebit_plan_create``).  Tensor
+    operands are bounds-checked before the library sees them."""
+
+    def __init__(self, lib, segments):
+        super().__init__(lib)
+        segments = [tuple(s) for s in segments]
+        for s in segments:
+            if len(s) != 4:
+                raise ValueError(f"onebit plan: a segment of {len(s)} items")
+            if int(s[3]) < 0:
+                raise ValueError(f"negative element count {s[3]}")
+            _fits(int(s[3]) * 4, s[0], s[1])
+            _fits(_payload_bytes(s[3]), s[2])
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (OneBitDesc * max(1, len(segments)))()
+        for d, s in zip(descs, segments):
+            d.grad, d.resid, d.payload, d.nelem = _ptr(s[0]), _ptr(s[1]), _ptr(s[2]), int(s[3])
+        _check(lib.byteps_reduce_onebit_plan_create(descs, len(segments),
+                                                    ctypes.byref(self.handle)))
+
+    def compress(self, stream=None) -> None:
+        """Accumulate, finish, pack (byteps_reduce_onebit_plan_compress)."""
+        _check(self.lib.byteps_reduce_onebit_plan_compress(self.handle,
+                                                           _stream_of(self.first, stream)))
+
+
+class OneBitFoldPlan(_OneBitPlanBase):
+    """A 1-bit fold plan (``byteps_reduce_onebit_fold_plan_create``)."""
+
+    def __init__(self, lib, segments, nsrc):
+        super().__init__(lib)
+        self.nsrc = int(nsrc)
+        segments = [(s[0], list(s[1]), int(s[2])) for s in segments]
+        for out, payloads, nelem in segments:
+            if nelem < 0:
+                raise ValueError(f"negative element count {nelem}")
+            if len(payloads) != self.nsrc:
+                raise ValueError(f"onebit fold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
+            _fits(nelem * 4, out)
+            _fits(_payload_bytes(nelem), *payloads)
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (OneBitFoldDesc * max(1, len(segments)))()
+        rows = []                     # alive through the create call, which copies them
+        for d, (out, payloads, nelem) in zip(descs, segments):
+            row = (_vp * max(1, len(payloads)))(*[_ptr(p) for p in payloads])
+            rows.append(row)
+            d.out, d.payloads, d.nelem = _ptr(out), ctypes.cast(row, ctypes.POINTER(_vp)), nelem
+        _check(lib.byteps_reduce_onebit_fold_plan_create(descs, len(segments), self.nsrc,
+                                                         ctypes.byref(self.handle)))
+
+    def launch(self, divisor: int = 1, stream=None) -> None:
+        """One launch (byteps_reduce_onebit_fold_plan_launch)."""
+        _check(self.lib.byteps_reduce_onebit_fold_plan_launch(self.handle, int(divisor),
+                                                              _stream_of(self.first, stream)))
 
 
 class BlockQueue:

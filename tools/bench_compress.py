@@ -231,7 +231,14 @@ def main() -> int:
                    help="the SGD step inside the decompress against the scaled decompress "
                         "followed by torch's fused and foreach SGD; the ResNet-50 table and "
                         "one segment")
+    p.add_argument("--onebit", action="store_true",
+                   help="1-bit sign compression: the three-launch compress against torch's "
+                        "add, abs().mean(), where, sub without any packing, and the 8-source "
+                        "fold against eight where + add steps on pre-unpacked bool masks; the "
+                        "ResNet-50 table and one segment")
     args = p.parse_args()
+    if args.onebit:
+        return onebit_mode(args)
     if args.sgd:
         return sgd_mode(args)
     if args.clip:
@@ -1294,6 +1301,144 @@ def sgd_mode(args) -> int:
     ok = all(gates.values()) and all(v for c in checks.values() for k, v in c.items()
                                      if isinstance(v, bool))
     return 0 if ok else 1
+
+
+def onebit_mode(args) -> int:
+    """1-bit sign compression, the --sgd protocol.  The
+    compress (accumulate, finish, pack) against torch's composition of the same
+    arithmetic per tensor with NO packing — add, abs().mean(), where, sub —
+    which favours torch; the 8-source fold against eight where + add steps per
+    tensor on bool masks unpacked ahead of time, which favours torch again."""
+    import torch
+
+    from prophet_amd import onebit
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    NSRC = 8
+    out = {"tool": "bench_compress", "mode": "onebit_ef compress and fold", "nsrc": NSRC,
+           "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+
+    def shape(label, seg_rows, arena_elems):
+        nelem = sum(n for _, n in seg_rows)
+        cut = lambda t: [t[o:o + n] for o, n in seg_rows]      # noqa: E731
+        pay_off, at = [], 0
+        for _, n in seg_rows:                    # 16-byte aligned payloads in one arena
+            pay_off.append(at)
+            at += (onebit.payload_bytes(n) + 15) & ~15
+        pcut = lambda t: [t[o:o + onebit.payload_bytes(n)]     # noqa: E731
+                          for o, (_, n) in zip(pay_off, seg_rows)]
+        shifts = torch.arange(8, device=dev, dtype=torch.uint8)
+
+        def unpack(p, n):
+            """The n sign bits of a device payload as a bool tensor."""
+            return ((p[16:].unsqueeze(1) >> shifts) & 1).reshape(-1)[:n].bool()
+
+        with step(f"setup, {label}", 180):
+            g = torch.Generator(device=dev).manual_seed(7)
+            sets = []
+            for _ in range(args.sets):
+                s = {"g": torch.randn(arena_elems, device=dev, generator=g),
+                     "r": torch.zeros(arena_elems, device=dev),
+                     "rt": torch.zeros(arena_elems, device=dev),
+                     "out": torch.empty(arena_elems, device=dev),
+                     "out_t": torch.empty(arena_elems, device=dev),
+                     "payc": torch.empty(at, dtype=torch.uint8, device=dev),
+                     "pay": [torch.empty(at, dtype=torch.uint8, device=dev) for _ in range(NSRC)]}
+                s["comp"] = red.onebit_plan(list(zip(cut(s["g"]), cut(s["r"]), pcut(s["payc"]),
+                                                     [n for _, n in seg_rows])))
+                # the fold's sources: the compress of NSRC different gradients
+                for k in range(NSRC):
+                    gk = torch.randn(arena_elems, device=dev, generator=g) * (k + 1)
+                    pl = red.onebit_plan(list(zip(cut(gk), cut(s["rt"]), pcut(s["pay"][k]),
+                                                  [n for _, n in seg_rows])))
+                    pl.compress()
+                    pl.close()
+                    s["rt"].zero_()
+                s["fold"] = red.onebit_fold_plan(
+                    [(o, [pcut(s["pay"][k])[i] for k in range(NSRC)], n)
+                     for i, (o, (_, n)) in enumerate(zip(cut(s["out"]), seg_rows))], NSRC)
+                s["masks"] = [[unpack(p, n) for p, (_, n) in zip(pcut(s["pay"][k]), seg_rows)]
+                              for k in range(NSRC)]
+                s["scales"] = [[p[:4].view(torch.float32).clone() for p in pcut(s["pay"][k])]
+                               for k in range(NSRC)]
+                sets.append(s)
+            torch.cuda.synchronize()
+
+        def compress(k):
+            sets[k]["comp"].compress()
+
+        def torch_compress(k):
+            s = sets[k]
+            for gi, ri in zip(cut(s["g"]), cut(s["rt"])):
+                c = gi + ri
+                scale = c.abs().mean()
+                torch.sub(c, torch.where(c < 0, -scale, scale), out=ri)
+
+        def fold(k):
+            sets[k]["fold"].launch(1)
+
+        def torch_fold(k):
+            s = sets[k]
+            for i, o in enumerate(cut(s["out_t"])):
+                sc = s["scales"][0][i]
+                torch.where(s["masks"][0][i], -sc, sc, out=o)
+                for j in range(1, NSRC):
+                    sc = s["scales"][j][i]
+                    o.add_(torch.where(s["masks"][j][i], -sc, sc))
+
+        with step(f"check, {label}", 180):
+            s = sets[0]
+            torch_compress(0)
+            s["rt"].zero_()
+            compress(0)
+            fold(0)
+            torch_fold(0)
+            torch.cuda.synchronize()
+            bits_ok = all(bool(torch.equal(unpack(p, n), gi < 0))      # r was zero: c = g
+                          for p, gi, (_, n) in zip(pcut(s["payc"]), cut(s["g"]), seg_rows))
+            fold_ok = all(bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
+                          for a, b in zip(cut(s["out"]), cut(s["out_t"])))
+            checks[label] = {"compress_bits_equal_torch_signs": bits_ok,
+                             "fold_equals_torch_left_fold": fold_ok}
+            s["r"].zero_()
+        res = timed_rounds(torch, {"compress": (compress, args.inner),
+                                   "torch_compress": (torch_compress, args.inner),
+                                   "fold": (fold, args.inner),
+                                   "torch_fold": (torch_fold, args.inner)}, len(sets), args)
+        # bytes an element the design moves: 12 + 8.125 (compress), 4 + N / 8 (fold)
+        for name, per in (("compress", 20.125), ("fold", 4 + NSRC / 8)):
+            res[name]["bytes_per_elem"] = per
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        for ours, theirs in (("compress", "torch_compress"), ("fold", "torch_fold")):
+            sp = max(res[ours]["spread_ms"], res[theirs]["spread_ms"])
+            gates[f"{label}_{ours}_beats_torch"] = res[theirs]["ms"] - res[ours]["ms"] > sp
+        for s in sets:
+            s["comp"].close()
+            s["fold"].close()
+        return {"segments": len(seg_rows), "elems": nelem, "results": res}
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    total_bytes, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    out["iteration"] = shape("table", [(o // 2, ln // 2) for o, ln in rows], total_bytes // 2)
+    torch.cuda.empty_cache()
+    out["big"] = shape("big", [(0, args.elems)], args.elems)
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    return 0 if all(gates.values()) and all(v for c in checks.values() for v in c.values()) else 1
 
 
 def end_to_end(nelem: int, iters: int, where: str) -> dict:
