@@ -79,7 +79,10 @@ extern "C" {
  *                       inside the decompress)
  *    additive, still 5: byteps_reduce_onebit_* (byteps_onebit_desc,
  *                       byteps_onebit_fold_desc: 1-bit sign compression with
- *                       error feedback) */
+ *                       error feedback)
+ *    additive, still 5: byteps_reduce_onebit_refold_plan_create / _launch
+ *                       (byteps_onebit_refold_desc: the server round of the
+ *                       1-bit wire) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -706,6 +709,30 @@ int byteps_reduce_onebit_fold_plan_create(const byteps_onebit_fold_desc* segs, i
 int byteps_reduce_onebit_fold_plan_launch(byteps_reduce_onebit_plan* plan, int divisor,
                                           void* stream);
 int byteps_reduce_onebit_plan_destroy(byteps_reduce_onebit_plan* plan);
+
+/* The server round of the 1-bit wire (prophet_amd/onebit.py's
+ * refold): per segment the nsrc pushed payloads are decoded and left-folded in
+ * argument order (no divisor), and the sum — held in registers, never written
+ * — is compressed against the server's FLOAT32 residual `resid` into
+ * `out_payload`, exactly as byteps_reduce_onebit_plan_compress compresses a
+ * gradient: three launches on `stream`, no host synchronisation.  Sizes come
+ * from the plan, never from a source's header.  An empty segment that names an
+ * output payload gets its header.
+ *
+ * EARGS before any HIP call, every buffer untouched: a null pointer with nelem >
+ * 0, a source or output payload that is not 16-byte aligned, more than 2^37
+ * elements a segment, nsrc outside 1..16, any two byte ranges of the plan
+ * overlapping (sources, residual, output payload), a refold launch on a
+ * compress or fold plan or the reverse.  _plan_destroy frees it. */
+typedef struct byteps_onebit_refold_desc {
+  const void* const* payloads; /* nsrc of them; read by _refold_plan_create alone */
+  void* resid;
+  void* out_payload;
+  uint64_t nelem;
+} byteps_onebit_refold_desc;
+int byteps_reduce_onebit_refold_plan_create(const byteps_onebit_refold_desc* segs, int nsegs,
+                                            int nsrc, byteps_reduce_onebit_plan** out);
+int byteps_reduce_onebit_refold_plan_launch(byteps_reduce_onebit_plan* plan, void* stream);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

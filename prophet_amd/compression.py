@@ -336,6 +336,15 @@ class CastPlanCache:
             for o, ps in segs)
         return self._get(key, lambda: _new_onebit_fold_plan(segs, nsrc))
 
+    def get_onebit_refold(self, segs, nsrc: int):
+        """The 1-bit refold plan (``GpuReducer.onebit_refold_plan``) over
+        ``segs`` of ``(payloads, resid, out_payload)`` device tensors on the
+        current device."""
+        key = ("onebit_refold", int(nsrc)) + tuple(
+            (int(r.data_ptr()), int(o.data_ptr()), int(r.numel()))
+            + tuple(int(p.data_ptr()) for p in ps) for ps, r, o in segs)
+        return self._get(key, lambda: _new_onebit_refold_plan(segs, nsrc))
+
     def close(self) -> None:
         while self._plans:
             _, plan = self._plans.popitem(last=False)
@@ -350,6 +359,11 @@ def _new_onebit_plan(segs):
 def _new_onebit_fold_plan(segs, nsrc: int):
     from .torch_ops import _red
     return _red().onebit_fold_plan([(o, ps, int(o.numel())) for o, ps in segs], nsrc)
+
+
+def _new_onebit_refold_plan(segs, nsrc: int):
+    from .torch_ops import _red
+    return _red().onebit_refold_plan([(ps, r, o, int(r.numel())) for ps, r, o in segs], nsrc)
 
 
 def _new_sgd_plan(triples, wire_dtype: int = 2):
@@ -1144,8 +1158,11 @@ class OneBitEFCompressor(Compressor):
     arrays go through ``onebit.py``.  Everything but float32 passes through.
 
     A payload is no element-wise dtype, so the PS server cannot fold it:
-    ``Worker.init_tensor`` refuses this compressor.  ``fold_many_into`` is what
-    a worker that gathered every worker's payload computes."""
+    ``Worker.init_tensor`` takes this compressor only over a frontend that
+    carries packed payloads (``ServerFrontend``: ``packed_round.PackedRound``
+    runs ``refold_many_into``, the two-way round of DESIGN.md §11.11).
+    ``fold_many_into`` is what a worker that gathered every worker's payload
+    computes."""
 
     ERROR_FEEDBACK = True
     PACKED = True
@@ -1266,6 +1283,44 @@ class OneBitEFCompressor(Compressor):
         cls._run(groups, plans, lambda cache, segs: cache.get_onebit_fold(segs, nsrc),
                  lambda plan, stream: plan.launch(int(divisor), stream=stream))
         return outs
+
+    @classmethod
+    def refold_many_into(cls, out_payloads, residuals, payload_lists,
+                         plans: CastPlanCache | None = None):
+        """The server round: ``out_payloads[i], residuals[i] =
+        onebit.refold(payload_lists[i], residuals[i].size, residuals[i])`` for
+        every i — every list of the same length N, 1..16, the residual in
+        place — the device tensors as one 1-bit refold plan per device (three
+        launches, the folded sum never written); returns ``out_payloads``."""
+        from . import onebit
+        if len(out_payloads) != len(payload_lists) or len(residuals) != len(payload_lists):
+            raise ValueError("refold_many_into: as many output payloads and residuals as "
+                             "payload lists")
+        nsrc = len(payload_lists[0]) if payload_lists else 1
+        if not 1 <= nsrc <= onebit.MAX_SRCS or any(len(ps) != nsrc for ps in payload_lists):
+            raise ValueError(f"refold_many_into: every segment takes the same "
+                             f"1..{onebit.MAX_SRCS} payloads")
+        groups: dict = {}
+        for i, (o, r, ps) in enumerate(zip(out_payloads, residuals, payload_lists)):
+            if not _is_f32(r):
+                raise ValueError(f"onebit_ef: residual {i} must be float32, got {r.dtype}")
+            dev = [_on_device(x) for x in [o, r] + list(ps)]
+            if any(dev) != all(dev):
+                raise ValueError(f"onebit_ef: segment {i}'s operands live in one place, a device "
+                                 f"or the host")
+            if dev[0]:
+                for p in [o] + list(ps):
+                    cls._check_device_segment(i, r, payload=p)
+                groups.setdefault(r.device, []).append((list(ps), r.reshape(-1), o))
+                continue
+            ra = (r.detach().numpy() if _is_torch(r) else r).reshape(-1)
+            oa = _payload_array(o)
+            if oa.size != onebit.payload_bytes(ra.size):
+                raise ValueError(f"onebit_ef: segment {i}'s operands differ in size")
+            oa[:], ra[:] = onebit.refold([_payload_array(p) for p in ps], ra.size, ra)
+        cls._run(groups, plans, lambda cache, segs: cache.get_onebit_refold(segs, nsrc),
+                 lambda plan, stream: plan.launch(stream=stream))
+        return out_payloads
 
     @staticmethod
     def _check_device_segment(i: int, tensor, resid=None, payload=None) -> None:

@@ -311,14 +311,24 @@ static hipError_t onebit_with_pol(int pol, F&& f) {
 hipError_t launch_onebit_compress(const OneBitCompress& p, uint64_t resid_bytes, const Tuning& tu,
                                   hipStream_t s) {
   if (p.nsegs == 0) return hipSuccess;
+  const hipError_t e = onebit_with_pol(cast_store_pol(tu, resid_bytes), [&](auto POL) {
+    if (!p.nrecs) return hipSuccess;
+    return launch_cast_kernel<onebit_accum_kernel<decltype(POL)::value>>(
+        p, p.nrecs, tu.occ_min_tiles_batch, tu, s);
+  });
+  return e == hipSuccess ? launch_onebit_finish_pack(p, resid_bytes, tu, s) : e;
+}
+
+// FINISH and PACK alone: the tail of a compress whose first pass has run on
+// `s` (ACCUMULATE above, or bpsr_k_onebit_refold.hip's REFOLD-ACCUMULATE).
+hipError_t launch_onebit_finish_pack(const OneBitCompress& p, uint64_t resid_bytes,
+                                     const Tuning& tu, hipStream_t s) {
+  if (p.nsegs == 0) return hipSuccess;
   return onebit_with_pol(cast_store_pol(tu, resid_bytes), [&](auto POL) {
     constexpr int kPol = decltype(POL)::value;
-    hipError_t e = hipSuccess;
-    if (p.nrecs)
-      e = launch_cast_kernel<onebit_accum_kernel<kPol>>(p, p.nrecs, tu.occ_min_tiles_batch, tu, s);
-    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(onebit_finish_kernel, dim3(p.nsegs), dim3(kFinishBlock), 0, s, p);
-    if ((e = hipGetLastError()) != hipSuccess || !p.nrecs) return e;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !p.nrecs) return e;
     return launch_cast_kernel<onebit_pack_kernel<kPol>>(p, p.nrecs, tu.occ_min_tiles_batch, tu, s);
   });
 }

@@ -11,7 +11,9 @@
 // c = g + r over r and leaves one f64 partial of sum |c| per wave, FINISH adds
 // each segment's partials up in a fixed order and writes its header, PACK
 // reads the scale from the header, writes r' = c -/+ scale and the bit words.
-// A fold is one launch over a table of per-wave records.
+// A fold is one launch over a table of per-wave records.  A refold (the server
+// round) is a compress whose first pass folds N payloads in
+// registers in place of reading a gradient.
 #pragma once
 
 #include "bpsr_internal.h"
@@ -72,10 +74,26 @@ struct OneBitFold {
   int divisor;
 };
 
+// The server round (bpsr_k_onebit_refold.hip): a compress whose input is the
+// fold of `nsrc` payloads.  It runs over the compress table — a record's `b`
+// the residual tile, `a` unused, `seg` also the row of sources — and leaves
+// the compress's partials.
+struct OneBitRefold {
+  OneBitCompress c;
+  const unsigned char* const* srcs;  // [nsegs * nsrc], as OneBitFold::srcs
+  int nsrc;
+};
+
 // ACCUMULATE, FINISH and PACK on `s`; `resid_bytes`: what ACCUMULATE writes
 // (store policy).
 hipError_t launch_onebit_compress(const OneBitCompress& p, uint64_t resid_bytes, const Tuning& tu,
                                   hipStream_t s);
+// FINISH and PACK alone, after a first pass on `s`.
+hipError_t launch_onebit_finish_pack(const OneBitCompress& p, uint64_t resid_bytes,
+                                     const Tuning& tu, hipStream_t s);
+// REFOLD-ACCUMULATE, FINISH and PACK on `s`.
+hipError_t launch_onebit_refold(const OneBitRefold& p, uint64_t resid_bytes, const Tuning& tu,
+                                hipStream_t s);
 // The fold; `out_bytes`: what it writes (store policy).
 hipError_t launch_onebit_fold(const OneBitFold& p, uint64_t out_bytes, const Tuning& tu,
                               hipStream_t s);

@@ -25,6 +25,8 @@ u32 0}``, then ``ceil(n / 64)`` uint64 words, bit ``k`` of word ``w`` being
 
 ``fold`` decodes N payloads of the same ``n`` and adds them in argument order,
 a float32 left fold, then divides by ``f32(divisor)`` when ``divisor > 1``.
+``refold`` is the server's round: the fold of the N pushed payloads, compressed
+again against the server's own residual.
 """
 from __future__ import annotations
 
@@ -124,5 +126,13 @@ def fold(payloads, n: int, divisor: int = 1):
     return out.astype(np.float32)
 
 
+def refold(payloads, n: int, r, scale=None):
+    """The server round: ``compress(fold(payloads, n, 1), r, scale)`` — the N
+    payloads decoded and left-folded in argument order, no divisor (averaging
+    stays in the worker's decode), then one compress step against the server
+    residual ``r``.  Returns ``(payload, r')`` as ``compress`` does."""
+    return compress(fold(payloads, n, 1), r, scale)
+
+
 __all__ = ["HEADER_BYTES", "MAX_SRCS", "payload_bytes", "mean_abs", "sign_scale", "compress",
-           "header", "bits", "decode", "fold"]
+           "header", "bits", "decode", "fold", "refold"]

@@ -81,6 +81,13 @@ one clip record made as above, and the step multiplies by its ``mult``; with
 ``SgdStep(skip_nonfinite=True)`` an overflowed iteration leaves parameters
 and momenta untouched, decided on the device.  ``Worker.momentum`` /
 ``reset_momentum`` read and zero a context's momentum buffer.
+
+``Compression.onebit_ef`` (float32 tensors) travels under
+request type ``kCompressedPushPull``: every partition is a 1-bit payload of
+its own in a flat uint8 staging buffer, ``ServerFrontend`` hands the requests
+to its ``packed_round.PackedRound`` store — decode, sum, compress again against
+the store's residual — and one fold plan decodes what was pulled, dividing for
+``average``.  ``stats``, ``clip_norm`` and ``apply`` refuse such a context.
 """
 from __future__ import annotations
 
@@ -94,24 +101,46 @@ from .dtypes import DType, elem_size
 from .reducer import SrKey
 
 K_DEFAULT_PUSH_PULL = 0     # RequestType::kDefaultPushPull (common.h:68-71)
+K_COMPRESSED_PUSH_PULL = 2  # RequestType::kCompressedPushPull (common.h:245)
 
 
 class ServerFrontend:
     """The handler in front of the GPU-resident server: decodes the request
     word, checks one key per request (server.cc:150-171) and forwards."""
 
+    # kCompressedPushPull requests (packed payloads: Compression.onebit_ef) go
+    # to a store of this front end's own, packed_round.PackedRound
+    carries_packed = True
+
     def __init__(self, server, size: int | None = None):
         self.server = server
         cfg = getattr(server, "cfg", None)
         self.size = size if size is not None else (cfg.num_workers if cfg is not None else None)
+        self.packed = None                   # the PackedRound, made on first use
+        self._packed_lock = threading.Lock()
 
     def push(self, cmd: int, key: int, worker: int, data, nbytes: int) -> None:
         req, dtype = depair_command(cmd)
+        if req == K_COMPRESSED_PUSH_PULL:
+            with self._packed_lock:
+                if self.packed is None:
+                    if not self.size:
+                        raise ValueError("kCompressedPushPull: the frontend does not know the "
+                                         "worker count")
+                    from .packed_round import PackedRound
+                    self.packed = PackedRound(self.size)
+            return self.packed.push(key, worker, data, nbytes)
         if req != K_DEFAULT_PUSH_PULL:       # server.cc:151 CHECK_EQ(type.requestType, ...)
             raise ValueError(f"request type {req} is not kDefaultPushPull")
         self.server.push(key, worker, data, dtype, nbytes=nbytes)
 
-    def pull(self, key: int, out, nbytes: int) -> None:
+    def pull(self, key: int, out, nbytes: int, worker: int | None = None) -> None:
+        """``worker``: who pulls — a packed key hands out the round that
+        worker pushed last; the element-wise server needs no name."""
+        if self.packed is not None and self.packed.owns(key):
+            if worker is None:
+                raise ValueError(f"key {key}: a pull of a packed key names its worker")
+            return self.packed.pull(key, worker, out, nbytes)
         self.server.pull(key, out, nbytes=nbytes)
 
 
@@ -145,12 +174,24 @@ class Context:
     @property
     def residual(self):
         """The error-feedback residual, or None."""
+        if isinstance(self.extra, PackedState):
+            return self.extra.residual
         return None if isinstance(self.extra, SrKey) else self.extra
 
     @property
     def sr_key(self) -> int:
         """The stochastic-rounding key, or 0."""
         return int(self.extra) if isinstance(self.extra, SrKey) else 0
+
+
+@dataclass
+class PackedState:
+    """``Context.extra`` of a packed context (``Compression.onebit_ef``): the
+    tensor-sized f32 residual and, per partition, ``(element offset, count,
+    staging byte offset)`` — every partition a payload of its own in the flat
+    uint8 staging buffer, at a 16-byte-aligned offset."""
+    residual: object
+    cuts: list
 
 
 class GradStats:
@@ -375,9 +416,11 @@ class Worker:
         dtype pass through as with ``Compression.none``)."""
         if getattr(compression, "PACKED", False):
             # the server folds element-wise by dtype; a packed payload needs a
-            # round type of its own (DESIGN.md §11.10)
-            raise ValueError(f"{name}: {compression.__name__} payloads do not travel through "
-                             f"push_pull yet; gather them and use fold_many_into")
+            # round type of its own (DESIGN.md §11.11), which the front end carries
+            if not getattr(self.frontend, "carries_packed", False):
+                raise ValueError(f"{name}: {compression.__name__} payloads do not travel through "
+                                 f"push_pull yet; gather them and use fold_many_into")
+            return self._init_packed(name, data, dtype, compression)
         self.declare(name)
         ctx = self.contexts[name]
         size = _nbytes(data)
@@ -407,6 +450,99 @@ class Worker:
             ctx.initialized = True
         return ctx
 
+    def _init_packed(self, name: str, data, dtype: int, compression) -> Context:
+        """``init_tensor`` of a packed context: the f32 tensor is cut under the
+        partition bound as any other, and every partition travels as a payload
+        of its own, with its own scale.  The init push of a key is the payload
+        of its partition's zeros, built on the host: the store's barrier."""
+        import numpy as np
+        from .onebit import HEADER_BYTES, payload_bytes
+        if not compression.compresses(data):
+            raise ValueError(f"{name}: {compression.__name__} needs a float32 tensor")
+        self.declare(name)
+        ctx = self.contexts[name]
+        with ctx.init_lock:
+            if ctx.initialized:
+                return ctx
+            size = _nbytes(data)
+            if size <= 0:
+                raise ValueError("init tensor size not larger than 0")      # operations.cc:229
+            if self.bound % 4:
+                raise ValueError(f"{name}: a partition bound of {self.bound} bytes cuts a float32")
+            ctx.compressor = compression
+            ctx.orig_dtype, ctx.orig_size = int(dtype), size
+            start, at = ctx.declared_key << 16, 0
+            cuts, ctx.parts = [], []
+            for i, (off, ln) in enumerate(self._partition(size)):
+                cuts.append((off // 4, ln // 4, at))
+                ctx.parts.append((start + i, at, payload_bytes(ln // 4)))
+                at += (payload_bytes(ln // 4) + 15) & ~15
+            ctx.key_list = [k for k, _, _ in ctx.parts]
+            ctx.size, ctx.dtype = at, int(DType.UINT8)
+            if hasattr(data, "data_ptr"):
+                import torch
+                ctx.staging = torch.zeros(at, dtype=torch.uint8, device=data.device)
+                resid = torch.zeros(size // 4, dtype=torch.float32, device=data.device)
+            else:
+                ctx.staging = np.zeros(at, dtype=np.uint8)
+                resid = np.zeros(size // 4, dtype=np.float32)
+            ctx.extra = PackedState(resid, cuts)
+            cmd = cantor_command(K_COMPRESSED_PUSH_PULL, ctx.dtype)
+            for (key, _, ln), (_, cnt, _) in zip(ctx.parts, cuts):
+                zero = np.zeros(ln, dtype=np.uint8)
+                zero[4:12] = np.array([cnt], dtype="<u8").view(np.uint8)
+                assert ln >= HEADER_BYTES
+                self.frontend.push(cmd, key, self.rank, zero, ln)
+            ctx.initialized = True
+        return ctx
+
+    def _packed_segments(self, ctx: Context, tensor):
+        """Per partition of a packed context: ``(tensor part, residual part,
+        payload)``, flat views."""
+        flat = _contiguous(tensor).reshape(-1)
+        return [(flat[e:e + cnt], ctx.extra.residual[e:e + cnt], _slice(ctx.staging, at, ln))
+                for (e, cnt, at), (_, _, ln) in zip(ctx.extra.cuts, ctx.parts)]
+
+    def _check_packed(self, ctx: Context, tensor, out) -> None:
+        from .compression import _is_f32
+        for x, what in ((tensor, "tensor"), (out, "output tensor")):
+            if not _is_f32(x) or _nbytes(x) != ctx.orig_size:
+                raise ValueError(f"{ctx.name}: {what} of {_nbytes(x)} bytes of {x.dtype}, "
+                                 f"declared {ctx.orig_size} of float32")
+            if _place(x) != _place(ctx.staging) or \
+                    hasattr(x, "data_ptr") != hasattr(ctx.staging, "data_ptr"):
+                raise ValueError(f"{ctx.name}: {what} does not live where the context does")
+
+    def _push_pull_packed(self, ctx: Context, tensor, output, order, average: bool,
+                          stats: bool) -> None:
+        """push_pull of a packed context: one compress plan over the
+        partitions (three launches), the payloads pushed and pulled under
+        kCompressedPushPull, then one fold plan (one source) with the
+        ``average`` divisor into the output."""
+        if stats:
+            raise ValueError(f"{ctx.name}: stats needs an element-wise wire, not "
+                             f"{ctx.compressor.__name__}")
+        out = tensor if output is None else output
+        self._check_packed(ctx, tensor, out)
+        divisor = 1
+        if average:
+            divisor = getattr(self.frontend, "size", None)
+            if not divisor:
+                raise ValueError("average: the frontend does not know the worker count")
+        segs = self._packed_segments(ctx, tensor)
+        ctx.compressor.compress_many_ef_into([p for _, _, p in segs], [r for _, r, _ in segs],
+                                             [g for g, _, _ in segs], plans=self._cast_plans)
+        cmd = cantor_command(K_COMPRESSED_PUSH_PULL, ctx.dtype)
+        idx = range(len(ctx.parts)) if order is None else order
+        for i in idx:
+            key, off, ln = ctx.parts[i]
+            self.frontend.push(cmd, key, self.rank, _slice(ctx.staging, off, ln), ln)
+        for key, off, ln in ctx.parts:
+            self.frontend.pull(key, _slice(ctx.staging, off, ln), ln, worker=self.rank)
+        outs = [o for o, _, _ in self._packed_segments(ctx, out)]
+        ctx.compressor.fold_many_into(outs, [[p] for _, _, p in segs], divisor,
+                                      plans=self._cast_plans)
+
     # ---------------------------------------------------------------- push_pull
     def push_pull(self, name: str, tensor, output=None, order=None,
                   average: bool = False, stats: bool = False) -> None:
@@ -422,6 +558,8 @@ class Worker:
         ctx = self.contexts[name]
         if not ctx.initialized:
             raise RuntimeError(f"{name}: init_tensor first")
+        if getattr(ctx.compressor, "PACKED", False):
+            return self._push_pull_packed(ctx, tensor, output, order, average, stats)
         if ctx.compressor is not None:
             return self._push_pull_compressed(ctx, tensor, output, order, average, stats)
         if stats:
@@ -588,6 +726,13 @@ class Worker:
         Returns the release groups as lists of (declared key, partition)."""
         from .prophet import PushTask, release_groups
         ctxs = [self.contexts[n] for n in self._declared if n in tensors]
+        packed = [c for c in ctxs if getattr(c.compressor, "PACKED", False)]
+        if packed and (stats or clip_norm is not None or apply is not None):
+            raise ValueError(f"stats, clip_norm and apply need an element-wise wire: "
+                             f"{packed[0].name} travels as {packed[0].compressor.__name__}")
+        for c in packed:                  # before anything is pushed
+            self._check_packed(c, tensors[c.name], tensors[c.name])
+        pnames = {c.name for c in packed}
         if clip_norm is None and unscale is not None:
             raise ValueError("unscale goes with clip_norm")
         if clip_norm is not None:         # before anything is pushed
@@ -621,8 +766,14 @@ class Worker:
         wire = {c.name: tensors[c.name] if c.compressor is None else c.staging for c in ctxs}
         casts = {}
         for c in ctxs:
-            if c.compressor is not None:
+            if c.compressor is not None and c.name not in pnames:
                 casts.setdefault(c.compressor, []).append(c)
+        # packed contexts: one compress plan over all their partitions
+        psegs = [s for c in packed for s in self._packed_segments(c, tensors[c.name])]
+        if psegs:
+            packed[0].compressor.compress_many_ef_into(
+                [p for _, _, p in psegs], [r for _, r, _ in psegs], [g for g, _, _ in psegs],
+                plans=self._cast_plans)
         for comp, cs in casts.items():
             comp.compress_many_with([c.staging for c in cs],
                                     [_contiguous(tensors[c.name]) for c in cs],
@@ -632,11 +783,19 @@ class Worker:
             for t in g:
                 c = by_key[t.grad]
                 key, off, ln = c.parts[t.part]
-                self.frontend.push(cantor_command(K_DEFAULT_PUSH_PULL, c.dtype), key, self.rank,
+                req = K_COMPRESSED_PUSH_PULL if c.name in pnames else K_DEFAULT_PUSH_PULL
+                self.frontend.push(cantor_command(req, c.dtype), key, self.rank,
                                    _slice(wire[c.name], off, ln), ln)
         for c in ctxs:
             for key, off, ln in c.parts:
-                self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
+                if c.name in pnames:
+                    self.frontend.pull(key, _slice(wire[c.name], off, ln), ln, worker=self.rank)
+                else:
+                    self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
+        if psegs:                         # one fold plan (one source) over all of them
+            packed[0].compressor.fold_many_into([g for g, _, _ in psegs],
+                                                [[p] for _, _, p in psegs], divisor,
+                                                plans=self._cast_plans)
         if apply is not None:
             self._apply_iteration(ctxs, casts, tensors, divisor, stats, clip_norm, clip_eps,
                                   unscale, apply)
@@ -861,4 +1020,5 @@ def _slice(x, off: int, ln: int):
     return x.reshape(-1).view(np.uint8)[off:off + ln]
 
 
-__all__ = ["ServerFrontend", "Worker", "Context", "GradStats", "GradClip", "SgdStep", "K_DEFAULT_PUSH_PULL", "DType", "elem_size"]
+__all__ = ["ServerFrontend", "Worker", "Context", "PackedState", "GradStats", "GradClip", "SgdStep",
+           "K_DEFAULT_PUSH_PULL", "K_COMPRESSED_PUSH_PULL", "DType", "elem_size"]

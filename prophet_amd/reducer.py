@@ -72,6 +72,7 @@ EXPORTS = (
     "byteps_reduce_onebit_payload_bytes", "byteps_reduce_onebit_plan_create",
     "byteps_reduce_onebit_plan_compress", "byteps_reduce_onebit_fold_plan_create",
     "byteps_reduce_onebit_fold_plan_launch", "byteps_reduce_onebit_plan_destroy",
+    "byteps_reduce_onebit_refold_plan_create", "byteps_reduce_onebit_refold_plan_launch",
 )
 
 
@@ -115,6 +116,12 @@ class OneBitDesc(ctypes.Structure):
 class OneBitFoldDesc(ctypes.Structure):
     """``byteps_onebit_fold_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64)]
+
+
+class OneBitRefoldDesc(ctypes.Structure):
+    """``byteps_onebit_refold_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("payloads", ctypes.POINTER(_vp)), ("resid", _vp), ("out_payload", _vp),
+                ("nelem", ctypes.c_uint64)]
 
 
 class SrKey(int):
@@ -212,6 +219,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                         ctypes.POINTER(_vp)]
     L.byteps_reduce_onebit_fold_plan_launch.argtypes = [_vp, _int, _vp]
     L.byteps_reduce_onebit_plan_destroy.argtypes = [_vp]
+    L.byteps_reduce_onebit_refold_plan_create.argtypes = [ctypes.POINTER(OneBitRefoldDesc), _int,
+                                                          _int, ctypes.POINTER(_vp)]
+    L.byteps_reduce_onebit_refold_plan_launch.argtypes = [_vp, _vp]
     _LIB = L
     return L
 
@@ -410,6 +420,16 @@ class GpuReducer:
         :meth:`OneBitFoldPlan.launch` is ONE launch: ``prophet_amd.onebit.fold``
         bit for bit; ``nsrc == 1`` is the plain decompress."""
         return OneBitFoldPlan(self.lib, segments, nsrc)
+
+    def onebit_refold_plan(self, segments: Sequence[tuple], nsrc: int) -> "OneBitRefoldPlan":
+        """The server round of the 1-bit wire
+        (byteps_reduce_onebit_refold_plan_create): ``segments`` are
+        ``(payloads, resid, out_payload, nelem)`` — ``nsrc`` pushed payloads,
+        the server's flat float32 residual, the payload every worker pulls.
+        :meth:`OneBitRefoldPlan.launch` is three launches on one stream:
+        ``prophet_amd.onebit.refold`` given the scale, the folded sum never
+        written."""
+        return OneBitRefoldPlan(self.lib, segments, nsrc)
 
     def clip_record(self, rows, max_norm: float, eps: float = 1e-6, inv_scale=None, out=None,
                     stream=None) -> "ClipRecord":
@@ -797,7 +817,7 @@ def _payload_bytes(nelem: int) -> int:
 
 
 class _OneBitPlanBase:
-    """What the two 1-bit plans share: the handle, the tensors held until
+    """What the 1-bit plans share: the handle, the tensors held until
     ``close`` (a launch is asynchronous), the stream's device."""
 
     def __init__(self, lib):
@@ -878,6 +898,39 @@ class OneBitFoldPlan(_OneBitPlanBase):
         """One launch (byteps_reduce_onebit_fold_plan_launch)."""
         _check(self.lib.byteps_reduce_onebit_fold_plan_launch(self.handle, int(divisor),
                                                               _stream_of(self.first, stream)))
+
+
+class OneBitRefoldPlan(_OneBitPlanBase):
+    """A 1-bit refold plan (``byteps_reduce_onebit_refold_plan_create``)."""
+
+    def __init__(self, lib, segments, nsrc):
+        super().__init__(lib)
+        self.nsrc = int(nsrc)
+        segments = [(list(s[0]), s[1], s[2], int(s[3])) for s in segments]
+        for payloads, resid, out, nelem in segments:
+            if nelem < 0:
+                raise ValueError(f"negative element count {nelem}")
+            if len(payloads) != self.nsrc:
+                raise ValueError(f"onebit refold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
+            _fits(nelem * 4, resid)
+            _fits(_payload_bytes(nelem), out, *payloads)
+        self._keep = segments
+        self.first = next((s[1] for s in segments if hasattr(s[1], "device")), None)
+        self.nsegs = len(segments)
+        descs = (OneBitRefoldDesc * max(1, len(segments)))()
+        rows = []                     # alive through the create call, which copies them
+        for d, (payloads, resid, out, nelem) in zip(descs, segments):
+            row = (_vp * max(1, len(payloads)))(*[_ptr(p) for p in payloads])
+            rows.append(row)
+            d.payloads, d.resid = ctypes.cast(row, ctypes.POINTER(_vp)), _ptr(resid)
+            d.out_payload, d.nelem = _ptr(out), nelem
+        _check(lib.byteps_reduce_onebit_refold_plan_create(descs, len(segments), self.nsrc,
+                                                           ctypes.byref(self.handle)))
+
+    def launch(self, stream=None) -> None:
+        """Refold-accumulate, finish, pack (byteps_reduce_onebit_refold_plan_launch)."""
+        _check(self.lib.byteps_reduce_onebit_refold_plan_launch(self.handle,
+                                                                _stream_of(self.first, stream)))
 
 
 class BlockQueue:
