@@ -82,7 +82,10 @@ extern "C" {
  *                       error feedback)
  *    additive, still 5: byteps_reduce_onebit_refold_plan_create / _launch
  *                       (byteps_onebit_refold_desc: the server round of the
- *                       1-bit wire) */
+ *                       1-bit wire)
+ *    additive, still 5: byteps_reduce_topk_* (byteps_topk_desc,
+ *                       byteps_topk_fold_desc: top-k sparsification with error
+ *                       feedback) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -733,6 +736,61 @@ typedef struct byteps_onebit_refold_desc {
 int byteps_reduce_onebit_refold_plan_create(const byteps_onebit_refold_desc* segs, int nsegs,
                                             int nsrc, byteps_reduce_onebit_plan** out);
 int byteps_reduce_onebit_refold_plan_launch(byteps_reduce_onebit_plan* plan, void* stream);
+
+/* Top-k sparsification with error feedback: the k values of
+ * largest magnitude travel with their indices, 8 k bytes for 4 n, and the rest
+ * stays in a residual.  For one tensor of n FLOAT32 elements g with its FLOAT32
+ * residual r and 1 <= k <= n, pinned to prophet_amd/topk.py byte for byte:
+ *
+ *   c_i   = g_i + r_i                  one IEEE f32 add
+ *   key_i = bits(c_i) & 0x7fffffff     orders |c|, NaN above inf, -0.0 == +0.0
+ *   T     = the k-th largest key
+ *   sel   = every i with key_i > T, and of those with key_i == T the first
+ *           (k - #{key > T}) in ascending i: exactly k elements
+ *   r'_i  = +0.0 if i in sel else c_i  replaces r_i
+ *
+ * The payload, little endian, 16-byte aligned, _payload_bytes(k) = 16 + 8 k:
+ * the header {u32 k, u32 n_lo, u32 n_hi, u32 0}, k u32 indices of sel, strictly
+ * ascending, then the k f32 values c_i in the same order.  n == 0 means k == 0
+ * and a bare header.
+ *
+ * Plans over many tensors are the only form.  _plan_compress is a fixed
+ * sequence of launches on `stream` with no host synchronisation; the plan owns
+ * its scratch, so one plan runs one compress at a time.
+ *
+ * The fold starts from +0.0 and adds nsrc payloads of the same n and k in
+ * argument order, out[idx] = out[idx] + val (one f32 add each), then divides by
+ * f32(divisor) when divisor > 1.  One launch.  Sizes come from the plan, never
+ * from a header: a malformed payload gives wrong values, but no write outside
+ * `out` and no read outside the payload's 16 + 8 k bytes.
+ *
+ * EARGS before any HIP call, every buffer untouched: a null pointer with nelem >
+ * 0, k outside 1..nelem (or nonzero with nelem == 0), nelem > 2^31, a payload
+ * that is not 16-byte aligned, nsrc outside 1..16, divisor < 1, any two byte
+ * ranges of a plan's operands overlapping (sources included), a fold launch on
+ * a compress plan or a compress on a fold plan.  _plan_destroy frees either. */
+typedef struct byteps_topk_desc {
+  const void* grad;
+  void* resid;
+  void* payload;
+  uint64_t nelem;
+  uint64_t k;
+} byteps_topk_desc;
+typedef struct byteps_topk_fold_desc {
+  void* out;
+  const void* const* payloads; /* nsrc of them; read by _fold_plan_create alone */
+  uint64_t nelem;
+  uint64_t k;
+} byteps_topk_fold_desc;
+typedef struct byteps_reduce_topk_plan byteps_reduce_topk_plan;
+uint64_t byteps_reduce_topk_payload_bytes(uint64_t k);
+int byteps_reduce_topk_plan_create(const byteps_topk_desc* segs, int nsegs,
+                                   byteps_reduce_topk_plan** out);
+int byteps_reduce_topk_plan_compress(byteps_reduce_topk_plan* plan, void* stream);
+int byteps_reduce_topk_fold_plan_create(const byteps_topk_fold_desc* segs, int nsegs, int nsrc,
+                                        byteps_reduce_topk_plan** out);
+int byteps_reduce_topk_fold_plan_launch(byteps_reduce_topk_plan* plan, int divisor, void* stream);
+int byteps_reduce_topk_plan_destroy(byteps_reduce_topk_plan* plan);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

@@ -130,6 +130,17 @@ uint8 buffer (``payload_like``); ``compress_many_ef_into`` is three launches
 per device, ``fold_many_into`` decodes up to 16 payloads per output and adds
 them in order in one.  The PS server cannot fold a packed payload, so
 ``Worker.init_tensor`` refuses this compressor.
+
+``Compression.topk_ef`` is the sparsifier beside it: a
+float32 tensor travels as the ``k`` values of largest ``|tensor + residual|``
+with their indices, ``16 + 8 k`` bytes, and the rest waits in the residual.
+``prophet_amd/topk.py`` is the definition, byte for byte: a radix select, a
+deterministic tie rule (the lowest indices win) and no floating-point
+reduction.  ``payload_like(tensor, ratio)`` sizes the payload, which carries
+its ``k`` in its size; ``compress_many_ef_into`` is one fixed sequence of
+launches per device, ``fold_many_into`` adds up to 16 sparse payloads per
+output in one.  There is no server round for it: ``Worker.init_tensor`` refuses
+this compressor over every front end.
 """
 from __future__ import annotations
 
@@ -345,10 +356,39 @@ class CastPlanCache:
             + tuple(int(p.data_ptr()) for p in ps) for ps, r, o in segs)
         return self._get(key, lambda: _new_onebit_refold_plan(segs, nsrc))
 
+    def get_topk(self, segs):
+        """The top-k compress plan (``GpuReducer.topk_plan``) over ``segs`` of
+        flat ``(grad, resid, payload)`` device tensors on the current device;
+        ``k`` is the payload's (``topk.k_of``), so another ratio misses."""
+        key = ("topk",) + tuple(
+            (int(g.data_ptr()), int(r.data_ptr()), int(p.data_ptr()), int(g.numel()),
+             int(p.numel())) for g, r, p in segs)
+        return self._get(key, lambda: _new_topk_plan(segs))
+
+    def get_topk_fold(self, segs, nsrc: int):
+        """The top-k fold plan (``GpuReducer.topk_fold_plan``) over ``segs`` of
+        ``(out, payloads)`` device tensors on the current device."""
+        key = ("topk_fold", int(nsrc)) + tuple(
+            (int(o.data_ptr()), int(o.numel()), int(ps[0].numel()))
+            + tuple(int(p.data_ptr()) for p in ps) for o, ps in segs)
+        return self._get(key, lambda: _new_topk_fold_plan(segs, nsrc))
+
     def close(self) -> None:
         while self._plans:
             _, plan = self._plans.popitem(last=False)
             plan.close()
+
+
+def _new_topk_plan(segs):
+    from .topk import k_of
+    from .torch_ops import _red
+    return _red().topk_plan([(g, r, p, int(g.numel()), k_of(p)) for g, r, p in segs])
+
+
+def _new_topk_fold_plan(segs, nsrc: int):
+    from .topk import k_of
+    from .torch_ops import _red
+    return _red().topk_fold_plan([(o, ps, int(o.numel()), k_of(ps[0])) for o, ps in segs], nsrc)
 
 
 def _new_onebit_plan(segs):
@@ -480,7 +520,8 @@ class Compressor:
 
     ERROR_FEEDBACK = False                # compress_ef_into and a residual per tensor
     STOCHASTIC = False                    # compress_sr_into under a key and a step
-    PACKED = False                        # the wire is no element-wise dtype (onebit_ef)
+    PACKED = False                        # the wire is no element-wise dtype (onebit_ef, topk_ef)
+    SERVER_ROUND = False                  # packed, and packed_round.PackedRound can fold it
 
     @staticmethod
     def compresses(tensor) -> bool:
@@ -1166,6 +1207,7 @@ class OneBitEFCompressor(Compressor):
 
     ERROR_FEEDBACK = True
     PACKED = True
+    SERVER_ROUND = True
 
     @classmethod
     def compresses(cls, tensor) -> bool:
@@ -1356,6 +1398,158 @@ class OneBitEFCompressor(Compressor):
                         cache.close()
 
 
+class TopKEFCompressor(Compressor):
+    """float32 tensors travel as their ``k`` values of largest magnitude with
+    their indices, with error feedback (``prophet_amd/topk.py`` is the
+    definition): ``16 + 8 k`` bytes for ``4 n``.  A payload is
+    a flat uint8 buffer (``payload_like(tensor, ratio)``), on the device 16-byte
+    aligned, and carries its ``k`` in its size.  Device tensors go through
+    top-k plans (``byteps_reduce_topk_*``, ``prophet_amd/csrc/bpsr_k_topk.hip``):
+    a compress of many tensors is one fixed sequence of launches per device, a
+    fold of many is one launch; CPU tensors and numpy arrays go through
+    ``topk.py``, byte for byte the same.  Everything but float32 passes
+    through.
+
+    The PS server cannot fold a sparse payload and there is no server round
+    for it yet: ``Worker.init_tensor`` refuses this compressor over every
+    front end.  ``fold_many_into`` is what a worker that gathered every
+    worker's payload computes."""
+
+    ERROR_FEEDBACK = True
+    PACKED = True
+
+    @classmethod
+    def compresses(cls, tensor) -> bool:
+        return _is_f32(tensor)
+
+    @classmethod
+    def payload_like(cls, x, ratio: float = 0.01):
+        """An uninitialised payload buffer for x at ``k = topk.k_for(n,
+        ratio)``, of x's kind and device."""
+        from .topk import k_for, payload_bytes
+        n = int(x.numel()) if _is_torch(x) else int(x.size)
+        size = payload_bytes(k_for(n, ratio) if n else 0)
+        if _is_torch(x):
+            import torch
+            return torch.empty(size, dtype=torch.uint8, device=x.device)
+        return np.empty(size, dtype=np.uint8)
+
+    residual_like = classmethod(_ErrorFeedback.residual_like.__func__)
+
+    @classmethod
+    def compress(cls, tensor, ratio: float = 0.01):
+        """The stateless form: one step from a zero residual, which is
+        dropped.  ``ctx`` is ``(dtype, shape)``."""
+        ctx = (tensor.dtype, tuple(tensor.shape))
+        if not cls.compresses(tensor):
+            return tensor, ctx
+        flat = tensor.contiguous() if _is_torch(tensor) else np.ascontiguousarray(tensor)
+        return cls.compress_ef_into(cls.payload_like(flat, ratio), cls.residual_like(flat),
+                                    flat), ctx
+
+    decompress = classmethod(OneBitEFCompressor.decompress.__func__)
+
+    @classmethod
+    def compress_ef_into(cls, payload, residual, tensor, plans: CastPlanCache | None = None):
+        """``payload, residual = topk.compress(tensor, residual,
+        topk.k_of(payload))``, the residual in place; returns ``payload``."""
+        cls.compress_many_ef_into([payload], [residual], [tensor], plans)
+        return payload
+
+    @classmethod
+    def compress_many_ef_into(cls, payloads, residuals, tensors,
+                              plans: CastPlanCache | None = None):
+        """``compress_ef_into`` for every i, the device tensors as one top-k
+        plan per device; returns ``payloads``."""
+        from . import topk
+        if len(payloads) != len(tensors) or len(residuals) != len(tensors):
+            raise ValueError("compress_many_ef_into: as many payloads and residuals as tensors")
+        groups: dict = {}
+        for i, (p, r, t) in enumerate(zip(payloads, residuals, tensors)):
+            if not cls.compresses(t) or not _is_f32(r):
+                raise ValueError("topk_ef needs float32 tensors and float32 residuals")
+            dev = [_on_device(x) for x in (p, r, t)]
+            if any(dev) != all(dev):
+                raise ValueError(f"topk_ef: tensor {i}'s operands live in one place, a device "
+                                 f"or the host")
+            if dev[0]:
+                cls._check_device_segment(i, t, r, payload=p)
+                groups.setdefault(t.device, []).append((t.reshape(-1), r.reshape(-1), p))
+                continue
+            ra = (r.detach().numpy() if _is_torch(r) else r).reshape(-1)
+            ga = t.detach().numpy() if _is_torch(t) else t
+            pa = _payload_array(p)
+            if ra.size != ga.size:
+                raise ValueError(f"topk_ef: tensor {i}'s operands differ in size")
+            pa[:], ra[:] = topk.compress(ga, ra, topk.k_of(pa))
+        OneBitEFCompressor._run(groups, plans, lambda cache, segs: cache.get_topk(segs),
+                                lambda plan, stream: plan.compress(stream=stream))
+        return payloads
+
+    @classmethod
+    def decompress_into(cls, out, payload, divisor: int = 1, plans: CastPlanCache | None = None):
+        """The one-source fold (``topk.fold([payload], n, divisor)``); returns
+        ``out``."""
+        cls.fold_many_into([out], [[payload]], divisor, plans)
+        return out
+
+    @classmethod
+    def fold_many_into(cls, outs, payload_lists, divisor: int = 1,
+                       plans: CastPlanCache | None = None):
+        """``outs[i] = topk.fold(payload_lists[i], outs[i].size, divisor)`` for
+        every i — every list of the same length N, 1..16, an output's payloads
+        of one size — the device tensors as one top-k fold plan per device (ONE
+        launch); returns ``outs``."""
+        from . import topk
+        if len(outs) != len(payload_lists):
+            raise ValueError("fold_many_into: as many payload lists as outputs")
+        if int(divisor) < 1:
+            raise ValueError(f"divisor {divisor} < 1")
+        nsrc = len(payload_lists[0]) if payload_lists else 1
+        if not 1 <= nsrc <= topk.MAX_SRCS or any(len(ps) != nsrc for ps in payload_lists):
+            raise ValueError(f"fold_many_into: every output takes the same 1..{topk.MAX_SRCS} "
+                             f"payloads")
+        groups: dict = {}
+        for i, (o, ps) in enumerate(zip(outs, payload_lists)):
+            if not _is_f32(o):
+                raise ValueError(f"topk_ef: output {i} must be float32, got {o.dtype}")
+            dev = [_on_device(x) for x in [o] + list(ps)]
+            if any(dev) != all(dev):
+                raise ValueError(f"topk_ef: output {i} and its payloads live in one place, a "
+                                 f"device or the host")
+            if len({topk.k_of(p) for p in ps}) != 1:
+                raise ValueError(f"topk_ef: output {i}'s payloads differ in size")
+            if dev[0]:
+                for p in ps:
+                    cls._check_device_segment(i, o, payload=p)
+                groups.setdefault(o.device, []).append((o.reshape(-1), list(ps)))
+                continue
+            oa = (o.detach().numpy() if _is_torch(o) else o).reshape(-1)
+            oa[:] = topk.fold([_payload_array(p) for p in ps], oa.size, divisor)
+        OneBitEFCompressor._run(groups, plans, lambda cache, segs: cache.get_topk_fold(segs, nsrc),
+                                lambda plan, stream: plan.launch(int(divisor), stream=stream))
+        return outs
+
+    @staticmethod
+    def _check_device_segment(i: int, tensor, resid=None, payload=None) -> None:
+        """One device segment: contiguous float32 operands of one size and a
+        flat uint8 payload of ``k`` entries, ``k`` in ``1..n``, all on one
+        device."""
+        import torch
+        from .topk import k_of
+        for x in (tensor, resid):
+            if x is not None and (not x.is_contiguous() or x.device != tensor.device
+                                  or x.numel() != tensor.numel()):
+                raise ValueError(f"topk_ef: tensor {i} needs contiguous operands of one size "
+                                 f"on one device")
+        n = int(tensor.numel())
+        if payload.dtype != torch.uint8 or not payload.is_contiguous() or payload.dim() != 1 \
+                or payload.device != tensor.device \
+                or not (1 <= k_of(payload) <= n or k_of(payload) == n == 0):
+            raise ValueError(f"topk_ef: tensor {i}'s payload must be a flat uint8 tensor of "
+                             f"16 + 8 k bytes, k in 1..{n}, on {tensor.device}")
+
+
 class Compression:
     """Optional gradient compression used during push_pull."""
 
@@ -1367,8 +1561,9 @@ class Compression:
     fp16_sr = FP16SRCompressor
     bf16_sr = BF16SRCompressor
     onebit_ef = OneBitEFCompressor
+    topk_ef = TopKEFCompressor
 
 
 __all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
            "FP16EFCompressor", "BF16EFCompressor", "FP16SRCompressor", "BF16SRCompressor",
-           "OneBitEFCompressor", "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]
+           "OneBitEFCompressor", "TopKEFCompressor", "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]

@@ -417,7 +417,9 @@ class Worker:
         if getattr(compression, "PACKED", False):
             # the server folds element-wise by dtype; a packed payload needs a
             # round type of its own, which the front end carries
-            if not getattr(self.frontend, "carries_packed", False):
+            # — for the compressors whose payloads PackedRound decodes
+            if not getattr(compression, "SERVER_ROUND", False) or \
+                    not getattr(self.frontend, "carries_packed", False):
                 raise ValueError(f"{name}: {compression.__name__} payloads do not travel through "
                                  f"push_pull yet; gather them and use fold_many_into")
             return self._init_packed(name, data, dtype, compression)

@@ -73,6 +73,9 @@ EXPORTS = (
     "byteps_reduce_onebit_plan_compress", "byteps_reduce_onebit_fold_plan_create",
     "byteps_reduce_onebit_fold_plan_launch", "byteps_reduce_onebit_plan_destroy",
     "byteps_reduce_onebit_refold_plan_create", "byteps_reduce_onebit_refold_plan_launch",
+    "byteps_reduce_topk_payload_bytes", "byteps_reduce_topk_plan_create",
+    "byteps_reduce_topk_plan_compress", "byteps_reduce_topk_fold_plan_create",
+    "byteps_reduce_topk_fold_plan_launch", "byteps_reduce_topk_plan_destroy",
 )
 
 
@@ -122,6 +125,18 @@ class OneBitRefoldDesc(ctypes.Structure):
     """``byteps_onebit_refold_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("payloads", ctypes.POINTER(_vp)), ("resid", _vp), ("out_payload", _vp),
                 ("nelem", ctypes.c_uint64)]
+
+
+class TopKDesc(ctypes.Structure):
+    """``byteps_topk_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("grad", _vp), ("resid", _vp), ("payload", _vp), ("nelem", ctypes.c_uint64),
+                ("k", ctypes.c_uint64)]
+
+
+class TopKFoldDesc(ctypes.Structure):
+    """``byteps_topk_fold_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64),
+                ("k", ctypes.c_uint64)]
 
 
 class SrKey(int):
@@ -222,6 +237,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_onebit_refold_plan_create.argtypes = [ctypes.POINTER(OneBitRefoldDesc), _int,
                                                           _int, ctypes.POINTER(_vp)]
     L.byteps_reduce_onebit_refold_plan_launch.argtypes = [_vp, _vp]
+    L.byteps_reduce_topk_payload_bytes.argtypes = [ctypes.c_uint64]
+    L.byteps_reduce_topk_payload_bytes.restype = ctypes.c_uint64
+    L.byteps_reduce_topk_plan_create.argtypes = [ctypes.POINTER(TopKDesc), _int,
+                                                 ctypes.POINTER(_vp)]
+    L.byteps_reduce_topk_plan_compress.argtypes = [_vp, _vp]
+    L.byteps_reduce_topk_fold_plan_create.argtypes = [ctypes.POINTER(TopKFoldDesc), _int, _int,
+                                                      ctypes.POINTER(_vp)]
+    L.byteps_reduce_topk_fold_plan_launch.argtypes = [_vp, _int, _vp]
+    L.byteps_reduce_topk_plan_destroy.argtypes = [_vp]
     _LIB = L
     return L
 
@@ -420,6 +444,22 @@ class GpuReducer:
         :meth:`OneBitFoldPlan.launch` is ONE launch: ``prophet_amd.onebit.fold``
         bit for bit; ``nsrc == 1`` is the plain decompress."""
         return OneBitFoldPlan(self.lib, segments, nsrc)
+
+    def topk_plan(self, segments: Sequence[tuple]) -> "TopKPlan":
+        """A top-k compress plan over many tensors
+        (byteps_reduce_topk_plan_create): ``segments`` are ``(grad, resid,
+        payload, nelem, k)`` — contiguous float32 gradients and residuals,
+        payloads of ``topk.payload_bytes(k)`` bytes, 16-byte aligned.
+        :meth:`TopKPlan.compress` is a fixed sequence of launches on one stream,
+        byte for byte ``prophet_amd.topk.compress``."""
+        return TopKPlan(self.lib, segments)
+
+    def topk_fold_plan(self, segments: Sequence[tuple], nsrc: int) -> "TopKFoldPlan":
+        """The N-way decode-and-sum (byteps_reduce_topk_fold_plan_create):
+        ``segments`` are ``(out, payloads, nelem, k)`` with ``nsrc`` (1..16)
+        payloads each, added in that order.  :meth:`TopKFoldPlan.launch` is ONE
+        launch: ``prophet_amd.topk.fold`` byte for byte."""
+        return TopKFoldPlan(self.lib, segments, nsrc)
 
     def onebit_refold_plan(self, segments: Sequence[tuple], nsrc: int) -> "OneBitRefoldPlan":
         """The server round of the 1-bit wire
@@ -931,6 +971,79 @@ class OneBitRefoldPlan(_OneBitPlanBase):
         """Refold-accumulate, finish, pack (byteps_reduce_onebit_refold_plan_launch)."""
         _check(self.lib.byteps_reduce_onebit_refold_plan_launch(self.handle,
                                                                 _stream_of(self.first, stream)))
+
+
+class _TopKPlanBase(_OneBitPlanBase):
+    """What the top-k plans share (the 1-bit plans' handle and held tensors)."""
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.byteps_reduce_topk_plan_destroy(self.handle)
+            self.handle = _vp()
+        self._keep = []
+
+
+class TopKPlan(_TopKPlanBase):
+    """A top-k compress plan (``byteps_reduce_topk_plan_create``).  Tensor
+    operands are bounds-checked before the library sees them."""
+
+    def __init__(self, lib, segments):
+        super().__init__(lib)
+        segments = [tuple(s) for s in segments]
+        for s in segments:
+            if len(s) != 5:
+                raise ValueError(f"topk plan: a segment of {len(s)} items")
+            if int(s[3]) < 0 or int(s[4]) < 0:
+                raise ValueError(f"negative count in ({s[3]}, {s[4]})")
+            _fits(int(s[3]) * 4, s[0], s[1])
+            _fits(16 + 8 * int(s[4]), s[2])
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (TopKDesc * max(1, len(segments)))()
+        for d, s in zip(descs, segments):
+            d.grad, d.resid, d.payload = _ptr(s[0]), _ptr(s[1]), _ptr(s[2])
+            d.nelem, d.k = int(s[3]), int(s[4])
+        _check(lib.byteps_reduce_topk_plan_create(descs, len(segments),
+                                                  ctypes.byref(self.handle)))
+
+    def compress(self, stream=None) -> None:
+        """The select and the compaction (byteps_reduce_topk_plan_compress)."""
+        _check(self.lib.byteps_reduce_topk_plan_compress(self.handle,
+                                                         _stream_of(self.first, stream)))
+
+
+class TopKFoldPlan(_TopKPlanBase):
+    """A top-k fold plan (``byteps_reduce_topk_fold_plan_create``)."""
+
+    def __init__(self, lib, segments, nsrc):
+        super().__init__(lib)
+        self.nsrc = int(nsrc)
+        segments = [(s[0], list(s[1]), int(s[2]), int(s[3])) for s in segments]
+        for out, payloads, nelem, k in segments:
+            if nelem < 0 or k < 0:
+                raise ValueError(f"negative count in ({nelem}, {k})")
+            if len(payloads) != self.nsrc:
+                raise ValueError(f"topk fold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
+            _fits(nelem * 4, out)
+            _fits(16 + 8 * k, *payloads)
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (TopKFoldDesc * max(1, len(segments)))()
+        rows = []                     # alive through the create call, which copies them
+        for d, (out, payloads, nelem, k) in zip(descs, segments):
+            row = (_vp * max(1, len(payloads)))(*[_ptr(p) for p in payloads])
+            rows.append(row)
+            d.out, d.payloads = _ptr(out), ctypes.cast(row, ctypes.POINTER(_vp))
+            d.nelem, d.k = nelem, k
+        _check(lib.byteps_reduce_topk_fold_plan_create(descs, len(segments), self.nsrc,
+                                                       ctypes.byref(self.handle)))
+
+    def launch(self, divisor: int = 1, stream=None) -> None:
+        """One launch (byteps_reduce_topk_fold_plan_launch)."""
+        _check(self.lib.byteps_reduce_topk_fold_plan_launch(self.handle, int(divisor),
+                                                            _stream_of(self.first, stream)))
 
 
 class BlockQueue:

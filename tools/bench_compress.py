@@ -240,7 +240,14 @@ def main() -> int:
                    help="the 1-bit server round: the refold plan (fold in registers, finish, "
                         "pack) against the fold plan into a scratch f32 buffer followed by the "
                         "compress plan, 8 sources; the ResNet-50 table and one segment")
+    p.add_argument("--topk", action="store_true",
+                   help="top-k sparsification: the radix-select compress against torch's add, "
+                        "topk(abs), gather and zero-scatter per tensor, and the 8-source fold "
+                        "against eight index_add_ into a zeroed tensor, at ratios 0.01 and "
+                        "0.001; the ResNet-50 table and one segment")
     args = p.parse_args()
+    if args.topk:
+        return topk_mode(args)
     if args.onebit_refold:
         return onebit_refold_mode(args)
     if args.onebit:
@@ -1437,6 +1444,168 @@ def onebit_mode(args) -> int:
     out["iteration"] = shape("table", [(o // 2, ln // 2) for o, ln in rows], total_bytes // 2)
     torch.cuda.empty_cache()
     out["big"] = shape("big", [(0, args.elems)], args.elems)
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    return 0 if all(gates.values()) and all(v for c in checks.values() for v in c.values()) else 1
+
+
+def topk_mode(args) -> int:
+    """Top-k sparsification, the --onebit protocol, at ratios
+    0.01 and 0.001.  The compress against torch's composition per tensor — add
+    into the residual, topk(abs), gather, zero-scatter — which leaves its
+    entries unsorted and so favours torch; the 8-source fold against eight
+    index_add_ per tensor into a zeroed tensor, on int64 indices converted
+    ahead of time, which favours torch again.  Before timing, ours is compared
+    with prophet_amd/topk.py byte for byte, and with torch by the sorted
+    magnitudes it selected (torch's tie order differs, the multiset does not)."""
+    import numpy as np
+    import torch
+
+    from prophet_amd import topk
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    NSRC = 8
+    out = {"tool": "bench_compress", "mode": "topk_ef compress and fold", "nsrc": NSRC,
+           "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+
+    def shape(label, ratio, seg_rows, arena_elems):
+        nelem = sum(n for _, n in seg_rows)
+        counts = [n for _, n in seg_rows]
+        kk = [topk.k_for(n, ratio) for n in counts]
+        cut = lambda t: [t[o:o + n] for o, n in seg_rows]      # noqa: E731
+        pay_off, at = [], 0
+        for k in kk:                             # 16-byte aligned payloads in one arena
+            pay_off.append(at)
+            at += (topk.payload_bytes(k) + 15) & ~15
+        pcut = lambda t: [t[o:o + topk.payload_bytes(k)]       # noqa: E731
+                          for o, k in zip(pay_off, kk)]
+
+        def entries(p, k):
+            return p[16:16 + 4 * k].view(torch.int32), p[16 + 4 * k:16 + 8 * k].view(torch.float32)
+
+        with step(f"setup, {label}", 300):
+            g = torch.Generator(device=dev).manual_seed(7)
+            sets = []
+            for _ in range(args.sets):
+                s = {"g": torch.randn(arena_elems, device=dev, generator=g),
+                     "r": torch.zeros(arena_elems, device=dev),
+                     "rt": torch.zeros(arena_elems, device=dev),
+                     "out": torch.empty(arena_elems, device=dev),
+                     "out_t": torch.empty(arena_elems, device=dev),
+                     "payc": torch.empty(at, dtype=torch.uint8, device=dev),
+                     "pay": [torch.empty(at, dtype=torch.uint8, device=dev) for _ in range(NSRC)]}
+                s["comp"] = red.topk_plan(list(zip(cut(s["g"]), cut(s["r"]), pcut(s["payc"]),
+                                                   counts, kk)))
+                # the fold's sources: the compress of NSRC different gradients
+                for j in range(NSRC):
+                    gj = torch.randn(arena_elems, device=dev, generator=g) * (j + 1)
+                    pl = red.topk_plan(list(zip(cut(gj), cut(s["rt"]), pcut(s["pay"][j]),
+                                                counts, kk)))
+                    pl.compress()
+                    pl.close()
+                    s["rt"].zero_()
+                s["fold"] = red.topk_fold_plan(
+                    [(o, [pcut(s["pay"][j])[i] for j in range(NSRC)], n, k)
+                     for i, (o, n, k) in enumerate(zip(cut(s["out"]), counts, kk))], NSRC)
+                s["idx"] = [[entries(p, k)[0].long() for p, k in zip(pcut(s["pay"][j]), kk)]
+                            for j in range(NSRC)]
+                s["val"] = [[entries(p, k)[1] for p, k in zip(pcut(s["pay"][j]), kk)]
+                            for j in range(NSRC)]
+                s["tv"] = [None] * len(kk)       # what torch's compress selected
+                sets.append(s)
+            torch.cuda.synchronize()
+
+        def compress(i):
+            sets[i]["comp"].compress()
+
+        def torch_compress(i):
+            s = sets[i]
+            for t, (gi, ri, k) in enumerate(zip(cut(s["g"]), cut(s["rt"]), kk)):
+                torch.add(gi, ri, out=ri)
+                idx = torch.topk(ri.abs(), k, sorted=False).indices
+                s["tv"][t] = ri[idx]
+                ri[idx] = 0.0
+
+        def fold(i):
+            sets[i]["fold"].launch(1)
+
+        def torch_fold(i):
+            s = sets[i]
+            s["out_t"].zero_()
+            for t, o in enumerate(cut(s["out_t"])):
+                for j in range(NSRC):
+                    o.index_add_(0, s["idx"][j][t], s["val"][j][t])
+
+        with step(f"check, {label}", 600):
+            s = sets[0]
+            torch_compress(0)
+            compress(0)
+            fold(0)
+            torch_fold(0)
+            torch.cuda.synchronize()
+            gh, rh, ph = s["g"].cpu().numpy(), s["r"].cpu().numpy(), s["payc"].cpu().numpy()
+            srch = [x.cpu().numpy() for x in s["pay"]]
+            oh = s["out"].cpu().numpy()
+            def_ok = fold_ok = torch_ok = True
+            for t, ((o, n), po, k) in enumerate(zip(seg_rows, pay_off, kk)):
+                nb = topk.payload_bytes(k)
+                pay, rn = topk.compress(gh[o:o + n], np.zeros(n, np.float32), k)
+                def_ok = def_ok and np.array_equal(ph[po:po + nb], pay) and \
+                    np.array_equal(rh[o:o + n].view(np.uint32), rn.view(np.uint32))
+                fold_ok = fold_ok and np.array_equal(
+                    oh[o:o + n].view(np.uint32),
+                    topk.fold([x[po:po + nb] for x in srch], n, 1, k).view(np.uint32))
+                ours = np.sort(np.abs(topk.entries(pay, k)[1]))
+                torch_ok = torch_ok and np.array_equal(
+                    ours, np.sort(np.abs(s["tv"][t].cpu().numpy())))
+            fold_t = all(bool(torch.equal(a, b)) for a, b in zip(cut(s["out"]), cut(s["out_t"])))
+            checks[label] = {"compress_equals_definition": bool(def_ok),
+                             "fold_equals_definition": bool(fold_ok),
+                             "compress_selects_torch_magnitudes": bool(torch_ok),
+                             "fold_equals_torch_index_add": fold_t}
+            s["r"].zero_()
+            s["rt"].zero_()
+        res = timed_rounds(torch, {"compress": (compress, args.inner),
+                                   "torch_compress": (torch_compress, args.inner),
+                                   "fold": (fold, args.inner),
+                                   "torch_fold": (torch_fold, args.inner)}, len(sets), args)
+        # bytes an element the design moves: ACCUMULATE 12, REFINE 4 + 4, COUNT 4,
+        # COMPACT 4 and per entry 8 of payload and at most 16 of r'; the fold 4
+        # and 8 an entry a source
+        kn = sum(kk) / nelem
+        for name, per in (("compress", 28 + 24 * kn), ("fold", 4 + 8 * NSRC * kn)):
+            res[name]["bytes_per_elem"] = round(per, 4)
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        for ours, theirs in (("compress", "torch_compress"), ("fold", "torch_fold")):
+            sp = max(res[ours]["spread_ms"], res[theirs]["spread_ms"])
+            gates[f"{label}_{ours}_beats_torch"] = res[theirs]["ms"] - res[ours]["ms"] > sp
+        for s in sets:
+            s["comp"].close()
+            s["fold"].close()
+        return {"segments": len(seg_rows), "elems": nelem, "k": sum(kk), "results": res}
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    total_bytes, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    for ratio in (0.01, 0.001):
+        out[f"iteration_{ratio}"] = shape(f"table_{ratio}", ratio,
+                                          [(o // 2, ln // 2) for o, ln in rows], total_bytes // 2)
+        torch.cuda.empty_cache()
+        out[f"big_{ratio}"] = shape(f"big_{ratio}", ratio, [(0, args.elems)], args.elems)
+        torch.cuda.empty_cache()
     out.update({"checks": checks, "gates": gates})
     line = json.dumps(out)
     print(line, flush=True)
