@@ -85,7 +85,9 @@ extern "C" {
  *                       1-bit wire)
  *    additive, still 5: byteps_reduce_topk_* (byteps_topk_desc,
  *                       byteps_topk_fold_desc: top-k sparsification with error
- *                       feedback) */
+ *                       feedback)
+ *    additive, still 5: byteps_reduce_mx_* (byteps_mx_desc, byteps_mx_fold_desc:
+ *                       block-scaled 8- and 4-bit wires with error feedback) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -791,6 +793,65 @@ int byteps_reduce_topk_fold_plan_create(const byteps_topk_fold_desc* segs, int n
                                         byteps_reduce_topk_plan** out);
 int byteps_reduce_topk_fold_plan_launch(byteps_reduce_topk_plan* plan, int divisor, void* stream);
 int byteps_reduce_topk_plan_destroy(byteps_reduce_topk_plan* plan);
+
+/* Block-scaled 8- and 4-bit wires with error feedback: every
+ * 32 consecutive elements share one power-of-two scale, an E8M0 byte, and travel
+ * as OCP e4m3 (bits == 8; emax 8, max 448) or OCP e2m1 (bits == 4; emax 2, max
+ * 6) codes, 8.25 or 4.25 bits an element.  For one tensor of n FLOAT32 elements
+ * g with its FLOAT32 residual r, pinned to prophet_amd/mx.py byte for byte,
+ * blocks by index in the tensor and the last one padded with +0.0:
+ *
+ *   c_i   = g_i + r_i                               one IEEE f32 add
+ *   E_b   = (max over the block of bits(c_i) & 0x7fffffff) >> 23
+ *   X_b   = 255 if E_b == 255 (an inf or a NaN), else max(E_b - emax, 0)
+ *   v_i   = clamp(c_i * 2^(127 - X_b), -max, +max)  one f32 multiply, then saturate
+ *   q_i   = v_i rounded to the format, nearest, ties to even, the sign kept
+ *   d_i   = f32(q_i) * 2^(X_b - 127)                one f32 multiply, exact
+ *   r'_i  = c_i - d_i                               replaces r_i
+ *
+ * A block with X_b == 255 carries codes of 0, decodes to the NaN 0x7fc00000 and
+ * leaves that NaN in r'.
+ *
+ * The payload, little endian, 16-byte aligned, _payload_bytes(n, bits) = 16 +
+ * align16(ceil(n / 32)) + align16(ceil(n bits / 8)): the header {u32 bits, u32
+ * n_lo, u32 n_hi, u32 0}, the scale bytes X_b, the codes q_i (bits == 4: element
+ * 2 j in the low nibble), both fields padded with zeros.  n == 0 is a bare
+ * header.  _payload_bytes is 0 for other bits or n > 2^31.
+ *
+ * Plans over many tensors are the only form, all segments of one format.
+ * _plan_compress is ONE launch on `stream` with no scratch memory and no host
+ * synchronisation.  The fold decodes nsrc payloads of the same n and adds them
+ * in argument order (d_0 + d_1 + ...), then divides by f32(divisor) when divisor
+ * > 1.  ONE launch.  Sizes come from the plan, never from a header: a malformed
+ * payload gives wrong values, but no write outside `out` and no read outside the
+ * payload's bytes.
+ *
+ * EARGS before any HIP call, every buffer untouched: a null pointer with nelem >
+ * 0, bits other than 8 or 4, nelem > 2^31, a gradient, residual or output that
+ * is not 4-byte aligned, a payload that is not 16-byte aligned, nsrc outside
+ * 1..16, divisor < 1, any two byte ranges of a plan's operands overlapping
+ * (sources included), a fold launch on a compress plan or a compress on a fold
+ * plan.  _plan_destroy frees either. */
+typedef struct byteps_mx_desc {
+  const void* grad;
+  void* resid;
+  void* payload;
+  uint64_t nelem;
+} byteps_mx_desc;
+typedef struct byteps_mx_fold_desc {
+  void* out;
+  const void* const* payloads; /* nsrc of them; read by _fold_plan_create alone */
+  uint64_t nelem;
+} byteps_mx_fold_desc;
+typedef struct byteps_reduce_mx_plan byteps_reduce_mx_plan;
+uint64_t byteps_reduce_mx_payload_bytes(uint64_t nelem, int bits);
+int byteps_reduce_mx_plan_create(const byteps_mx_desc* segs, int nsegs, int bits,
+                                 byteps_reduce_mx_plan** out);
+int byteps_reduce_mx_plan_compress(byteps_reduce_mx_plan* plan, void* stream);
+int byteps_reduce_mx_fold_plan_create(const byteps_mx_fold_desc* segs, int nsegs, int nsrc,
+                                      int bits, byteps_reduce_mx_plan** out);
+int byteps_reduce_mx_fold_plan_launch(byteps_reduce_mx_plan* plan, int divisor, void* stream);
+int byteps_reduce_mx_plan_destroy(byteps_reduce_mx_plan* plan);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

@@ -141,6 +141,16 @@ its ``k`` in its size; ``compress_many_ef_into`` is one fixed sequence of
 launches per device, ``fold_many_into`` adds up to 16 sparse payloads per
 output in one.  There is no server round for it: ``Worker.init_tensor`` refuses
 this compressor over every front end.
+
+``Compression.mxfp8_ef`` and ``Compression.mxfp4_ef`` sit between the 2-byte
+wires and those two: every 32 consecutive elements share one
+power-of-two scale byte and travel as OCP e4m3 or e2m1 codes, 8.25 or 4.25 bits
+an element, the rounding and saturation error waiting in the residual.
+``prophet_amd/mx.py`` is the definition, byte for byte: an integer block
+maximum, round to nearest even, no floating-point reduction.
+``compress_many_ef_into`` is ONE launch per device, ``fold_many_into`` decodes
+up to 16 payloads per output and adds them in order in one.  There is no server
+round for them yet: ``Worker.init_tensor`` refuses both over every front end.
 """
 from __future__ import annotations
 
@@ -373,10 +383,36 @@ class CastPlanCache:
             + tuple(int(p.data_ptr()) for p in ps) for o, ps in segs)
         return self._get(key, lambda: _new_topk_fold_plan(segs, nsrc))
 
+    def get_mx(self, segs, fmt: str):
+        """The block-scaled compress plan (``GpuReducer.mx_plan``) over ``segs``
+        of flat ``(grad, resid, payload)`` device tensors on the current device."""
+        key = ("mx", fmt) + tuple(
+            (int(g.data_ptr()), int(r.data_ptr()), int(p.data_ptr()), int(g.numel()))
+            for g, r, p in segs)
+        return self._get(key, lambda: _new_mx_plan(segs, fmt))
+
+    def get_mx_fold(self, segs, nsrc: int, fmt: str):
+        """The block-scaled fold plan (``GpuReducer.mx_fold_plan``) over ``segs``
+        of ``(out, payloads)`` device tensors on the current device."""
+        key = ("mx_fold", fmt, int(nsrc)) + tuple(
+            (int(o.data_ptr()), int(o.numel())) + tuple(int(p.data_ptr()) for p in ps)
+            for o, ps in segs)
+        return self._get(key, lambda: _new_mx_fold_plan(segs, nsrc, fmt))
+
     def close(self) -> None:
         while self._plans:
             _, plan = self._plans.popitem(last=False)
             plan.close()
+
+
+def _new_mx_plan(segs, fmt: str):
+    from .torch_ops import _red
+    return _red().mx_plan([(g, r, p, int(g.numel())) for g, r, p in segs], fmt)
+
+
+def _new_mx_fold_plan(segs, nsrc: int, fmt: str):
+    from .torch_ops import _red
+    return _red().mx_fold_plan([(o, ps, int(o.numel())) for o, ps in segs], nsrc, fmt)
 
 
 def _new_topk_plan(segs):
@@ -520,7 +556,7 @@ class Compressor:
 
     ERROR_FEEDBACK = False                # compress_ef_into and a residual per tensor
     STOCHASTIC = False                    # compress_sr_into under a key and a step
-    PACKED = False                        # the wire is no element-wise dtype (onebit_ef, topk_ef)
+    PACKED = False                        # the wire is no element-wise dtype (onebit_ef, topk_ef, mx*_ef)
     SERVER_ROUND = False                  # packed, and packed_round.PackedRound can fold it
 
     @staticmethod
@@ -1550,6 +1586,158 @@ class TopKEFCompressor(Compressor):
                              f"16 + 8 k bytes, k in 1..{n}, on {tensor.device}")
 
 
+class MXFP8EFCompressor(Compressor):
+    """float32 tensors travel in blocks of 32 elements, one power-of-two scale
+    byte and 32 OCP e4m3 codes each, with error feedback (``prophet_amd/mx.py``
+    is the definition): 8.25 bits an element.
+    ``MXFP4EFCompressor`` is the same body over OCP e2m1 codes, 4.25 bits.  A
+    payload is a flat uint8 buffer (``payload_like``), on the device 16-byte
+    aligned.  Device tensors go through block-scaled plans
+    (``byteps_reduce_mx_*``, ``prophet_amd/csrc/bpsr_k_mx.hip``): a compress of
+    many tensors is ONE launch per device, and so is a fold of many; CPU
+    tensors and numpy arrays go through ``mx.py``, byte for byte the same.
+    Everything but float32 passes through.
+
+    There is no server round for these wires yet: ``Worker.init_tensor``
+    refuses them over every front end.  ``fold_many_into`` is what a worker
+    that gathered every worker's payload computes."""
+
+    ERROR_FEEDBACK = True
+    PACKED = True
+    FMT = "fp8"
+
+    @classmethod
+    def compresses(cls, tensor) -> bool:
+        return _is_f32(tensor)
+
+    @classmethod
+    def payload_like(cls, x):
+        """An uninitialised payload buffer for x, of x's kind and device."""
+        from .mx import payload_bytes
+        size = payload_bytes(int(x.numel()) if _is_torch(x) else int(x.size), cls.FMT)
+        if _is_torch(x):
+            import torch
+            return torch.empty(size, dtype=torch.uint8, device=x.device)
+        return np.empty(size, dtype=np.uint8)
+
+    residual_like = classmethod(_ErrorFeedback.residual_like.__func__)
+
+    @classmethod
+    def compress(cls, tensor):
+        """The stateless form: one step from a zero residual, which is
+        dropped.  ``ctx`` is ``(dtype, shape)``."""
+        ctx = (tensor.dtype, tuple(tensor.shape))
+        if not cls.compresses(tensor):
+            return tensor, ctx
+        flat = tensor.contiguous() if _is_torch(tensor) else np.ascontiguousarray(tensor)
+        return cls.compress_ef_into(cls.payload_like(flat), cls.residual_like(flat), flat), ctx
+
+    decompress = classmethod(OneBitEFCompressor.decompress.__func__)
+
+    @classmethod
+    def compress_ef_into(cls, payload, residual, tensor, plans: CastPlanCache | None = None):
+        """``payload, residual = mx.compress(tensor, residual, FMT)``, the
+        residual in place; returns ``payload``."""
+        cls.compress_many_ef_into([payload], [residual], [tensor], plans)
+        return payload
+
+    @classmethod
+    def compress_many_ef_into(cls, payloads, residuals, tensors,
+                              plans: CastPlanCache | None = None):
+        """``compress_ef_into`` for every i, the device tensors as one
+        block-scaled plan per device (ONE launch); returns ``payloads``."""
+        from . import mx
+        if len(payloads) != len(tensors) or len(residuals) != len(tensors):
+            raise ValueError("compress_many_ef_into: as many payloads and residuals as tensors")
+        name, groups = f"mx{cls.FMT}_ef", {}
+        for i, (p, r, t) in enumerate(zip(payloads, residuals, tensors)):
+            if not cls.compresses(t) or not _is_f32(r):
+                raise ValueError(f"{name} needs float32 tensors and float32 residuals")
+            dev = [_on_device(x) for x in (p, r, t)]
+            if any(dev) != all(dev):
+                raise ValueError(f"{name}: tensor {i}'s operands live in one place, a device "
+                                 f"or the host")
+            if dev[0]:
+                cls._check_device_segment(i, t, r, payload=p)
+                groups.setdefault(t.device, []).append((t.reshape(-1), r.reshape(-1), p))
+                continue
+            ra = (r.detach().numpy() if _is_torch(r) else r).reshape(-1)
+            ga = t.detach().numpy() if _is_torch(t) else t
+            pa = _payload_array(p)
+            if ra.size != ga.size or pa.size != mx.payload_bytes(ga.size, cls.FMT):
+                raise ValueError(f"{name}: tensor {i}'s operands differ in size")
+            pa[:], ra[:] = mx.compress(ga, ra, cls.FMT)
+        OneBitEFCompressor._run(groups, plans, lambda cache, segs: cache.get_mx(segs, cls.FMT),
+                                lambda plan, stream: plan.compress(stream=stream))
+        return payloads
+
+    @classmethod
+    def decompress_into(cls, out, payload, divisor: int = 1, plans: CastPlanCache | None = None):
+        """``out = mx.decode(payload)`` (divided by ``divisor`` above 1): the
+        one-source fold; returns ``out``."""
+        cls.fold_many_into([out], [[payload]], divisor, plans)
+        return out
+
+    @classmethod
+    def fold_many_into(cls, outs, payload_lists, divisor: int = 1,
+                       plans: CastPlanCache | None = None):
+        """``outs[i] = mx.fold(payload_lists[i], outs[i].size, FMT, divisor)``
+        for every i — every list of the same length N, 1..16 — the device
+        tensors as one block-scaled fold plan per device (ONE launch); returns
+        ``outs``."""
+        from . import mx
+        if len(outs) != len(payload_lists):
+            raise ValueError("fold_many_into: as many payload lists as outputs")
+        if int(divisor) < 1:
+            raise ValueError(f"divisor {divisor} < 1")
+        nsrc = len(payload_lists[0]) if payload_lists else 1
+        if not 1 <= nsrc <= mx.MAX_SRCS or any(len(ps) != nsrc for ps in payload_lists):
+            raise ValueError(f"fold_many_into: every output takes the same 1..{mx.MAX_SRCS} "
+                             f"payloads")
+        name, groups = f"mx{cls.FMT}_ef", {}
+        for i, (o, ps) in enumerate(zip(outs, payload_lists)):
+            if not _is_f32(o):
+                raise ValueError(f"{name}: output {i} must be float32, got {o.dtype}")
+            dev = [_on_device(x) for x in [o] + list(ps)]
+            if any(dev) != all(dev):
+                raise ValueError(f"{name}: output {i} and its payloads live in one place, a "
+                                 f"device or the host")
+            if dev[0]:
+                for p in ps:
+                    cls._check_device_segment(i, o, payload=p)
+                groups.setdefault(o.device, []).append((o.reshape(-1), list(ps)))
+                continue
+            oa = (o.detach().numpy() if _is_torch(o) else o).reshape(-1)
+            oa[:] = mx.fold([_payload_array(p) for p in ps], oa.size, cls.FMT, divisor)
+        OneBitEFCompressor._run(groups, plans,
+                                lambda cache, segs: cache.get_mx_fold(segs, nsrc, cls.FMT),
+                                lambda plan, stream: plan.launch(int(divisor), stream=stream))
+        return outs
+
+    @classmethod
+    def _check_device_segment(cls, i: int, tensor, resid=None, payload=None) -> None:
+        """One device segment: contiguous float32 operands of one size and a
+        flat uint8 payload of the payload's size, all on one device."""
+        import torch
+        from .mx import payload_bytes
+        for x in (tensor, resid):
+            if x is not None and (not x.is_contiguous() or x.device != tensor.device
+                                  or x.numel() != tensor.numel()):
+                raise ValueError(f"mx{cls.FMT}_ef: tensor {i} needs contiguous operands of one "
+                                 f"size on one device")
+        size = payload_bytes(tensor.numel(), cls.FMT)
+        if payload.dtype != torch.uint8 or not payload.is_contiguous() or payload.dim() != 1 \
+                or payload.device != tensor.device or payload.numel() != size:
+            raise ValueError(f"mx{cls.FMT}_ef: tensor {i}'s payload must be a flat uint8 tensor "
+                             f"of {size} bytes on {tensor.device}")
+
+
+class MXFP4EFCompressor(MXFP8EFCompressor):
+    """``MXFP8EFCompressor`` over OCP e2m1 codes: 4.25 bits an element."""
+
+    FMT = "fp4"
+
+
 class Compression:
     """Optional gradient compression used during push_pull."""
 
@@ -1562,8 +1750,11 @@ class Compression:
     bf16_sr = BF16SRCompressor
     onebit_ef = OneBitEFCompressor
     topk_ef = TopKEFCompressor
+    mxfp8_ef = MXFP8EFCompressor
+    mxfp4_ef = MXFP4EFCompressor
 
 
 __all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
            "FP16EFCompressor", "BF16EFCompressor", "FP16SRCompressor", "BF16SRCompressor",
-           "OneBitEFCompressor", "TopKEFCompressor", "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]
+           "OneBitEFCompressor", "TopKEFCompressor", "MXFP8EFCompressor", "MXFP4EFCompressor",
+           "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]

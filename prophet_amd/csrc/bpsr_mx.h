@@ -1,0 +1,84 @@
+// Block-scaled 8- and 4-bit wires with error feedback (byteps_reduce_mx_*,
+// DESIGN.md §11.13; the definition is prophet_amd/mx.py).  What the host side
+// (bpsr_mx.cpp: operand checks, tables, the C entry points) and the kernels
+// (bpsr_k_mx.hip) share: the payload's layout, the tables' records and the
+// launches.
+//
+// A payload is a 16-byte header {u32 bits, u32 n_lo, u32 n_hi, u32 0}, one E8M0
+// scale byte a block of 32 elements, padded with zeros to 16 bytes, and the
+// element codes — OCP e4m3 bytes or OCP e2m1 nibbles, element 2 j in the low
+// one — padded with zeros to 16 bytes.
+//
+// A compress is one launch over a table of tiles, a fold is one launch over a
+// table of output tiles; neither has scratch memory.
+#pragma once
+
+#include "bpsr_internal.h"
+
+namespace bpsr {
+
+constexpr uint64_t kMxHeader = 16;
+constexpr uint32_t kMxBlock = 32;
+// A tile: kBlock lanes x 4 b128 vectors, 4,096 elements a workgroup; vector
+// j * kBlock + lane is lane's j-th, so a block is eight adjacent lanes of one j
+// and a tile holds 128 blocks.  Tiles start on multiples of the tile in their
+// segment: on block boundaries, and 16-byte aligned in the scales and the codes.
+constexpr uint32_t kMxTile = kBlock * 16;
+constexpr uint32_t kMxTileBlocks = kMxTile / kMxBlock;
+constexpr int kMxMaxSrcs = 16;
+constexpr uint64_t kMxMaxElems = 1ull << 31;
+
+constexpr uint64_t mx_align16(uint64_t x) { return (x + 15) & ~15ull; }
+constexpr uint64_t mx_scale_bytes(uint64_t n) { return (n + kMxBlock - 1) / kMxBlock; }
+constexpr uint64_t mx_code_bytes(uint64_t n, uint32_t bits) { return (n * bits + 7) / 8; }
+// where the codes begin in a payload of n elements
+constexpr uint64_t mx_codes_at(uint64_t n) { return kMxHeader + mx_align16(mx_scale_bytes(n)); }
+constexpr uint64_t mx_payload_bytes(uint64_t n, uint32_t bits) {
+  return mx_codes_at(n) + mx_align16(mx_code_bytes(n, bits));
+}
+
+// One tile of a compress or of a fold: both pointers already advanced to the
+// tile's first element.  A compress of an empty segment that names a payload
+// is one record of count 0: it writes the header.
+enum : uint32_t { kMxVec = 1, kMxAligned = 2 };
+struct MxRec {
+  unsigned char* a;  // compress: the gradient; fold: the output
+  unsigned char* b;  // compress: the residual; fold: null
+  uint32_t seg;      // the segment (MxSeg)
+  uint32_t e0;       // the tile's first element in its segment
+  uint32_t count;    // elements, 0..kMxTile
+  uint32_t flags;    // kMxVec: a and b 16-byte aligned; kMxAligned: 4-byte aligned
+};
+static_assert(sizeof(MxRec) == 32, "MxRec layout");
+
+// One segment: compress — its payload; fold — `payload` unused, its sources
+// are row `seg` of MxFold::srcs.
+struct MxSeg {
+  unsigned char* payload;
+  uint64_t nelem;
+};
+static_assert(sizeof(MxSeg) == 16, "MxSeg layout");
+
+struct MxCompress {
+  const MxRec* recs;
+  const MxSeg* segs;
+  uint32_t nrecs;
+};
+
+struct MxFold {
+  const MxRec* recs;
+  const MxSeg* segs;
+  const unsigned char* const* srcs;  // [nsegs * nsrc] payloads, a segment's row in argument order
+  uint32_t nrecs;
+  int nsrc;
+  int divisor;
+};
+
+// `bits`: 8 or 4.  `resid_bytes` / `out_bytes`: what the launch writes in f32
+// (store policy).
+hipError_t launch_mx_compress(const MxCompress& p, uint32_t bits, uint64_t resid_bytes,
+                              const Tuning& tu, hipStream_t s);
+hipError_t launch_mx_fold(const MxFold& p, uint32_t bits, uint64_t out_bytes, const Tuning& tu,
+                          hipStream_t s);
+
+}  // namespace bpsr

@@ -76,6 +76,9 @@ EXPORTS = (
     "byteps_reduce_topk_payload_bytes", "byteps_reduce_topk_plan_create",
     "byteps_reduce_topk_plan_compress", "byteps_reduce_topk_fold_plan_create",
     "byteps_reduce_topk_fold_plan_launch", "byteps_reduce_topk_plan_destroy",
+    "byteps_reduce_mx_payload_bytes", "byteps_reduce_mx_plan_create",
+    "byteps_reduce_mx_plan_compress", "byteps_reduce_mx_fold_plan_create",
+    "byteps_reduce_mx_fold_plan_launch", "byteps_reduce_mx_plan_destroy",
 )
 
 
@@ -137,6 +140,16 @@ class TopKFoldDesc(ctypes.Structure):
     """``byteps_topk_fold_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64),
                 ("k", ctypes.c_uint64)]
+
+
+class MXDesc(ctypes.Structure):
+    """``byteps_mx_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("grad", _vp), ("resid", _vp), ("payload", _vp), ("nelem", ctypes.c_uint64)]
+
+
+class MXFoldDesc(ctypes.Structure):
+    """``byteps_mx_fold_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64)]
 
 
 class SrKey(int):
@@ -246,6 +259,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                       ctypes.POINTER(_vp)]
     L.byteps_reduce_topk_fold_plan_launch.argtypes = [_vp, _int, _vp]
     L.byteps_reduce_topk_plan_destroy.argtypes = [_vp]
+    L.byteps_reduce_mx_payload_bytes.argtypes = [ctypes.c_uint64, _int]
+    L.byteps_reduce_mx_payload_bytes.restype = ctypes.c_uint64
+    L.byteps_reduce_mx_plan_create.argtypes = [ctypes.POINTER(MXDesc), _int, _int,
+                                               ctypes.POINTER(_vp)]
+    L.byteps_reduce_mx_plan_compress.argtypes = [_vp, _vp]
+    L.byteps_reduce_mx_fold_plan_create.argtypes = [ctypes.POINTER(MXFoldDesc), _int, _int, _int,
+                                                    ctypes.POINTER(_vp)]
+    L.byteps_reduce_mx_fold_plan_launch.argtypes = [_vp, _int, _vp]
+    L.byteps_reduce_mx_plan_destroy.argtypes = [_vp]
     _LIB = L
     return L
 
@@ -460,6 +482,23 @@ class GpuReducer:
         payloads each, added in that order.  :meth:`TopKFoldPlan.launch` is ONE
         launch: ``prophet_amd.topk.fold`` byte for byte."""
         return TopKFoldPlan(self.lib, segments, nsrc)
+
+    def mx_plan(self, segments: Sequence[tuple], fmt: str) -> "MXPlan":
+        """The block-scaled compress of a whole iteration
+        (byteps_reduce_mx_plan_create): ``segments`` are ``(grad, resid,
+        payload, nelem)`` — float32 tensors of ``nelem`` elements and uint8
+        payloads of ``mx.payload_bytes(nelem, fmt)`` bytes, 16-byte aligned —
+        all of the format ``fmt`` (``"fp8"`` or ``"fp4"``).
+        :meth:`MXPlan.compress` is ONE launch, byte for byte
+        ``prophet_amd.mx.compress``."""
+        return MXPlan(self.lib, segments, fmt)
+
+    def mx_fold_plan(self, segments: Sequence[tuple], nsrc: int, fmt: str) -> "MXFoldPlan":
+        """The N-way decode-and-sum (byteps_reduce_mx_fold_plan_create):
+        ``segments`` are ``(out, payloads, nelem)`` with ``nsrc`` (1..16)
+        payloads each, added in that order.  :meth:`MXFoldPlan.launch` is ONE
+        launch: ``prophet_amd.mx.fold`` byte for byte."""
+        return MXFoldPlan(self.lib, segments, nsrc, fmt)
 
     def onebit_refold_plan(self, segments: Sequence[tuple], nsrc: int) -> "OneBitRefoldPlan":
         """The server round of the 1-bit wire
@@ -1044,6 +1083,85 @@ class TopKFoldPlan(_TopKPlanBase):
         """One launch (byteps_reduce_topk_fold_plan_launch)."""
         _check(self.lib.byteps_reduce_topk_fold_plan_launch(self.handle, int(divisor),
                                                             _stream_of(self.first, stream)))
+
+
+class _MXPlanBase(_OneBitPlanBase):
+    """What the block-scaled plans share (the 1-bit plans' handle and held
+    tensors) and the format's element bits."""
+
+    def __init__(self, lib, fmt):
+        from .mx import bits_of
+        super().__init__(lib)
+        self.fmt, self.bits = fmt, bits_of(fmt)
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.byteps_reduce_mx_plan_destroy(self.handle)
+            self.handle = _vp()
+        self._keep = []
+
+
+class MXPlan(_MXPlanBase):
+    """A block-scaled compress plan (``byteps_reduce_mx_plan_create``).  Tensor
+    operands are bounds-checked before the library sees them."""
+
+    def __init__(self, lib, segments, fmt):
+        from .mx import payload_bytes
+        super().__init__(lib, fmt)
+        segments = [tuple(s) for s in segments]
+        for s in segments:
+            if len(s) != 4:
+                raise ValueError(f"mx plan: a segment of {len(s)} items")
+            if int(s[3]) < 0:
+                raise ValueError(f"negative element count {s[3]}")
+            _fits(int(s[3]) * 4, s[0], s[1])
+            _fits(payload_bytes(s[3], fmt), s[2])
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (MXDesc * max(1, len(segments)))()
+        for d, s in zip(descs, segments):
+            d.grad, d.resid, d.payload, d.nelem = _ptr(s[0]), _ptr(s[1]), _ptr(s[2]), int(s[3])
+        _check(lib.byteps_reduce_mx_plan_create(descs, len(segments), self.bits,
+                                                ctypes.byref(self.handle)))
+
+    def compress(self, stream=None) -> None:
+        """One launch (byteps_reduce_mx_plan_compress)."""
+        _check(self.lib.byteps_reduce_mx_plan_compress(self.handle,
+                                                       _stream_of(self.first, stream)))
+
+
+class MXFoldPlan(_MXPlanBase):
+    """A block-scaled fold plan (``byteps_reduce_mx_fold_plan_create``)."""
+
+    def __init__(self, lib, segments, nsrc, fmt):
+        from .mx import payload_bytes
+        super().__init__(lib, fmt)
+        self.nsrc = int(nsrc)
+        segments = [(s[0], list(s[1]), int(s[2])) for s in segments]
+        for out, payloads, nelem in segments:
+            if nelem < 0:
+                raise ValueError(f"negative element count {nelem}")
+            if len(payloads) != self.nsrc:
+                raise ValueError(f"mx fold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
+            _fits(nelem * 4, out)
+            _fits(payload_bytes(nelem, fmt), *payloads)
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (MXFoldDesc * max(1, len(segments)))()
+        rows = []                     # alive through the create call, which copies them
+        for d, (out, payloads, nelem) in zip(descs, segments):
+            row = (_vp * max(1, len(payloads)))(*[_ptr(p) for p in payloads])
+            rows.append(row)
+            d.out, d.payloads, d.nelem = _ptr(out), ctypes.cast(row, ctypes.POINTER(_vp)), nelem
+        _check(lib.byteps_reduce_mx_fold_plan_create(descs, len(segments), self.nsrc, self.bits,
+                                                     ctypes.byref(self.handle)))
+
+    def launch(self, divisor: int = 1, stream=None) -> None:
+        """One launch (byteps_reduce_mx_fold_plan_launch)."""
+        _check(self.lib.byteps_reduce_mx_fold_plan_launch(self.handle, int(divisor),
+                                                          _stream_of(self.first, stream)))
 
 
 class BlockQueue:
