@@ -87,7 +87,9 @@ extern "C" {
  *                       byteps_topk_fold_desc: top-k sparsification with error
  *                       feedback)
  *    additive, still 5: byteps_reduce_mx_* (byteps_mx_desc, byteps_mx_fold_desc:
- *                       block-scaled 8- and 4-bit wires with error feedback) */
+ *                       block-scaled 8- and 4-bit wires with error feedback)
+ *    additive, still 5: byteps_reduce_powersgd_* (byteps_powersgd_desc: PowerSGD
+ *                       low-rank compression with error feedback) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -852,6 +854,57 @@ int byteps_reduce_mx_fold_plan_create(const byteps_mx_fold_desc* segs, int nsegs
                                       int bits, byteps_reduce_mx_plan** out);
 int byteps_reduce_mx_fold_plan_launch(byteps_reduce_mx_plan* plan, int divisor, void* stream);
 int byteps_reduce_mx_plan_destroy(byteps_reduce_mx_plan* plan);
+
+/* PowerSGD low-rank compression with error feedback (the
+ * definition is prophet_amd/powersgd.py).  A segment is one row-major n x m
+ * FLOAT32 matrix with the plan's rank r, 1..16: `grad`, `resid` (R) and `out`
+ * are n x m, `p` is n x r, `q` and `qn` are m x r, all row-major FLOAT32.  One
+ * iteration is four phases, the caller averaging P after the first and Qn after
+ * the third (they are plain FLOAT32 tensors: any fold of this header sums them):
+ *
+ *   _project_p      R = grad + R (one IEEE f32 add; R now holds M); P = M Q
+ *   _orthogonalize  modified Gram-Schmidt over P's columns 0..r-1 in place,
+ *                   sums in float64; a column whose squared norm is 0 or not
+ *                   finite becomes zeros
+ *   _project_q      Qn = M^T P
+ *   _finish         a = 0; a = a + P[:, k] Qn[:, k] for k = 0..r-1, a multiply
+ *                   and an add in f32 each; out = a; R = R - a where both are
+ *                   finite, else +0.0
+ *
+ * The bytes R holds after _project_p and everything _finish writes are pinned to
+ * the definition.  The two contractions are NOT: they run on f32 matrix
+ * instructions in the kernels' own order, per-chunk partial tiles added in
+ * chunk order, and are held to the error bound of an f32 dot product.  No
+ * atomics anywhere: a phase on the same bytes writes the same bytes.
+ *
+ * Each phase is a fixed sequence of launches on `stream` (two, one, two, one)
+ * with no host synchronisation.  The partial tiles live in scratch memory the
+ * plan allocates and owns, _scratch_bytes(n, m, rank) for a segment (0 for a
+ * shape or rank the plan would refuse).  `out` may be `grad` itself.  A plan has
+ * ONE rank, every segment's: tensors at different ranks take a plan each.
+ *
+ * EARGS before any HIP call, every buffer untouched: a null pointer, rank
+ * outside 1..16, n or m of 0 or above 2^24, more than 2^33 elements, more than
+ * 65535 segments, an operand that is not 16-byte aligned, any two byte ranges
+ * of a plan's operands overlapping (except out == grad), a null plan. */
+typedef struct byteps_powersgd_desc {
+  const void* grad;
+  void* resid;
+  void* p;
+  const void* q; /* the warm start: read by _project_p */
+  void* qn;      /* written by _project_q, read by _finish */
+  void* out;
+  uint64_t n, m;
+} byteps_powersgd_desc;
+typedef struct byteps_reduce_powersgd_plan byteps_reduce_powersgd_plan;
+uint64_t byteps_reduce_powersgd_scratch_bytes(uint64_t n, uint64_t m, int rank);
+int byteps_reduce_powersgd_plan_create(const byteps_powersgd_desc* segs, int nsegs, int rank,
+                                       byteps_reduce_powersgd_plan** out);
+int byteps_reduce_powersgd_plan_project_p(byteps_reduce_powersgd_plan* plan, void* stream);
+int byteps_reduce_powersgd_plan_orthogonalize(byteps_reduce_powersgd_plan* plan, void* stream);
+int byteps_reduce_powersgd_plan_project_q(byteps_reduce_powersgd_plan* plan, void* stream);
+int byteps_reduce_powersgd_plan_finish(byteps_reduce_powersgd_plan* plan, void* stream);
+int byteps_reduce_powersgd_plan_destroy(byteps_reduce_powersgd_plan* plan);
 
 /* Block the calling thread until all work queued on `stream` has finished. */
 int byteps_reduce_sync(void* stream);

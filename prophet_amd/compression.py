@@ -151,6 +151,19 @@ maximum, round to nearest even, no floating-point reduction.
 ``compress_many_ef_into`` is ONE launch per device, ``fold_many_into`` decodes
 up to 16 payloads per output and adds them in order in one.  There is no server
 round for them yet: ``Worker.init_tensor`` refuses both over every front end.
+
+``Compression.powersgd_ef`` is the low-rank wire: a float32
+tensor of two or more dimensions is an n x m matrix and travels as ``P`` (n x r)
+and ``Q`` (m x r), ``(n + m) r`` floats, with error feedback and a warm-started
+``Q``.  ``prophet_amd/powersgd.py`` is the definition.  It is the first wire
+whose device path is not pinned byte for byte throughout: the two projections
+run on f32 matrix instructions in the kernels' own order and are held to a dot
+product's error bound; the ``g + R`` left in the residual, all of ``finish`` and
+determinism are pinned.  ``P`` and ``Q`` are plain float32 tensors, so the round
+needs no compressed context: ``powersgd.push_pull_many`` sends them with
+``Compression.none`` between the four phases ``project_p_many``,
+``orthogonalize_many``, ``project_q_many`` and ``finish_many``.
+``Worker.init_tensor`` refuses the compressor itself.
 """
 from __future__ import annotations
 
@@ -399,10 +412,23 @@ class CastPlanCache:
             for o, ps in segs)
         return self._get(key, lambda: _new_mx_fold_plan(segs, nsrc, fmt))
 
+    def get_powersgd(self, segs, rank: int):
+        """The PowerSGD plan (``GpuReducer.powersgd_plan``) over ``segs`` of
+        ``(grad, resid, p, q, qn, out, n, m)`` device tensors and shapes on the
+        current device."""
+        key = ("powersgd", int(rank)) + tuple(
+            tuple(int(x.data_ptr()) for x in s[:6]) + (int(s[6]), int(s[7])) for s in segs)
+        return self._get(key, lambda: _new_powersgd_plan(segs, rank))
+
     def close(self) -> None:
         while self._plans:
             _, plan = self._plans.popitem(last=False)
             plan.close()
+
+
+def _new_powersgd_plan(segs, rank: int):
+    from .torch_ops import _red
+    return _red().powersgd_plan(segs, rank)
 
 
 def _new_mx_plan(segs, fmt: str):
@@ -1738,6 +1764,133 @@ class MXFP4EFCompressor(MXFP8EFCompressor):
     FMT = "fp4"
 
 
+class PowerSGDEFCompressor(Compressor):
+    """float32 tensors of two or more dimensions travel as the two factors of
+    a rank-r approximation, with error feedback (``prophet_amd/powersgd.py`` is
+    the definition).  Device tensors go through PowerSGD plans
+    (``byteps_reduce_powersgd_*``, ``prophet_amd/csrc/bpsr_k_powersgd.hip``):
+    each of the four phases is one fixed sequence of launches per device over
+    every tensor; CPU tensors and numpy arrays go through ``powersgd.py``.  The
+    two projections are held to a dot product's error bound, not to the host's
+    bytes; the residual's ``g + R``, ``finish`` and determinism are pinned.
+
+    The wire is ``P`` and ``Q`` themselves, plain float32:
+    ``powersgd.push_pull_many`` is the round, and ``Worker.init_tensor`` refuses
+    this compressor.  The four ``*_many`` take the same ``tensors`` and
+    ``states`` (and ``outs``, the tensors themselves unless given), which is how
+    a cached plan is found again."""
+
+    ERROR_FEEDBACK = True
+    PACKED = True                         # no element-wise wire dtype: init_tensor refuses it
+
+    @staticmethod
+    def compresses(tensor, rank: int = 4) -> bool:
+        from .powersgd import compresses
+        return compresses(tensor, rank)
+
+    @classmethod
+    def state_like(cls, tensor, rank: int, seed: int):
+        """A ``powersgd.State`` of the tensor's kind and device — a zero
+        residual, the warm start ``init_q(m, rank, seed)``, zeroed ``P`` and
+        ``Qn`` — or None for a tensor that does not compress."""
+        from . import powersgd
+        if not cls.compresses(tensor, rank):
+            return None
+        n, m = powersgd.shape_of(tensor)
+        q = powersgd.init_q(m, rank, seed)
+        if _is_torch(tensor):
+            import torch
+            z = lambda *shape: torch.zeros(*shape, dtype=torch.float32,      # noqa: E731
+                                           device=tensor.device)
+            return powersgd.State(rank, n, m, z(n, m), torch.from_numpy(q).to(tensor.device),
+                                  z(n, rank), z(m, rank))
+        z = lambda *shape: np.zeros(shape, np.float32)                       # noqa: E731
+        return powersgd.State(rank, n, m, z(n, m), q, z(n, rank), z(m, rank))
+
+    @classmethod
+    def compress(cls, tensor):
+        raise ValueError("powersgd_ef has no stateless form: use powersgd.push_pull_many")
+
+    decompress = compress
+
+    @classmethod
+    def _phase(cls, name, tensors, states, plans, outs, host) -> None:
+        """Phase ``name`` of every (tensor, state): the device ones as one plan
+        per device and rank, the host ones through ``host(g, out, state)``."""
+        outs = tensors if outs is None else outs
+        if len(states) != len(tensors) or len(outs) != len(tensors):
+            raise ValueError(f"{name}_many: as many states and outputs as tensors")
+        groups = {}
+        for i, (t, o, st) in enumerate(zip(tensors, outs, states)):
+            ops = (t, o, st.R, st.Q, st.P, st.Qn)
+            if not cls.compresses(t, st.rank) or not all(_is_f32(x) for x in ops):
+                raise ValueError(f"powersgd_ef: tensor {i} does not compress at rank {st.rank}")
+            dev = [_on_device(x) for x in ops]
+            if any(dev) != all(dev):
+                raise ValueError(f"powersgd_ef: tensor {i}'s operands live in one place, a "
+                                 f"device or the host")
+            n, m = st.n, st.m
+            want = ((n * m, (t, o, st.R)), (n * st.rank, (st.P,)), (m * st.rank, (st.Q, st.Qn)))
+            if dev[0]:
+                for size, xs in want:
+                    if any(x.numel() != size or not x.is_contiguous() or x.device != t.device
+                           for x in xs):
+                        raise ValueError(f"powersgd_ef: tensor {i} needs contiguous operands of "
+                                         f"a {n} x {m} matrix at rank {st.rank} on {t.device}")
+                groups.setdefault((t.device, st.rank), []).append(
+                    (t, st.R, st.P, st.Q, st.Qn, o, n, m))
+                continue
+            if any(int(np.asarray(x).size) != size for size, xs in want for x in xs):
+                raise ValueError(f"powersgd_ef: tensor {i}'s operands differ in size")
+            # the phases write through reshaped views: a copy would lose the result
+            if not all(x.is_contiguous() if _is_torch(x) else x.flags["C_CONTIGUOUS"]
+                       for x in ops):
+                raise ValueError(f"powersgd_ef: tensor {i} needs contiguous operands")
+            view = lambda x, rows: (x.detach().numpy() if _is_torch(x) else x).reshape(rows, -1)  # noqa: E731
+            host(view(t, n), view(o, n), st, view)
+        for (device, rank), segs in groups.items():
+            OneBitEFCompressor._run({device: segs}, plans,
+                                    lambda cache, sg: cache.get_powersgd(sg, rank),
+                                    lambda plan, stream: getattr(plan, name)(stream=stream))
+
+    @classmethod
+    def project_p_many(cls, tensors, states, plans: CastPlanCache | None = None, outs=None):
+        """``state.P = powersgd.project_p(tensor, state.R, state.Q)`` for every i."""
+        from . import powersgd
+
+        def host(g, o, st, view):
+            view(st.P, st.n)[:] = powersgd.project_p(g, view(st.R, st.n), view(st.Q, st.m))
+        cls._phase("project_p", tensors, states, plans, outs, host)
+
+    @classmethod
+    def orthogonalize_many(cls, tensors, states, plans: CastPlanCache | None = None, outs=None):
+        """``powersgd.orthogonalize(state.P)`` for every i, on the aggregated ``P``."""
+        from . import powersgd
+        cls._phase("orthogonalize", tensors, states, plans, outs,
+                   lambda g, o, st, view: powersgd.orthogonalize(view(st.P, st.n)))
+
+    @classmethod
+    def project_q_many(cls, tensors, states, plans: CastPlanCache | None = None, outs=None):
+        """``state.Qn = powersgd.project_q(state.R, state.P)`` for every i."""
+        from . import powersgd
+
+        def host(g, o, st, view):
+            view(st.Qn, st.m)[:] = powersgd.project_q(view(st.R, st.n), view(st.P, st.n))
+        cls._phase("project_q", tensors, states, plans, outs, host)
+
+    @classmethod
+    def finish_many(cls, tensors, states, plans: CastPlanCache | None = None, outs=None):
+        """``powersgd.finish(out, state.R, state.P, state.Qn)`` for every i, on
+        the aggregated ``Qn``, which then becomes the warm start: ``state.Q`` and
+        ``state.Qn`` change places."""
+        from . import powersgd
+        cls._phase("finish", tensors, states, plans, outs,
+                   lambda g, o, st, view: powersgd.finish(o, view(st.R, st.n), view(st.P, st.n),
+                                                          view(st.Qn, st.m)))
+        for st in states:
+            st.Q, st.Qn = st.Qn, st.Q
+
+
 class Compression:
     """Optional gradient compression used during push_pull."""
 
@@ -1752,9 +1905,10 @@ class Compression:
     topk_ef = TopKEFCompressor
     mxfp8_ef = MXFP8EFCompressor
     mxfp4_ef = MXFP4EFCompressor
+    powersgd_ef = PowerSGDEFCompressor
 
 
 __all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
            "FP16EFCompressor", "BF16EFCompressor", "FP16SRCompressor", "BF16SRCompressor",
            "OneBitEFCompressor", "TopKEFCompressor", "MXFP8EFCompressor", "MXFP4EFCompressor",
-           "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]
+           "PowerSGDEFCompressor", "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]

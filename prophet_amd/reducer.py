@@ -79,6 +79,10 @@ EXPORTS = (
     "byteps_reduce_mx_payload_bytes", "byteps_reduce_mx_plan_create",
     "byteps_reduce_mx_plan_compress", "byteps_reduce_mx_fold_plan_create",
     "byteps_reduce_mx_fold_plan_launch", "byteps_reduce_mx_plan_destroy",
+    "byteps_reduce_powersgd_scratch_bytes", "byteps_reduce_powersgd_plan_create",
+    "byteps_reduce_powersgd_plan_project_p", "byteps_reduce_powersgd_plan_orthogonalize",
+    "byteps_reduce_powersgd_plan_project_q", "byteps_reduce_powersgd_plan_finish",
+    "byteps_reduce_powersgd_plan_destroy",
 )
 
 
@@ -150,6 +154,12 @@ class MXDesc(ctypes.Structure):
 class MXFoldDesc(ctypes.Structure):
     """``byteps_mx_fold_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64)]
+
+
+class PowerSGDDesc(ctypes.Structure):
+    """``byteps_powersgd_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("grad", _vp), ("resid", _vp), ("p", _vp), ("q", _vp), ("qn", _vp), ("out", _vp),
+                ("n", ctypes.c_uint64), ("m", ctypes.c_uint64)]
 
 
 class SrKey(int):
@@ -268,6 +278,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                     ctypes.POINTER(_vp)]
     L.byteps_reduce_mx_fold_plan_launch.argtypes = [_vp, _int, _vp]
     L.byteps_reduce_mx_plan_destroy.argtypes = [_vp]
+    L.byteps_reduce_powersgd_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, _int]
+    L.byteps_reduce_powersgd_scratch_bytes.restype = ctypes.c_uint64
+    L.byteps_reduce_powersgd_plan_create.argtypes = [ctypes.POINTER(PowerSGDDesc), _int, _int,
+                                                     ctypes.POINTER(_vp)]
+    for phase in ("project_p", "orthogonalize", "project_q", "finish"):
+        getattr(L, "byteps_reduce_powersgd_plan_" + phase).argtypes = [_vp, _vp]
+    L.byteps_reduce_powersgd_plan_destroy.argtypes = [_vp]
     _LIB = L
     return L
 
@@ -499,6 +516,17 @@ class GpuReducer:
         payloads each, added in that order.  :meth:`MXFoldPlan.launch` is ONE
         launch: ``prophet_amd.mx.fold`` byte for byte."""
         return MXFoldPlan(self.lib, segments, nsrc, fmt)
+
+    def powersgd_plan(self, segments: Sequence[tuple], rank: int) -> "PowerSGDPlan":
+        """PowerSGD low-rank compression of a whole iteration
+        (byteps_reduce_powersgd_plan_create): ``segments`` are ``(grad, resid,
+        p, q, qn, out, n, m)`` — float32 tensors or raw pointers, 16-byte
+        aligned: ``grad``, ``resid`` and ``out`` n x m (``out`` may be ``grad``),
+        ``p`` n x rank, ``q`` and ``qn`` m x rank.  The four phase methods of
+        :class:`PowerSGDPlan` are fixed sequences of launches on one stream;
+        ``prophet_amd.powersgd`` is the definition, the two contractions held to
+        a dot product's error bound and everything else byte for byte."""
+        return PowerSGDPlan(self.lib, segments, rank)
 
     def onebit_refold_plan(self, segments: Sequence[tuple], nsrc: int) -> "OneBitRefoldPlan":
         """The server round of the 1-bit wire
@@ -1162,6 +1190,60 @@ class MXFoldPlan(_MXPlanBase):
         """One launch (byteps_reduce_mx_fold_plan_launch)."""
         _check(self.lib.byteps_reduce_mx_fold_plan_launch(self.handle, int(divisor),
                                                           _stream_of(self.first, stream)))
+
+
+class PowerSGDPlan(_OneBitPlanBase):
+    """A PowerSGD plan (``byteps_reduce_powersgd_plan_create``).  Tensor
+    operands are bounds-checked before the library sees them."""
+
+    def __init__(self, lib, segments, rank):
+        super().__init__(lib)
+        self.rank = int(rank)
+        segments = [tuple(s) for s in segments]
+        for s in segments:
+            if len(s) != 8:
+                raise ValueError(f"powersgd plan: a segment of {len(s)} items")
+            n, m = int(s[6]), int(s[7])
+            if n < 0 or m < 0:
+                raise ValueError(f"negative shape ({n}, {m})")
+            _fits(n * m * 4, s[0], s[1], s[5])
+            _fits(n * self.rank * 4, s[2])
+            _fits(m * self.rank * 4, s[3], s[4])
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (PowerSGDDesc * max(1, len(segments)))()
+        for d, s in zip(descs, segments):
+            d.grad, d.resid, d.p, d.q, d.qn, d.out = (_ptr(x) for x in s[:6])
+            d.n, d.m = int(s[6]), int(s[7])
+        _check(lib.byteps_reduce_powersgd_plan_create(descs, len(segments), self.rank,
+                                                      ctypes.byref(self.handle)))
+
+    def _phase(self, name, stream) -> None:
+        _check(getattr(self.lib, "byteps_reduce_powersgd_plan_" + name)(
+            self.handle, _stream_of(self.first, stream)))
+
+    def project_p(self, stream=None) -> None:
+        """``R = g + R``, ``P = R @ Q`` (byteps_reduce_powersgd_plan_project_p)."""
+        self._phase("project_p", stream)
+
+    def orthogonalize(self, stream=None) -> None:
+        """Gram-Schmidt over every ``P`` (byteps_reduce_powersgd_plan_orthogonalize)."""
+        self._phase("orthogonalize", stream)
+
+    def project_q(self, stream=None) -> None:
+        """``Qn = R.T @ P`` (byteps_reduce_powersgd_plan_project_q)."""
+        self._phase("project_q", stream)
+
+    def finish(self, stream=None) -> None:
+        """``out = P @ Qn.T``, ``R -= out`` (byteps_reduce_powersgd_plan_finish)."""
+        self._phase("finish", stream)
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.byteps_reduce_powersgd_plan_destroy(self.handle)
+            self.handle = _vp()
+        self._keep = []
 
 
 class BlockQueue:

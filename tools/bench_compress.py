@@ -251,7 +251,13 @@ def main() -> int:
                         "multiply, subtract per tensor and against the fp16_ef cast plan, and "
                         "the 8-source fold against eight widen-multiply-add steps on "
                         "pre-unpacked codes; the ResNet-50 table and one segment")
+    p.add_argument("--powersgd", action="store_true",
+                   help="PowerSGD at rank 4: the four phases and their sum against torch's add, "
+                        "matmul, linalg.qr, matmul, mm and sub per tensor; the ResNet-50 table's "
+                        "entries that compress, viewed as matrices, and one 4096 x 16384 matrix")
     args = p.parse_args()
+    if args.powersgd:
+        return powersgd_mode(args)
     if args.mx:
         return mx_mode(args)
     if args.topk:
@@ -1806,6 +1812,126 @@ def mx_mode(args) -> int:
         torch.cuda.empty_cache()
         out[f"big_{fmt}"] = shape(f"big_{fmt}", fmt, [(0, args.elems)], args.elems)
         torch.cuda.empty_cache()
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    return 0 if all(gates.values()) and all(v for c in checks.values() for v in c.values()) else 1
+
+
+def powersgd_mode(args) -> int:
+    """PowerSGD, the --onebit protocol, rank 4.  The table
+    holds flat sizes, so an entry of N >= 4096 elements is viewed as the n x N / n
+    matrix with n the largest power of two that divides N, n <= 512 and n n <= N
+    (64 x 147, 512 x 1152, 512 x 4000, ...); the shorter entries are the vectors
+    of the model and do not compress.  Each phase is timed on its own and the
+    four are added; torch's column is the same iteration per tensor: add, matmul,
+    linalg.qr, matmul, mm, sub.  Before timing, one iteration from a zero residual:
+    out against torch's out, and R against g - out byte for byte."""
+    import torch
+
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    RANK = 4
+    out = {"tool": "bench_compress", "mode": "powersgd_ef phases", "rank": RANK,
+           "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+    PHASES = ("project_p", "orthogonalize", "project_q", "finish")
+
+    def shape(label, mats):
+        nelem = sum(n * m for n, m in mats)
+        small = sum((n + m) * RANK for n, m in mats)
+
+        def cut(t, sizes):                       # consecutive 2-d views of a flat arena
+            views, at = [], 0
+            for rows, cols in sizes:
+                views.append(t[at:at + rows * cols].view(rows, cols))
+                at += rows * cols
+            return views
+        with step(f"setup, {label}", 300):
+            gen = torch.Generator(device=dev).manual_seed(13)
+            sets = []
+            for _ in range(args.sets):
+                s = {k: cut(torch.zeros(nelem, device=dev), mats) for k in ("R", "Rt", "out", "out_t")}
+                s["g"] = cut(torch.randn(nelem, device=dev, generator=gen), mats)
+                s["Q"] = cut(torch.randn(small, device=dev, generator=gen),
+                             [(m, RANK) for _, m in mats])
+                s["P"] = cut(torch.zeros(small, device=dev), [(n, RANK) for n, _ in mats])
+                s["Qn"] = cut(torch.zeros(small, device=dev), [(m, RANK) for _, m in mats])
+                s["Pt"], s["Qt"] = [torch.zeros_like(x) for x in s["P"]], \
+                    [torch.zeros_like(x) for x in s["Qn"]]
+                s["plan"] = red.powersgd_plan(
+                    [(g, r, pp, q, qn, o, n, m) for g, r, pp, q, qn, o, (n, m) in
+                     zip(s["g"], s["R"], s["P"], s["Q"], s["Qn"], s["out"], mats)], RANK)
+                sets.append(s)
+            torch.cuda.synchronize()
+
+        def torch_iteration(i):
+            s = sets[i]
+            for g, r, q, pt, qt, o in zip(s["g"], s["Rt"], s["Q"], s["Pt"], s["Qt"], s["out_t"]):
+                torch.add(g, r, out=r)
+                torch.matmul(r, q, out=pt)
+                ph = torch.linalg.qr(pt)[0]
+                torch.matmul(r.t(), ph, out=qt)
+                torch.mm(ph, qt.t(), out=o)
+                r.sub_(o)
+
+        with step(f"check, {label}", 300):
+            s = sets[0]
+            s["plan"].project_p()
+            torch_iteration(0)
+            for name in PHASES[1:]:
+                getattr(s["plan"], name)()
+            torch.cuda.synchronize()
+            close = True
+            for g, r, o, ot in zip(s["g"], s["R"], s["out"], s["out_t"]):   # R was 0: M is g
+                close = close and bool((o - ot).abs().max() <= 1e-3 * g.abs().max())
+                close = close and bool(torch.equal(r, torch.where(torch.isfinite(o), g - o, 0.0)))
+            checks[label] = {"out_close_to_torch_and_residual_is_g_minus_out": close}
+            for name in ("R", "Rt"):
+                for x in s[name]:
+                    x.zero_()
+        cands = {name: ((lambda i, name=name: getattr(sets[i]["plan"], name)()), args.inner)
+                 for name in PHASES}
+        cands["torch_iteration"] = (torch_iteration, max(1, args.inner // 4))
+        res = timed_rounds(torch, cands, len(sets), args)
+        total = sum(res[name]["ms"] for name in PHASES)
+        spread = sum(res[name]["spread_ms"] for name in PHASES)
+        res["sum_of_phases"] = {"ms": round(total, 5), "spread_ms": round(spread, 5),
+                                "bytes_per_elem": 28.0,
+                                "roofline_frac": round(28.0 * nelem / (total * 1e-3)
+                                                       / HBM_BYTES_PER_S, 4),
+                                "torch_over_ours": round(res["torch_iteration"]["ms"] / total, 2)}
+        for name, per in (("project_p", 12.0), ("project_q", 4.0), ("finish", 12.0)):
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        gates[f"{label}_sum_beats_torch"] = \
+            res["torch_iteration"]["ms"] - total > max(spread, res["torch_iteration"]["spread_ms"])
+        for s in sets:
+            s["plan"].close()
+        return {"segments": len(mats), "elems": nelem, "wire_floats": small, "results": res}
+
+    def matrix_of(nelem):
+        n = 512
+        while nelem % n or n * n > nelem:
+            n //= 2
+        return n, nelem // n
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    _, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    out["iteration"] = shape("table", [matrix_of(ln // 2) for _, ln in rows if ln // 2 >= 4096])
+    torch.cuda.empty_cache()
+    out["big"] = shape("big", [(4096, 16384)])
     out.update({"checks": checks, "gates": gates})
     line = json.dumps(out)
     print(line, flush=True)
