@@ -88,6 +88,10 @@ extern "C" {
  *                       feedback)
  *    additive, still 5: byteps_reduce_mx_* (byteps_mx_desc, byteps_mx_fold_desc:
  *                       block-scaled 8- and 4-bit wires with error feedback)
+ *    additive, still 5: byteps_reduce_mx_sr_*, byteps_reduce_mx_rht_fold_*
+ *                       (byteps_mx_sr_desc, byteps_mx_rht_fold_desc: the same
+ *                       wires stateless, stochastically rounded, optionally
+ *                       rotated)
  *    additive, still 5: byteps_reduce_powersgd_* (byteps_powersgd_desc: PowerSGD
  *                       low-rank compression with error feedback) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
@@ -854,6 +858,52 @@ int byteps_reduce_mx_fold_plan_create(const byteps_mx_fold_desc* segs, int nsegs
                                       int bits, byteps_reduce_mx_plan** out);
 int byteps_reduce_mx_fold_plan_launch(byteps_reduce_mx_plan* plan, int divisor, void* stream);
 int byteps_reduce_mx_plan_destroy(byteps_reduce_mx_plan* plan);
+
+/* The stateless block-scaled wires (the definition is
+ * prophet_amd/mx_sr.py, byte for byte): the payload above without a residual.
+ * A code is rounded up with a probability equal to the dropped fraction, under
+ * the 16 bits of byteps_reduce_compress_sr's element (Philox2x32-10 of (i >> 2,
+ * step, key)), and the scale is bumped by one where 2^emax times the block's
+ * largest mantissa would pass the format's max, so nothing is clamped:
+ *
+ *   X_b   = 255 if E_b == 255, else max(E_b - emax + bump, 0)
+ *   v_i   = c_i * 2^(127 - X_b)
+ *   q_i   = v_i rounded down to the format, plus the carry of (f + r16_i), f the
+ *           dropped fraction's first 16 bits; the sign kept
+ *
+ * rotate == 0: c = g, and the payloads fold through _fold_plan_* above.  rotate
+ * == 1: every whole block of 32 has the signs of its elements flipped by the
+ * bits of x0 of Philox2x32-10 of (block, step, rot_key) and goes through the
+ * unnormalised Walsh-Hadamard butterflies (h = 1, 2, 4, 8, 16; (a + b, a - b))
+ * before it is scaled; a last block of fewer than 32 elements is left as it is.
+ * The header's fourth u32 is `rotate`.  _rht_fold_* is the fold of such
+ * payloads: the sum in argument order, the butterflies again, 2^-5, the signs,
+ * then the divide; a block where any source has X_b == 255 is 0x7fc00000.  It
+ * takes the rot_key and the step of the compress.
+ *
+ * Both plans are byteps_reduce_mx_plan: ONE launch each, no scratch memory,
+ * freed by byteps_reduce_mx_plan_destroy.  EARGS as above, and for rotate other
+ * than 0 or 1 and any launch on a plan of another kind. */
+typedef struct byteps_mx_sr_desc {
+  const void* grad;
+  void* payload;
+  uint64_t nelem;
+  uint32_t key;
+  uint32_t rot_key;
+} byteps_mx_sr_desc;
+typedef struct byteps_mx_rht_fold_desc {
+  void* out;
+  const void* const* payloads; /* nsrc of them; read by _plan_create alone */
+  uint64_t nelem;
+  uint32_t rot_key;
+} byteps_mx_rht_fold_desc;
+int byteps_reduce_mx_sr_plan_create(const byteps_mx_sr_desc* segs, int nsegs, int bits,
+                                    int rotate, byteps_reduce_mx_plan** out);
+int byteps_reduce_mx_sr_plan_compress(byteps_reduce_mx_plan* plan, uint32_t step, void* stream);
+int byteps_reduce_mx_rht_fold_plan_create(const byteps_mx_rht_fold_desc* segs, int nsegs,
+                                          int nsrc, int bits, byteps_reduce_mx_plan** out);
+int byteps_reduce_mx_rht_fold_plan_launch(byteps_reduce_mx_plan* plan, int divisor,
+                                          uint32_t step, void* stream);
 
 /* PowerSGD low-rank compression with error feedback (the
  * definition is prophet_amd/powersgd.py).  A segment is one row-major n x m

@@ -152,6 +152,15 @@ maximum, round to nearest even, no floating-point reduction.
 up to 16 payloads per output and adds them in order in one.  There is no server
 round for them yet: ``Worker.init_tensor`` refuses both over every front end.
 
+``Compression.mxfp8_sr`` and ``Compression.mxfp4_sr`` are the same wire with no
+residual (``prophet_amd/mx_sr.py`` is the definition): the
+codes are rounded stochastically under ``fp16_sr``'s bits and the scale is
+bumped so that nothing is clamped, which makes the decode right in expectation.
+``Compression.mxfp8_rht_sr`` and ``Compression.mxfp4_rht_sr`` rotate every whole
+block by a random-sign Hadamard transform first, under a key all workers share,
+and undo it once in the fold.  ``compress_many_sr_into`` and ``fold_many_into``
+are ONE launch per device each; ``Worker.init_tensor`` refuses all four.
+
 ``Compression.powersgd_ef`` is the low-rank wire: a float32
 tensor of two or more dimensions is an n x m matrix and travels as ``P`` (n x r)
 and ``Q`` (m x r), ``(n + m) r`` floats, with error feedback and a warm-started
@@ -412,6 +421,23 @@ class CastPlanCache:
             for o, ps in segs)
         return self._get(key, lambda: _new_mx_fold_plan(segs, nsrc, fmt))
 
+    def get_mx_sr(self, segs, fmt: str, rotate: bool = False):
+        """The stateless block-scaled compress plan (``GpuReducer.mx_sr_plan``)
+        over ``segs`` of flat ``(grad, payload, key, rot_key)`` device tensors
+        and keys on the current device: another key misses."""
+        key = ("mx_sr", fmt, bool(rotate)) + tuple(
+            (int(g.data_ptr()), int(p.data_ptr()), int(g.numel()), int(k), int(rk))
+            for g, p, k, rk in segs)
+        return self._get(key, lambda: _new_mx_sr_plan(segs, fmt, rotate))
+
+    def get_mx_rht_fold(self, segs, nsrc: int, fmt: str):
+        """The rotated block-scaled fold plan (``GpuReducer.mx_rht_fold_plan``)
+        over ``segs`` of ``(out, payloads, rot_key)`` on the current device."""
+        key = ("mx_rht_fold", fmt, int(nsrc)) + tuple(
+            (int(o.data_ptr()), int(o.numel()), int(rk)) + tuple(int(p.data_ptr()) for p in ps)
+            for o, ps, rk in segs)
+        return self._get(key, lambda: _new_mx_rht_fold_plan(segs, nsrc, fmt))
+
     def get_powersgd(self, segs, rank: int):
         """The PowerSGD plan (``GpuReducer.powersgd_plan``) over ``segs`` of
         ``(grad, resid, p, q, qn, out, n, m)`` device tensors and shapes on the
@@ -439,6 +465,16 @@ def _new_mx_plan(segs, fmt: str):
 def _new_mx_fold_plan(segs, nsrc: int, fmt: str):
     from .torch_ops import _red
     return _red().mx_fold_plan([(o, ps, int(o.numel())) for o, ps in segs], nsrc, fmt)
+
+
+def _new_mx_sr_plan(segs, fmt: str, rotate: bool):
+    from .torch_ops import _red
+    return _red().mx_sr_plan([(g, p, int(g.numel()), k, rk) for g, p, k, rk in segs], fmt, rotate)
+
+
+def _new_mx_rht_fold_plan(segs, nsrc: int, fmt: str):
+    from .torch_ops import _red
+    return _red().mx_rht_fold_plan([(o, ps, int(o.numel()), rk) for o, ps, rk in segs], nsrc, fmt)
 
 
 def _new_topk_plan(segs):
@@ -1764,6 +1800,182 @@ class MXFP4EFCompressor(MXFP8EFCompressor):
     FMT = "fp4"
 
 
+class MXFP8SRCompressor(Compressor):
+    """float32 tensors travel in ``mxfp8_ef``'s blocks with no residual: a code
+    is rounded up with a probability equal to the dropped fraction, under bits
+    that are a pure function of ``(key, step, element index)``
+    (``prophet_amd/mx_sr.py`` is the definition).  The
+    ``ROTATE`` variants (``mxfp8_rht_sr``, ``mxfp4_rht_sr``) put every whole
+    block through a random-sign Hadamard rotation first, under a ``rot_key``
+    all workers of a tensor share (``mx_sr.rotation_key``), and undo it once in
+    the fold, which then takes the compress's ``rot_keys`` and ``step``.
+    Device tensors go through plans (``byteps_reduce_mx_sr_*``,
+    ``byteps_reduce_mx_rht_fold_*``, ``prophet_amd/csrc/bpsr_k_mx_sr.hip``; the
+    unrotated fold is ``mxfp8_ef``'s): ONE launch per device either way; CPU
+    tensors and numpy arrays go through ``mx_sr.py``, byte for byte the same.
+    Everything but float32 passes through.
+
+    There is no server round for these wires: ``Worker.init_tensor`` refuses
+    them over every front end."""
+
+    STOCHASTIC = True
+    PACKED = True
+    FMT = "fp8"
+    ROTATE = False
+
+    compresses = classmethod(MXFP8EFCompressor.compresses.__func__)
+    payload_like = classmethod(MXFP8EFCompressor.payload_like.__func__)
+
+    @classmethod
+    def _name(cls) -> str:
+        return f"mx{cls.FMT}{'_rht' if cls.ROTATE else ''}_sr"
+
+    @classmethod
+    def compress(cls, tensor, key: int = 0, step: int = 0, rot_key: int = 0):
+        """One payload under ``(key, step, rot_key)``; ``ctx`` is ``(dtype,
+        shape, rot_key, step)``."""
+        ctx = (tensor.dtype, tuple(tensor.shape), rot_key, step)
+        if not cls.compresses(tensor):
+            return tensor, ctx
+        flat = tensor.contiguous() if _is_torch(tensor) else np.ascontiguousarray(tensor)
+        return cls.compress_sr_into(cls.payload_like(flat), flat, key, step, rot_key), ctx
+
+    @classmethod
+    def decompress(cls, payload, ctx):
+        dtype, shape, rot_key, step = ctx
+        if payload.dtype == dtype:
+            return payload
+        if _is_torch(payload):
+            import torch
+            out = torch.empty(shape, dtype=dtype, device=payload.device)
+        else:
+            out = np.empty(shape, dtype=dtype)
+        return cls.decompress_into(out, payload, 1, rot_key, step)
+
+    @classmethod
+    def compress_sr_into(cls, payload, tensor, key: int, step: int, rot_key: int = 0,
+                         plans: CastPlanCache | None = None):
+        """``payload = mx_sr.compress(tensor, FMT, key, step, ROTATE,
+        rot_key)``; returns ``payload``."""
+        cls.compress_many_sr_into([payload], [tensor], [key], step, [rot_key], plans)
+        return payload
+
+    @classmethod
+    def compress_many_sr_into(cls, payloads, tensors, keys, step: int, rot_keys=None,
+                              plans: CastPlanCache | None = None):
+        """``compress_sr_into`` for every i, the device tensors as one plan per
+        device (ONE launch); returns ``payloads``."""
+        from . import mx, mx_sr
+        rot_keys = [0] * len(tensors) if rot_keys is None else list(rot_keys)
+        if not len(payloads) == len(keys) == len(rot_keys) == len(tensors):
+            raise ValueError("compress_many_sr_into: as many payloads and keys as tensors")
+        name, groups = cls._name(), {}
+        for i, (p, t, k, rk) in enumerate(zip(payloads, tensors, keys, rot_keys)):
+            if not cls.compresses(t):
+                raise ValueError(f"{name} needs float32 tensors")
+            k, rk = int(k) & 0xffffffff, int(rk) & 0xffffffff
+            if _on_device(p) != _on_device(t):
+                raise ValueError(f"{name}: tensor {i}'s operands live in one place, a device "
+                                 f"or the host")
+            if _on_device(t):
+                cls._check_device_segment(i, t, p)
+                groups.setdefault(t.device, []).append((t.reshape(-1), p, k, rk))
+                continue
+            ga = t.detach().numpy() if _is_torch(t) else t
+            pa = _payload_array(p)
+            if pa.size != mx.payload_bytes(ga.size, cls.FMT):
+                raise ValueError(f"{name}: tensor {i}'s operands differ in size")
+            pa[:] = mx_sr.compress(ga, cls.FMT, k, step, cls.ROTATE, rk)
+        OneBitEFCompressor._run(
+            groups, plans, lambda cache, segs: cache.get_mx_sr(segs, cls.FMT, cls.ROTATE),
+            lambda plan, stream: plan.compress(step, stream=stream))
+        return payloads
+
+    @classmethod
+    def decompress_into(cls, out, payload, divisor: int = 1, rot_key: int = 0, step=None,
+                        plans: CastPlanCache | None = None):
+        """The one-source fold; returns ``out``."""
+        cls.fold_many_into([out], [[payload]], divisor, [rot_key], step, plans)
+        return out
+
+    @classmethod
+    def fold_many_into(cls, outs, payload_lists, divisor: int = 1, rot_keys=None, step=None,
+                       plans: CastPlanCache | None = None):
+        """``outs[i] = mx_sr.fold(payload_lists[i], outs[i].size, FMT, divisor,
+        ROTATE, rot_keys[i], step)`` for every i — every list of the same
+        length N, 1..16 — the device tensors as one fold plan per device (ONE
+        launch); returns ``outs``.  The unrotated compressors take
+        ``mxfp8_ef``'s fold plan and read neither ``rot_keys`` nor ``step``."""
+        from . import mx, mx_sr
+        if not cls.ROTATE:
+            return MXFP8EFCompressor.fold_many_into.__func__(cls, outs, payload_lists, divisor,
+                                                             plans)
+        if step is None:
+            raise ValueError(f"{cls._name()}: a rotated fold takes the compress's step")
+        rot_keys = [0] * len(outs) if rot_keys is None else list(rot_keys)
+        if len(outs) != len(payload_lists) or len(rot_keys) != len(outs):
+            raise ValueError("fold_many_into: as many payload lists and rotation keys as outputs")
+        if int(divisor) < 1:
+            raise ValueError(f"divisor {divisor} < 1")
+        nsrc = len(payload_lists[0]) if payload_lists else 1
+        if not 1 <= nsrc <= mx.MAX_SRCS or any(len(ps) != nsrc for ps in payload_lists):
+            raise ValueError(f"fold_many_into: every output takes the same 1..{mx.MAX_SRCS} "
+                             f"payloads")
+        name, groups = cls._name(), {}
+        for i, (o, ps, rk) in enumerate(zip(outs, payload_lists, rot_keys)):
+            if not _is_f32(o):
+                raise ValueError(f"{name}: output {i} must be float32, got {o.dtype}")
+            dev = [_on_device(x) for x in [o] + list(ps)]
+            if any(dev) != all(dev):
+                raise ValueError(f"{name}: output {i} and its payloads live in one place, a "
+                                 f"device or the host")
+            rk = int(rk) & 0xffffffff
+            if dev[0]:
+                for p in ps:
+                    cls._check_device_segment(i, o, p)
+                groups.setdefault(o.device, []).append((o.reshape(-1), list(ps), rk))
+                continue
+            oa = (o.detach().numpy() if _is_torch(o) else o).reshape(-1)
+            oa[:] = mx_sr.fold([_payload_array(p) for p in ps], oa.size, cls.FMT, divisor, True,
+                               rk, step)
+        OneBitEFCompressor._run(
+            groups, plans, lambda cache, segs: cache.get_mx_rht_fold(segs, nsrc, cls.FMT),
+            lambda plan, stream: plan.launch(int(divisor), step, stream=stream))
+        return outs
+
+    @classmethod
+    def _check_device_segment(cls, i: int, tensor, payload=None, **_) -> None:
+        """One device segment: a contiguous float32 tensor and a flat uint8
+        payload of the payload's size on its device."""
+        import torch
+        from .mx import payload_bytes
+        size = payload_bytes(tensor.numel(), cls.FMT)
+        if not tensor.is_contiguous() or payload.dtype != torch.uint8 \
+                or not payload.is_contiguous() or payload.dim() != 1 \
+                or payload.device != tensor.device or payload.numel() != size:
+            raise ValueError(f"{cls._name()}: tensor {i} must be contiguous and its payload a "
+                             f"flat uint8 tensor of {size} bytes on {tensor.device}")
+
+
+class MXFP4SRCompressor(MXFP8SRCompressor):
+    """``MXFP8SRCompressor`` over OCP e2m1 codes."""
+
+    FMT = "fp4"
+
+
+class MXFP8RHTSRCompressor(MXFP8SRCompressor):
+    """``MXFP8SRCompressor`` with every whole block rotated."""
+
+    ROTATE = True
+
+
+class MXFP4RHTSRCompressor(MXFP8SRCompressor):
+    """``MXFP4SRCompressor`` with every whole block rotated."""
+
+    FMT = "fp4"
+    ROTATE = True
+
+
 class PowerSGDEFCompressor(Compressor):
     """float32 tensors of two or more dimensions travel as the two factors of
     a rank-r approximation, with error feedback (``prophet_amd/powersgd.py`` is
@@ -1905,10 +2117,15 @@ class Compression:
     topk_ef = TopKEFCompressor
     mxfp8_ef = MXFP8EFCompressor
     mxfp4_ef = MXFP4EFCompressor
+    mxfp8_sr = MXFP8SRCompressor
+    mxfp4_sr = MXFP4SRCompressor
+    mxfp8_rht_sr = MXFP8RHTSRCompressor
+    mxfp4_rht_sr = MXFP4RHTSRCompressor
     powersgd_ef = PowerSGDEFCompressor
 
 
 __all__ = ["Compressor", "NoneCompressor", "FP16Compressor", "BF16Compressor",
            "FP16EFCompressor", "BF16EFCompressor", "FP16SRCompressor", "BF16SRCompressor",
            "OneBitEFCompressor", "TopKEFCompressor", "MXFP8EFCompressor", "MXFP4EFCompressor",
-           "PowerSGDEFCompressor", "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]
+           "MXFP8SRCompressor", "MXFP4SRCompressor", "MXFP8RHTSRCompressor",
+           "MXFP4RHTSRCompressor", "PowerSGDEFCompressor", "Compression", "CastPlanCache", "decompress_stats", "clip_record", "ClipValues"]

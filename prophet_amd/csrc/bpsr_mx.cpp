@@ -1,7 +1,9 @@
-// Block-scaled 8- and 4-bit wires with error feedback, host side
-// (byteps_reduce_mx_*, include/bpsr/reduce.h): the operand checks, the two
-// plans' tables (bpsr_mx.h) and the C entry points.  Every check runs before
-// the first HIP call of its entry: a refused call has touched nothing.
+// Block-scaled 8- and 4-bit wires, host side (byteps_reduce_mx_*,
+// include/bpsr/reduce.h): the operand checks, the plans' tables (bpsr_mx.h) and
+// the C entry points — the error-feedback compress and the fold, and the
+// stateless wires' compress and rotated fold (byteps_reduce_mx_sr_*,
+// byteps_reduce_mx_rht_fold_*).  Every check runs before the first HIP call of
+// its entry: a refused call has touched nothing.
 #include <algorithm>
 #include <cstring>
 
@@ -9,7 +11,11 @@
 #include "bpsr_mx.h"
 
 struct byteps_reduce_mx_plan {
-  bool fold = false;
+  // which launch takes it: _plan_compress, _fold_plan_launch, _sr_plan_compress,
+  // _rht_fold_plan_launch
+  enum Kind { kCompress, kFold, kSrCompress, kRhtFold };
+  Kind kind = kCompress;
+  bool rotate = false;  // kSrCompress
   uint32_t bits = 0;
   int nsrc = 0;  // fold
   uint32_t nrecs = 0;
@@ -155,8 +161,8 @@ int byteps_reduce_mx_plan_create(const byteps_mx_desc* segs, int nsegs, int bits
 
 int byteps_reduce_mx_plan_compress(byteps_reduce_mx_plan* p, void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
-  if (p->fold)
-    return fail(BYTEPS_REDUCE_EARGS, "compress on a fold plan (byteps_reduce_mx_fold_plan_launch)");
+  if (p->kind != byteps_reduce_mx_plan::kCompress)
+    return fail(BYTEPS_REDUCE_EARGS, "compress on a plan of another kind");
   const MxCompress a{static_cast<const MxRec*>(p->table), static_cast<const MxSeg*>(p->side),
                      p->nrecs};
   // more than 4 sources: the process-wide tuning as it stands
@@ -196,7 +202,7 @@ int byteps_reduce_mx_fold_plan_create(const byteps_mx_fold_desc* segs, int nsegs
   }
   if (int rc = check_disjoint(ranges)) return rc;
   auto* p = new byteps_reduce_mx_plan();
-  p->fold = true;
+  p->kind = byteps_reduce_mx_plan::kFold;
   p->bits = (uint32_t)bits;
   p->nsrc = nsrc;
   p->nrecs = (uint32_t)recs.size();
@@ -214,7 +220,8 @@ int byteps_reduce_mx_fold_plan_create(const byteps_mx_fold_desc* segs, int nsegs
 
 int byteps_reduce_mx_fold_plan_launch(byteps_reduce_mx_plan* p, int divisor, void* stream) {
   if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
-  if (!p->fold) return fail(BYTEPS_REDUCE_EARGS, "fold launch on a compress plan");
+  if (p->kind != byteps_reduce_mx_plan::kFold)
+    return fail(BYTEPS_REDUCE_EARGS, "fold launch on a plan of another kind");
   if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
   const MxFold a{static_cast<const MxRec*>(p->table),
                  static_cast<const MxSeg*>(p->side),
@@ -225,6 +232,121 @@ int byteps_reduce_mx_fold_plan_launch(byteps_reduce_mx_plan* p, int divisor, voi
   const hipError_t e = launch_mx_fold(a, p->bits, p->nelem * 4, launch_tuning_for_n(kMxMaxSrcs),
                                       stream_of(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx fold kernel launch");
+}
+
+int byteps_reduce_mx_sr_plan_create(const byteps_mx_sr_desc* segs, int nsegs, int bits,
+                                    int rotate, byteps_reduce_mx_plan** out) {
+  if (int rc = check_table(segs, nsegs, bits, out)) return rc;
+  if (rotate != 0 && rotate != 1) return fail(BYTEPS_REDUCE_EARGS, "rotate %d: 0 or 1", rotate);
+  std::vector<MxRec> recs;
+  std::vector<MxSrSeg> stab((size_t)nsegs);
+  std::vector<Range> ranges;
+  for (int i = 0; i < nsegs; ++i) {
+    const byteps_mx_sr_desc& d = segs[i];
+    if (int rc = check_operand(d.nelem, d.payload, 16, "payload", i)) return rc;
+    if (int rc = check_operand(d.nelem, d.grad, 4, "gradient", i)) return rc;
+    if (d.nelem > 0 && (!d.grad || !d.payload))
+      return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
+    // an empty segment still gets its header where it names a payload
+    const bool ok = (!d.payload ||
+                     add_range(ranges, d.payload, mx_payload_bytes(d.nelem, (uint32_t)bits), i)) &&
+                    add_range(ranges, d.grad, d.nelem * 4, i);
+    if (!ok) return fail(BYTEPS_REDUCE_EARGS, "segment %d: operand wraps the address space", i);
+    cut(recs, static_cast<unsigned char*>(const_cast<void*>(d.grad)), nullptr, d.nelem,
+        (uint32_t)i, d.payload != nullptr);
+    stab[(size_t)i] = MxSrSeg{static_cast<unsigned char*>(d.payload), d.nelem, d.key, d.rot_key,
+                              {0, 0}};
+    if (recs.size() >= (1ull << 31)) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
+  }
+  if (int rc = check_disjoint(ranges)) return rc;
+  auto* p = new byteps_reduce_mx_plan();
+  p->kind = byteps_reduce_mx_plan::kSrCompress;
+  p->rotate = rotate == 1;
+  p->bits = (uint32_t)bits;
+  p->nrecs = (uint32_t)recs.size();
+  hipError_t e = upload(&p->table, recs);
+  if (e == hipSuccess) e = upload(&p->side, stab);
+  if (e != hipSuccess) {
+    (void)plan_free(p);
+    return hip_fail(e, "mx sr plan table upload");
+  }
+  *out = p;
+  return BYTEPS_REDUCE_OK;
+}
+
+int byteps_reduce_mx_sr_plan_compress(byteps_reduce_mx_plan* p, uint32_t step, void* stream) {
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (p->kind != byteps_reduce_mx_plan::kSrCompress)
+    return fail(BYTEPS_REDUCE_EARGS, "stochastic compress on a plan of another kind");
+  const MxSrCompress a{static_cast<const MxRec*>(p->table), static_cast<const MxSrSeg*>(p->side),
+                       p->nrecs, step};
+  const hipError_t e = launch_mx_sr_compress(a, p->bits, p->rotate, stream_of(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx sr compress kernel launch");
+}
+
+int byteps_reduce_mx_rht_fold_plan_create(const byteps_mx_rht_fold_desc* segs, int nsegs,
+                                          int nsrc, int bits, byteps_reduce_mx_plan** out) {
+  if (int rc = check_table(segs, nsegs, bits, out)) return rc;
+  if (nsrc < 1 || nsrc > kMxMaxSrcs)
+    return fail(BYTEPS_REDUCE_EARGS, "nsrc %d outside 1..%d", nsrc, kMxMaxSrcs);
+  std::vector<MxRec> recs;
+  std::vector<MxSrSeg> stab((size_t)nsegs);
+  std::vector<const unsigned char*> rows((size_t)nsegs * (size_t)nsrc, nullptr);
+  std::vector<Range> ranges;
+  uint64_t total = 0;
+  for (int i = 0; i < nsegs; ++i) {
+    const byteps_mx_rht_fold_desc& d = segs[i];
+    if (int rc = check_operand(d.nelem, d.out, 4, "output", i)) return rc;
+    stab[(size_t)i] = MxSrSeg{nullptr, d.nelem, 0, d.rot_key, {0, 0}};
+    if (d.nelem == 0) continue;
+    if (!d.out || !d.payloads) return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
+    bool ok = add_range(ranges, d.out, d.nelem * 4, i);
+    for (int s = 0; s < nsrc; ++s) {
+      const void* pl = d.payloads[s];
+      if (!pl) return fail(BYTEPS_REDUCE_EARGS, "segment %d: null payload %d", i, s);
+      if (int rc = check_operand(d.nelem, pl, 16, "payload", i)) return rc;
+      ok = ok && add_range(ranges, pl, mx_payload_bytes(d.nelem, (uint32_t)bits), i);
+      rows[(size_t)i * (size_t)nsrc + (size_t)s] = static_cast<const unsigned char*>(pl);
+    }
+    if (!ok) return fail(BYTEPS_REDUCE_EARGS, "segment %d: operand wraps the address space", i);
+    cut(recs, static_cast<unsigned char*>(d.out), nullptr, d.nelem, (uint32_t)i, false);
+    total += d.nelem;
+    if (recs.size() >= (1ull << 31)) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
+  }
+  if (int rc = check_disjoint(ranges)) return rc;
+  auto* p = new byteps_reduce_mx_plan();
+  p->kind = byteps_reduce_mx_plan::kRhtFold;
+  p->bits = (uint32_t)bits;
+  p->nsrc = nsrc;
+  p->nrecs = (uint32_t)recs.size();
+  p->nelem = total;
+  hipError_t e = upload(&p->table, recs);
+  if (e == hipSuccess) e = upload(&p->side, stab);
+  if (e == hipSuccess) e = upload(&p->rows, rows);
+  if (e != hipSuccess) {
+    (void)plan_free(p);
+    return hip_fail(e, "mx rht fold plan table upload");
+  }
+  *out = p;
+  return BYTEPS_REDUCE_OK;
+}
+
+int byteps_reduce_mx_rht_fold_plan_launch(byteps_reduce_mx_plan* p, int divisor, uint32_t step,
+                                          void* stream) {
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (p->kind != byteps_reduce_mx_plan::kRhtFold)
+    return fail(BYTEPS_REDUCE_EARGS, "rotated fold launch on a plan of another kind");
+  if (divisor < 1) return fail(BYTEPS_REDUCE_EARGS, "divisor %d < 1", divisor);
+  const MxRhtFold a{static_cast<const MxRec*>(p->table),
+                    static_cast<const MxSrSeg*>(p->side),
+                    static_cast<const unsigned char* const*>(p->rows),
+                    p->nrecs,
+                    p->nsrc,
+                    divisor,
+                    step};
+  const hipError_t e = launch_mx_rht_fold(a, p->bits, p->nelem * 4,
+                                          launch_tuning_for_n(kMxMaxSrcs), stream_of(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx rht fold kernel launch");
 }
 
 int byteps_reduce_mx_plan_destroy(byteps_reduce_mx_plan* p) {

@@ -81,4 +81,38 @@ hipError_t launch_mx_compress(const MxCompress& p, uint32_t bits, uint64_t resid
 hipError_t launch_mx_fold(const MxFold& p, uint32_t bits, uint64_t out_bytes, const Tuning& tu,
                           hipStream_t s);
 
+// The stateless wires (byteps_reduce_mx_sr_*, byteps_reduce_mx_rht_fold_*,
+// DESIGN.md §11.15; the definition is prophet_amd/mx_sr.py; the kernels are
+// bpsr_k_mx_sr.hip).  Records are MxRec with `b` null; a segment carries the key
+// its elements round under and the key its whole blocks are rotated under.
+struct MxSrSeg {
+  unsigned char* payload;  // compress; unused by the rotated fold
+  uint64_t nelem;
+  uint32_t key, rot_key;
+  uint32_t pad[2];
+};
+static_assert(sizeof(MxSrSeg) == 32, "MxSrSeg layout");
+
+struct MxSrCompress {
+  const MxRec* recs;
+  const MxSrSeg* segs;
+  uint32_t nrecs;
+  uint32_t step;
+};
+
+struct MxRhtFold {
+  const MxRec* recs;
+  const MxSrSeg* segs;
+  const unsigned char* const* srcs;  // as MxFold::srcs
+  uint32_t nrecs;
+  int nsrc;
+  int divisor;
+  uint32_t step;
+};
+
+hipError_t launch_mx_sr_compress(const MxSrCompress& p, uint32_t bits, bool rotate,
+                                 hipStream_t s);
+hipError_t launch_mx_rht_fold(const MxRhtFold& p, uint32_t bits, uint64_t out_bytes,
+                              const Tuning& tu, hipStream_t s);
+
 }  // namespace bpsr

@@ -79,6 +79,8 @@ EXPORTS = (
     "byteps_reduce_mx_payload_bytes", "byteps_reduce_mx_plan_create",
     "byteps_reduce_mx_plan_compress", "byteps_reduce_mx_fold_plan_create",
     "byteps_reduce_mx_fold_plan_launch", "byteps_reduce_mx_plan_destroy",
+    "byteps_reduce_mx_sr_plan_create", "byteps_reduce_mx_sr_plan_compress",
+    "byteps_reduce_mx_rht_fold_plan_create", "byteps_reduce_mx_rht_fold_plan_launch",
     "byteps_reduce_powersgd_scratch_bytes", "byteps_reduce_powersgd_plan_create",
     "byteps_reduce_powersgd_plan_project_p", "byteps_reduce_powersgd_plan_orthogonalize",
     "byteps_reduce_powersgd_plan_project_q", "byteps_reduce_powersgd_plan_finish",
@@ -154,6 +156,18 @@ class MXDesc(ctypes.Structure):
 class MXFoldDesc(ctypes.Structure):
     """``byteps_mx_fold_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64)]
+
+
+class MXSRDesc(ctypes.Structure):
+    """``byteps_mx_sr_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("grad", _vp), ("payload", _vp), ("nelem", ctypes.c_uint64),
+                ("key", ctypes.c_uint32), ("rot_key", ctypes.c_uint32)]
+
+
+class MXRHTFoldDesc(ctypes.Structure):
+    """``byteps_mx_rht_fold_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64),
+                ("rot_key", ctypes.c_uint32)]
 
 
 class PowerSGDDesc(ctypes.Structure):
@@ -278,6 +292,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                     ctypes.POINTER(_vp)]
     L.byteps_reduce_mx_fold_plan_launch.argtypes = [_vp, _int, _vp]
     L.byteps_reduce_mx_plan_destroy.argtypes = [_vp]
+    L.byteps_reduce_mx_sr_plan_create.argtypes = [ctypes.POINTER(MXSRDesc), _int, _int, _int,
+                                                  ctypes.POINTER(_vp)]
+    L.byteps_reduce_mx_sr_plan_compress.argtypes = [_vp, ctypes.c_uint32, _vp]
+    L.byteps_reduce_mx_rht_fold_plan_create.argtypes = [ctypes.POINTER(MXRHTFoldDesc), _int, _int,
+                                                        _int, ctypes.POINTER(_vp)]
+    L.byteps_reduce_mx_rht_fold_plan_launch.argtypes = [_vp, _int, ctypes.c_uint32, _vp]
     L.byteps_reduce_powersgd_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, _int]
     L.byteps_reduce_powersgd_scratch_bytes.restype = ctypes.c_uint64
     L.byteps_reduce_powersgd_plan_create.argtypes = [ctypes.POINTER(PowerSGDDesc), _int, _int,
@@ -516,6 +536,24 @@ class GpuReducer:
         payloads each, added in that order.  :meth:`MXFoldPlan.launch` is ONE
         launch: ``prophet_amd.mx.fold`` byte for byte."""
         return MXFoldPlan(self.lib, segments, nsrc, fmt)
+
+    def mx_sr_plan(self, segments: Sequence[tuple], fmt: str, rotate: bool = False) -> "MXSRPlan":
+        """The stateless block-scaled compress of a whole iteration
+        (byteps_reduce_mx_sr_plan_create): ``segments`` are ``(grad, payload,
+        nelem, key, rot_key)`` — a float32 tensor, a uint8 payload of
+        ``mx.payload_bytes(nelem, fmt)`` bytes, 16-byte aligned, the key its
+        elements round under and the key its blocks are rotated under (read
+        only where ``rotate``).  :meth:`MXSRPlan.compress` is ONE launch, byte
+        for byte ``prophet_amd.mx_sr.compress``."""
+        return MXSRPlan(self.lib, segments, fmt, rotate)
+
+    def mx_rht_fold_plan(self, segments: Sequence[tuple], nsrc: int,
+                         fmt: str) -> "MXRHTFoldPlan":
+        """The N-way decode-and-sum of rotated payloads
+        (byteps_reduce_mx_rht_fold_plan_create): ``segments`` are ``(out,
+        payloads, nelem, rot_key)``.  :meth:`MXRHTFoldPlan.launch` is ONE
+        launch: ``prophet_amd.mx_sr.fold`` byte for byte."""
+        return MXRHTFoldPlan(self.lib, segments, nsrc, fmt)
 
     def powersgd_plan(self, segments: Sequence[tuple], rank: int) -> "PowerSGDPlan":
         """PowerSGD low-rank compression of a whole iteration
@@ -1190,6 +1228,74 @@ class MXFoldPlan(_MXPlanBase):
         """One launch (byteps_reduce_mx_fold_plan_launch)."""
         _check(self.lib.byteps_reduce_mx_fold_plan_launch(self.handle, int(divisor),
                                                           _stream_of(self.first, stream)))
+
+
+class MXSRPlan(_MXPlanBase):
+    """A stateless block-scaled compress plan
+    (``byteps_reduce_mx_sr_plan_create``).  Tensor operands are bounds-checked
+    before the library sees them."""
+
+    def __init__(self, lib, segments, fmt, rotate=False):
+        from .mx import payload_bytes
+        super().__init__(lib, fmt)
+        self.rotate = bool(rotate)
+        segments = [tuple(s) for s in segments]
+        for s in segments:
+            if len(s) != 5:
+                raise ValueError(f"mx sr plan: a segment of {len(s)} items")
+            if int(s[2]) < 0:
+                raise ValueError(f"negative element count {s[2]}")
+            _fits(int(s[2]) * 4, s[0])
+            _fits(payload_bytes(s[2], fmt), s[1])
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (MXSRDesc * max(1, len(segments)))()
+        for d, s in zip(descs, segments):
+            d.grad, d.payload, d.nelem = _ptr(s[0]), _ptr(s[1]), int(s[2])
+            d.key, d.rot_key = int(s[3]) & 0xffffffff, int(s[4]) & 0xffffffff
+        _check(lib.byteps_reduce_mx_sr_plan_create(descs, len(segments), self.bits,
+                                                   int(self.rotate), ctypes.byref(self.handle)))
+
+    def compress(self, step: int, stream=None) -> None:
+        """One launch (byteps_reduce_mx_sr_plan_compress)."""
+        _check(self.lib.byteps_reduce_mx_sr_plan_compress(self.handle, int(step) & 0xffffffff,
+                                                          _stream_of(self.first, stream)))
+
+
+class MXRHTFoldPlan(_MXPlanBase):
+    """A rotated block-scaled fold plan
+    (``byteps_reduce_mx_rht_fold_plan_create``)."""
+
+    def __init__(self, lib, segments, nsrc, fmt):
+        from .mx import payload_bytes
+        super().__init__(lib, fmt)
+        self.nsrc = int(nsrc)
+        segments = [(s[0], list(s[1]), int(s[2]), int(s[3]) & 0xffffffff) for s in segments]
+        for out, payloads, nelem, _ in segments:
+            if nelem < 0:
+                raise ValueError(f"negative element count {nelem}")
+            if len(payloads) != self.nsrc:
+                raise ValueError(f"mx rht fold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
+            _fits(nelem * 4, out)
+            _fits(payload_bytes(nelem, fmt), *payloads)
+        self._keep = segments
+        self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
+        self.nsegs = len(segments)
+        descs = (MXRHTFoldDesc * max(1, len(segments)))()
+        rows = []                     # alive through the create call, which copies them
+        for d, (out, payloads, nelem, rot_key) in zip(descs, segments):
+            row = (_vp * max(1, len(payloads)))(*[_ptr(p) for p in payloads])
+            rows.append(row)
+            d.out, d.payloads = _ptr(out), ctypes.cast(row, ctypes.POINTER(_vp))
+            d.nelem, d.rot_key = nelem, rot_key
+        _check(lib.byteps_reduce_mx_rht_fold_plan_create(descs, len(segments), self.nsrc,
+                                                         self.bits, ctypes.byref(self.handle)))
+
+    def launch(self, divisor: int = 1, step: int = 0, stream=None) -> None:
+        """One launch (byteps_reduce_mx_rht_fold_plan_launch)."""
+        _check(self.lib.byteps_reduce_mx_rht_fold_plan_launch(
+            self.handle, int(divisor), int(step) & 0xffffffff, _stream_of(self.first, stream)))
 
 
 class PowerSGDPlan(_OneBitPlanBase):

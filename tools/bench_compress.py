@@ -251,6 +251,13 @@ def main() -> int:
                         "multiply, subtract per tensor and against the fp16_ef cast plan, and "
                         "the 8-source fold against eight widen-multiply-add steps on "
                         "pre-unpacked codes; the ResNet-50 table and one segment")
+    p.add_argument("--mx-sr", action="store_true",
+                   help="stateless block-scaled wires, fp8 and fp4, rotated and not: the "
+                        "one-launch compress against the mx*_ef compress of the same tensors "
+                        "and against torch's block amax, scale, random add and shift (after a "
+                        "sign flip and a 32 x 32 Hadamard matmul where rotated), and the "
+                        "8-source rotated fold against the mx fold; the ResNet-50 table and one "
+                        "segment")
     p.add_argument("--powersgd", action="store_true",
                    help="PowerSGD at rank 4: the four phases and their sum against torch's add, "
                         "matmul, linalg.qr, matmul, mm and sub per tensor; the ResNet-50 table's "
@@ -260,6 +267,8 @@ def main() -> int:
         return powersgd_mode(args)
     if args.mx:
         return mx_mode(args)
+    if args.mx_sr:
+        return mx_sr_mode(args)
     if args.topk:
         return topk_mode(args)
     if args.onebit_refold:
@@ -1812,6 +1821,180 @@ def mx_mode(args) -> int:
         torch.cuda.empty_cache()
         out[f"big_{fmt}"] = shape(f"big_{fmt}", fmt, [(0, args.elems)], args.elems)
         torch.cuda.empty_cache()
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    return 0 if all(gates.values()) and all(v for c in checks.values() for v in c.values()) else 1
+
+
+def mx_sr_mode(args) -> int:
+    """The stateless block-scaled wires, the --mx protocol:
+    fp8 and fp4, rotated and not.  The compress against the mx*_ef compress of
+    the same tensors in the same run (4 + bits / 8 + 1 / 32 bytes an element
+    against 12 + ...) and against torch's composition per tensor on tensors
+    padded to whole blocks ahead of time — integer-key amax, the bumped scale,
+    multiply, random 16 bits added to the magnitude's bits, shift, cast to
+    uint8 (the normal-range path only, torch.randint for the bits), after a
+    sign flip and a matmul with the 32 x 32 Hadamard matrix where rotated: all
+    of which favours torch.  The 8-source rotated fold against the mx fold of
+    the same payloads, which moves the same bytes.  Before timing, ours is
+    compared with prophet_amd/mx_sr.py byte for byte: payloads and folds."""
+    import numpy as np
+    import torch
+
+    from prophet_amd import mx, mx_sr
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    NSRC, STEP = 8, 3
+    out = {"tool": "bench_compress", "mode": "mxfp8/4_sr and _rht_sr compress and fold",
+           "nsrc": NSRC, "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+    had = torch.tensor([[(-1.0) ** bin(i & j).count("1") for j in range(32)] for i in range(32)],
+                       device=dev)
+
+    def shape(label, fmt, rot, seg_rows, arena_elems):
+        bits, emax, _, mbits, bias = mx._FORMATS[fmt]
+        mant = 0x600000 if fmt == "fp8" else 0x400000
+        nelem, counts = sum(n for _, n in seg_rows), [n for _, n in seg_rows]
+        cut = lambda t: [t[o:o + n] for o, n in seg_rows]      # noqa: E731
+        pay_off, pad_off, at, pat = [], [], 0, 0
+        for n in counts:
+            pay_off.append(at)
+            pad_off.append(pat)
+            at += mx.payload_bytes(n, fmt)
+            pat += -(-n // 32) * 32
+        pcut = lambda t: [t[o:o + mx.payload_bytes(n, fmt)]    # noqa: E731
+                          for o, n in zip(pay_off, counts)]
+        padcut = lambda t: [t[o:o + -(-n // 32) * 32].view(-1, 32)   # noqa: E731
+                            for o, n in zip(pad_off, counts)]
+        keys = [(1000 + i, 77 + i) for i in range(len(counts))]
+
+        with step(f"setup, {label}", 300):
+            g = torch.Generator(device=dev).manual_seed(13)
+            sets = []
+            for _ in range(args.sets):
+                s = {"g": torch.randn(arena_elems, device=dev, generator=g),
+                     "r": torch.zeros(arena_elems, device=dev),
+                     "out": torch.empty(arena_elems, device=dev),
+                     "gt": torch.zeros(pat, device=dev),
+                     "qt": torch.empty(pat, dtype=torch.uint8, device=dev),
+                     "sign": torch.randint(0, 2, (pat,), device=dev, generator=g).float() * 2 - 1,
+                     "payc": torch.empty(at, dtype=torch.uint8, device=dev),
+                     "paye": torch.empty(at, dtype=torch.uint8, device=dev),
+                     "pay": [torch.empty(at, dtype=torch.uint8, device=dev) for _ in range(NSRC)]}
+                for a, b in zip(padcut(s["gt"]), cut(s["g"])):
+                    a.view(-1)[:b.numel()].copy_(b)
+                s["comp"] = red.mx_sr_plan([(w, p, n, k, rk) for w, p, n, (k, rk) in
+                                            zip(cut(s["g"]), pcut(s["payc"]), counts, keys)],
+                                           fmt, rot)
+                s["ef"] = red.mx_plan(list(zip(cut(s["g"]), cut(s["r"]), pcut(s["paye"]), counts)),
+                                      fmt)
+                for j in range(NSRC):                # the fold's sources: NSRC other gradients
+                    gj = torch.randn(arena_elems, device=dev, generator=g) * (j + 1)
+                    pl = red.mx_sr_plan([(w, p, n, k + j, rk) for w, p, n, (k, rk) in
+                                         zip(cut(gj), pcut(s["pay"][j]), counts, keys)], fmt, rot)
+                    pl.compress(STEP)
+                    pl.close()
+                    del gj
+                srcs = [(o, [pcut(s["pay"][j])[i] for j in range(NSRC)], n)
+                        for i, (o, n) in enumerate(zip(cut(s["out"]), counts))]
+                s["mxfold"] = red.mx_fold_plan(srcs, NSRC, fmt)
+                s["fold"] = red.mx_rht_fold_plan(
+                    [(o, ps, n, rk) for (o, ps, n), (_, rk) in zip(srcs, keys)], NSRC, fmt) \
+                    if rot else s["mxfold"]
+                sets.append(s)
+            torch.cuda.synchronize()
+
+        def compress(i):
+            sets[i]["comp"].compress(STEP)
+
+        def mx_ef(i):
+            sets[i]["ef"].compress()
+
+        def torch_compress(i):
+            s = sets[i]
+            for gb, sb, qb in zip(padcut(s["gt"]), padcut(s["sign"]), padcut(s["qt"])):
+                c = torch.mm(gb * sb, had) if rot else gb
+                K = (c.view(torch.int32) & 0x7fffffff).amax(1)
+                X = ((K >> 23) - emax + ((K & 0x7fffff) > mant)).clamp_(0)
+                v = (c * ((254 - X) << 23).view(torch.float32)[:, None]).view(torch.int32)
+                t = ((v & 0x7fffffff) >> (7 - mbits)) - (((127 - bias) << mbits) << 16)
+                t = (t + torch.randint(0, 65536, t.shape, device=dev, dtype=torch.int32)) >> 16
+                torch.bitwise_or(t.clamp_(0), (v >> 31) & (1 << (bits - 1)), out=t)
+                qb.copy_(t)
+
+        def fold(i):
+            if rot:
+                sets[i]["fold"].launch(1, STEP)
+            else:
+                sets[i]["fold"].launch(1)
+
+        def mx_fold(i):
+            sets[i]["mxfold"].launch(1)
+
+        with step(f"check, {label}", 1500):
+            s = sets[0]
+            torch_compress(0)
+            compress(0)
+            fold(0)
+            torch.cuda.synchronize()
+            gh, ph, oh = s["g"].cpu().numpy(), s["payc"].cpu().numpy(), s["out"].cpu().numpy()
+            srch = [x.cpu().numpy() for x in s["pay"]]
+            def_ok = fold_ok = True
+            for (o, n), po, (k, rk) in zip(seg_rows, pay_off, keys):
+                nb = mx.payload_bytes(n, fmt)
+                def_ok = def_ok and np.array_equal(
+                    ph[po:po + nb], mx_sr.compress(gh[o:o + n], fmt, k, STEP, rot, rk))
+                fold_ok = fold_ok and np.array_equal(
+                    oh[o:o + n].view(np.uint32),
+                    mx_sr.fold([x[po:po + nb] for x in srch], n, fmt, 1, rot, rk, STEP)
+                    .view(np.uint32))
+            checks[label] = {"compress_equals_definition": bool(def_ok),
+                             "fold_equals_definition": bool(fold_ok)}
+            del gh, ph, oh, srch
+        cands = {"compress": (compress, args.inner), "mx_ef_compress": (mx_ef, args.inner),
+                 "torch_compress": (torch_compress, args.inner), "fold": (fold, args.inner)}
+        if rot:
+            cands["mx_fold"] = (mx_fold, args.inner)
+        res = timed_rounds(torch, cands, len(sets), args)
+        wire = bits / 8 + 1 / 32
+        for name, per in (("compress", 4 + wire), ("mx_ef_compress", 12 + wire),
+                          ("fold", 4 + NSRC * wire)):
+            res[name]["bytes_per_elem"] = round(per, 4)
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        res["compress"]["ratio_to_mx_ef"] = round(res["compress"]["ms"]
+                                                  / res["mx_ef_compress"]["ms"], 4)
+        sp = max(res["compress"]["spread_ms"], res["torch_compress"]["spread_ms"])
+        gates[f"{label}_compress_beats_torch"] = \
+            res["torch_compress"]["ms"] - res["compress"]["ms"] > sp
+        for s in sets:
+            for name in ("comp", "ef", "mxfold") + (("fold",) if rot else ()):
+                s[name].close()
+        return {"segments": len(seg_rows), "elems": nelem, "results": res}
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    total_bytes, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    for fmt in ("fp8", "fp4"):
+        for rot in (False, True):
+            tag = fmt + ("_rht" if rot else "")
+            out[f"iteration_{tag}"] = shape(f"table_{tag}", fmt, rot,
+                                            [(o // 2, ln // 2) for o, ln in rows],
+                                            total_bytes // 2)
+            torch.cuda.empty_cache()
+            out[f"big_{tag}"] = shape(f"big_{tag}", fmt, rot, [(0, args.elems)], args.elems)
+            torch.cuda.empty_cache()
     out.update({"checks": checks, "gates": gates})
     line = json.dumps(out)
     print(line, flush=True)
