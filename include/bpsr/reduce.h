@@ -93,7 +93,9 @@ extern "C" {
  *                       wires stateless, stochastically rounded, optionally
  *                       rotated)
  *    additive, still 5: byteps_reduce_powersgd_* (byteps_powersgd_desc: PowerSGD
- *                       low-rank compression with error feedback) */
+ *                       low-rank compression with error feedback)
+ *    additive, still 5: byteps_reduce_mx_*_plan_create_typed (the block-scaled
+ *                       wires over FLOAT16 and BFLOAT16 tensors) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -904,6 +906,35 @@ int byteps_reduce_mx_rht_fold_plan_create(const byteps_mx_rht_fold_desc* segs, i
                                           int nsrc, int bits, byteps_reduce_mx_plan** out);
 int byteps_reduce_mx_rht_fold_plan_launch(byteps_reduce_mx_plan* plan, int divisor,
                                           uint32_t step, void* stream);
+
+/* The block-scaled wires over 2-byte tensors.  The _typed
+ * creates are the four creates above with the element type of every segment's
+ * gradient (compress) or output (fold): FLOAT32 — the plan the untyped create
+ * makes — FLOAT16 or BFLOAT16.  They return the same byteps_reduce_mx_plan, run
+ * by the same _compress / _launch calls and freed by _plan_destroy; ONE launch
+ * each, no scratch memory.
+ *
+ * A 2-byte gradient is widened exactly to FLOAT32 and compressed as above: the
+ * payload is, byte for byte, the one its FLOAT32 upcast gives, so workers of
+ * different element types share a round and every fold reads every payload.
+ * The residual stays FLOAT32 (c = f32(g) + r is one IEEE add).  A fold into a
+ * 2-byte output computes the FLOAT32 result above — the sum in argument order,
+ * the rotation undone, the divide — and converts it once as
+ * byteps_reduce_compress does: nearest, ties to even, overflow to infinity,
+ * subnormals kept, a NaN in that function's bits.
+ *
+ * EDTYPE for any other dtype.  EARGS as above, with a 2-byte gradient or output
+ * 2-byte aligned (the residual 4-byte, a payload 16-byte) and the overlap test
+ * over the operands' real byte sizes. */
+int byteps_reduce_mx_plan_create_typed(const byteps_mx_desc* segs, int nsegs, int bits,
+                                       int dtype, byteps_reduce_mx_plan** out);
+int byteps_reduce_mx_fold_plan_create_typed(const byteps_mx_fold_desc* segs, int nsegs, int nsrc,
+                                            int bits, int dtype, byteps_reduce_mx_plan** out);
+int byteps_reduce_mx_sr_plan_create_typed(const byteps_mx_sr_desc* segs, int nsegs, int bits,
+                                          int rotate, int dtype, byteps_reduce_mx_plan** out);
+int byteps_reduce_mx_rht_fold_plan_create_typed(const byteps_mx_rht_fold_desc* segs, int nsegs,
+                                                int nsrc, int bits, int dtype,
+                                                byteps_reduce_mx_plan** out);
 
 /* PowerSGD low-rank compression with error feedback (the
  * definition is prophet_amd/powersgd.py).  A segment is one row-major n x m

@@ -161,6 +161,12 @@ block by a random-sign Hadamard transform first, under a key all workers share,
 and undo it once in the fold.  ``compress_many_sr_into`` and ``fold_many_into``
 are ONE launch per device each; ``Worker.init_tensor`` refuses all four.
 
+All six block-scaled wires take float16 and bfloat16 tensors as well as float32
+(DESIGN.md §11.16): a half gradient gives the payload of its exact float32
+upcast, the residual stays float32, and ``fold_many_into`` writes float32,
+float16 or bfloat16 outputs, converting its float32 result once.  Segments are
+grouped by device and dtype, ONE launch a group.
+
 ``Compression.powersgd_ef`` is the low-rank wire: a float32
 tensor of two or more dimensions is an n x m matrix and travels as ``P`` (n x r)
 and ``Q`` (m x r), ``(n + m) r`` floats, with error feedback and a warm-started
@@ -405,38 +411,42 @@ class CastPlanCache:
             + tuple(int(p.data_ptr()) for p in ps) for o, ps in segs)
         return self._get(key, lambda: _new_topk_fold_plan(segs, nsrc))
 
-    def get_mx(self, segs, fmt: str):
+    def get_mx(self, segs, fmt: str, dtype: int = 0):
         """The block-scaled compress plan (``GpuReducer.mx_plan``) over ``segs``
-        of flat ``(grad, resid, payload)`` device tensors on the current device."""
-        key = ("mx", fmt) + tuple(
+        of flat ``(grad, resid, payload)`` device tensors on the current device,
+        the gradients of ``dtype`` (a DType id; float32 unless named)."""
+        key = ("mx", fmt, int(dtype)) + tuple(
             (int(g.data_ptr()), int(r.data_ptr()), int(p.data_ptr()), int(g.numel()))
             for g, r, p in segs)
-        return self._get(key, lambda: _new_mx_plan(segs, fmt))
+        return self._get(key, lambda: _new_mx_plan(segs, fmt, dtype))
 
-    def get_mx_fold(self, segs, nsrc: int, fmt: str):
+    def get_mx_fold(self, segs, nsrc: int, fmt: str, dtype: int = 0):
         """The block-scaled fold plan (``GpuReducer.mx_fold_plan``) over ``segs``
-        of ``(out, payloads)`` device tensors on the current device."""
-        key = ("mx_fold", fmt, int(nsrc)) + tuple(
+        of ``(out, payloads)`` device tensors on the current device, the
+        outputs of ``dtype``."""
+        key = ("mx_fold", fmt, int(nsrc), int(dtype)) + tuple(
             (int(o.data_ptr()), int(o.numel())) + tuple(int(p.data_ptr()) for p in ps)
             for o, ps in segs)
-        return self._get(key, lambda: _new_mx_fold_plan(segs, nsrc, fmt))
+        return self._get(key, lambda: _new_mx_fold_plan(segs, nsrc, fmt, dtype))
 
-    def get_mx_sr(self, segs, fmt: str, rotate: bool = False):
+    def get_mx_sr(self, segs, fmt: str, rotate: bool = False, dtype: int = 0):
         """The stateless block-scaled compress plan (``GpuReducer.mx_sr_plan``)
         over ``segs`` of flat ``(grad, payload, key, rot_key)`` device tensors
-        and keys on the current device: another key misses."""
-        key = ("mx_sr", fmt, bool(rotate)) + tuple(
+        and keys on the current device, the gradients of ``dtype``: another key
+        misses."""
+        key = ("mx_sr", fmt, bool(rotate), int(dtype)) + tuple(
             (int(g.data_ptr()), int(p.data_ptr()), int(g.numel()), int(k), int(rk))
             for g, p, k, rk in segs)
-        return self._get(key, lambda: _new_mx_sr_plan(segs, fmt, rotate))
+        return self._get(key, lambda: _new_mx_sr_plan(segs, fmt, rotate, dtype))
 
-    def get_mx_rht_fold(self, segs, nsrc: int, fmt: str):
+    def get_mx_rht_fold(self, segs, nsrc: int, fmt: str, dtype: int = 0):
         """The rotated block-scaled fold plan (``GpuReducer.mx_rht_fold_plan``)
-        over ``segs`` of ``(out, payloads, rot_key)`` on the current device."""
-        key = ("mx_rht_fold", fmt, int(nsrc)) + tuple(
+        over ``segs`` of ``(out, payloads, rot_key)`` on the current device,
+        the outputs of ``dtype``."""
+        key = ("mx_rht_fold", fmt, int(nsrc), int(dtype)) + tuple(
             (int(o.data_ptr()), int(o.numel()), int(rk)) + tuple(int(p.data_ptr()) for p in ps)
             for o, ps, rk in segs)
-        return self._get(key, lambda: _new_mx_rht_fold_plan(segs, nsrc, fmt))
+        return self._get(key, lambda: _new_mx_rht_fold_plan(segs, nsrc, fmt, dtype))
 
     def get_powersgd(self, segs, rank: int):
         """The PowerSGD plan (``GpuReducer.powersgd_plan``) over ``segs`` of
@@ -457,24 +467,26 @@ def _new_powersgd_plan(segs, rank: int):
     return _red().powersgd_plan(segs, rank)
 
 
-def _new_mx_plan(segs, fmt: str):
+def _new_mx_plan(segs, fmt: str, dtype: int = 0):
     from .torch_ops import _red
-    return _red().mx_plan([(g, r, p, int(g.numel())) for g, r, p in segs], fmt)
+    return _red().mx_plan([(g, r, p, int(g.numel())) for g, r, p in segs], fmt, dtype)
 
 
-def _new_mx_fold_plan(segs, nsrc: int, fmt: str):
+def _new_mx_fold_plan(segs, nsrc: int, fmt: str, dtype: int = 0):
     from .torch_ops import _red
-    return _red().mx_fold_plan([(o, ps, int(o.numel())) for o, ps in segs], nsrc, fmt)
+    return _red().mx_fold_plan([(o, ps, int(o.numel())) for o, ps in segs], nsrc, fmt, dtype)
 
 
-def _new_mx_sr_plan(segs, fmt: str, rotate: bool):
+def _new_mx_sr_plan(segs, fmt: str, rotate: bool, dtype: int = 0):
     from .torch_ops import _red
-    return _red().mx_sr_plan([(g, p, int(g.numel()), k, rk) for g, p, k, rk in segs], fmt, rotate)
+    return _red().mx_sr_plan([(g, p, int(g.numel()), k, rk) for g, p, k, rk in segs], fmt, rotate,
+                             dtype)
 
 
-def _new_mx_rht_fold_plan(segs, nsrc: int, fmt: str):
+def _new_mx_rht_fold_plan(segs, nsrc: int, fmt: str, dtype: int = 0):
     from .torch_ops import _red
-    return _red().mx_rht_fold_plan([(o, ps, int(o.numel()), rk) for o, ps, rk in segs], nsrc, fmt)
+    return _red().mx_rht_fold_plan([(o, ps, int(o.numel()), rk) for o, ps, rk in segs], nsrc, fmt,
+                                   dtype)
 
 
 def _new_topk_plan(segs):
@@ -1061,6 +1073,32 @@ def _is_f32(x) -> bool:
         import torch
         return x.dtype == torch.float32
     return x.dtype == np.float32
+
+
+def _mx_dtype(x):
+    """The DType id of a tensor the block-scaled wires take — float32, float16
+    or (torch) bfloat16 — else ``None``."""
+    return 0 if _is_f32(x) else 2 if _is_half(x) else 11 if _is_bf16(x) else None
+
+
+_MX_OUT = {0: None, 2: "float16", 11: "bfloat16"}     # DType id: mx.narrow's out_dtype
+
+
+def _mx_host(x):
+    """A host tensor of a block-scaled wire as the definition takes it: a flat
+    numpy view, a bf16 tensor as its uint16 bits."""
+    if _is_bf16(x):
+        import torch
+        return x.detach().view(torch.int16).numpy().view(np.uint16).reshape(-1)
+    return (x.detach().numpy() if _is_torch(x) else x).reshape(-1)
+
+
+def _run_by_dtype(groups, plans, get, launch) -> None:
+    """``OneBitEFCompressor._run`` over segments grouped by ``(device,
+    dtype)``: one plan, ``get(cache, segs, dtype)``, and one launch a group."""
+    for (device, dt), segs in groups.items():
+        OneBitEFCompressor._run({device: segs}, plans,
+                                lambda cache, s, dt=dt: get(cache, s, dt), launch)
 
 
 class _ErrorFeedback:
@@ -1658,7 +1696,11 @@ class MXFP8EFCompressor(Compressor):
     (``byteps_reduce_mx_*``, ``prophet_amd/csrc/bpsr_k_mx.hip``): a compress of
     many tensors is ONE launch per device, and so is a fold of many; CPU
     tensors and numpy arrays go through ``mx.py``, byte for byte the same.
-    Everything but float32 passes through.
+    float16 and bfloat16 tensors are compressed too, from their exact float32
+    upcast (the same payload; ``prophet_amd/csrc/bpsr_k_mx_half.hip``, DESIGN.md
+    §11.16): the residual stays float32, and a fold writes float32, float16 or
+    bfloat16 outputs, converting its float32 result once.  Everything else
+    passes through.
 
     There is no server round for these wires yet: ``Worker.init_tensor``
     refuses them over every front end.  ``fold_many_into`` is what a worker
@@ -1670,7 +1712,7 @@ class MXFP8EFCompressor(Compressor):
 
     @classmethod
     def compresses(cls, tensor) -> bool:
-        return _is_f32(tensor)
+        return _mx_dtype(tensor) is not None
 
     @classmethod
     def payload_like(cls, x):
@@ -1714,23 +1756,23 @@ class MXFP8EFCompressor(Compressor):
         name, groups = f"mx{cls.FMT}_ef", {}
         for i, (p, r, t) in enumerate(zip(payloads, residuals, tensors)):
             if not cls.compresses(t) or not _is_f32(r):
-                raise ValueError(f"{name} needs float32 tensors and float32 residuals")
+                raise ValueError(f"{name} needs float32, float16 or bfloat16 tensors and "
+                                 f"float32 residuals")
             dev = [_on_device(x) for x in (p, r, t)]
             if any(dev) != all(dev):
                 raise ValueError(f"{name}: tensor {i}'s operands live in one place, a device "
                                  f"or the host")
             if dev[0]:
                 cls._check_device_segment(i, t, r, payload=p)
-                groups.setdefault(t.device, []).append((t.reshape(-1), r.reshape(-1), p))
+                groups.setdefault((t.device, _mx_dtype(t)), []).append(
+                    (t.reshape(-1), r.reshape(-1), p))
                 continue
-            ra = (r.detach().numpy() if _is_torch(r) else r).reshape(-1)
-            ga = t.detach().numpy() if _is_torch(t) else t
-            pa = _payload_array(p)
+            ra, ga, pa = _mx_host(r), _mx_host(t), _payload_array(p)
             if ra.size != ga.size or pa.size != mx.payload_bytes(ga.size, cls.FMT):
                 raise ValueError(f"{name}: tensor {i}'s operands differ in size")
-            pa[:], ra[:] = mx.compress(ga, ra, cls.FMT)
-        OneBitEFCompressor._run(groups, plans, lambda cache, segs: cache.get_mx(segs, cls.FMT),
-                                lambda plan, stream: plan.compress(stream=stream))
+            pa[:], ra[:] = mx.compress(ga, ra, cls.FMT, _is_bf16(t))
+        _run_by_dtype(groups, plans, lambda cache, segs, dt: cache.get_mx(segs, cls.FMT, dt),
+                      lambda plan, stream: plan.compress(stream=stream))
         return payloads
 
     @classmethod
@@ -1758,8 +1800,9 @@ class MXFP8EFCompressor(Compressor):
                              f"payloads")
         name, groups = f"mx{cls.FMT}_ef", {}
         for i, (o, ps) in enumerate(zip(outs, payload_lists)):
-            if not _is_f32(o):
-                raise ValueError(f"{name}: output {i} must be float32, got {o.dtype}")
+            if _mx_dtype(o) is None:
+                raise ValueError(f"{name}: output {i} must be float32, float16 or bfloat16, "
+                                 f"got {o.dtype}")
             dev = [_on_device(x) for x in [o] + list(ps)]
             if any(dev) != all(dev):
                 raise ValueError(f"{name}: output {i} and its payloads live in one place, a "
@@ -1767,19 +1810,20 @@ class MXFP8EFCompressor(Compressor):
             if dev[0]:
                 for p in ps:
                     cls._check_device_segment(i, o, payload=p)
-                groups.setdefault(o.device, []).append((o.reshape(-1), list(ps)))
+                groups.setdefault((o.device, _mx_dtype(o)), []).append((o.reshape(-1), list(ps)))
                 continue
-            oa = (o.detach().numpy() if _is_torch(o) else o).reshape(-1)
-            oa[:] = mx.fold([_payload_array(p) for p in ps], oa.size, cls.FMT, divisor)
-        OneBitEFCompressor._run(groups, plans,
-                                lambda cache, segs: cache.get_mx_fold(segs, nsrc, cls.FMT),
-                                lambda plan, stream: plan.launch(int(divisor), stream=stream))
+            oa = _mx_host(o)
+            oa[:] = mx.fold([_payload_array(p) for p in ps], oa.size, cls.FMT, divisor,
+                            _MX_OUT[_mx_dtype(o)])
+        _run_by_dtype(groups, plans,
+                      lambda cache, segs, dt: cache.get_mx_fold(segs, nsrc, cls.FMT, dt),
+                      lambda plan, stream: plan.launch(int(divisor), stream=stream))
         return outs
 
     @classmethod
     def _check_device_segment(cls, i: int, tensor, resid=None, payload=None) -> None:
-        """One device segment: contiguous float32 operands of one size and a
-        flat uint8 payload of the payload's size, all on one device."""
+        """One device segment: contiguous operands of one size and a flat
+        uint8 payload of the payload's size, all on one device."""
         import torch
         from .mx import payload_bytes
         for x in (tensor, resid):
@@ -1801,7 +1845,7 @@ class MXFP4EFCompressor(MXFP8EFCompressor):
 
 
 class MXFP8SRCompressor(Compressor):
-    """float32 tensors travel in ``mxfp8_ef``'s blocks with no residual: a code
+    """float32, float16 and bfloat16 tensors travel in ``mxfp8_ef``'s blocks with no residual: a code
     is rounded up with a probability equal to the dropped fraction, under bits
     that are a pure function of ``(key, step, element index)``
     (``prophet_amd/mx_sr.py`` is the definition).  The
@@ -1813,7 +1857,10 @@ class MXFP8SRCompressor(Compressor):
     ``byteps_reduce_mx_rht_fold_*``, ``prophet_amd/csrc/bpsr_k_mx_sr.hip``; the
     unrotated fold is ``mxfp8_ef``'s): ONE launch per device either way; CPU
     tensors and numpy arrays go through ``mx_sr.py``, byte for byte the same.
-    Everything but float32 passes through.
+    A float16 or bfloat16 tensor gives the payload of its exact float32 upcast
+    and a fold converts its float32 result once to the output's type
+    (``prophet_amd/csrc/bpsr_k_mx_half.hip``).  Everything
+    else passes through.
 
     There is no server round for these wires: ``Worker.init_tensor`` refuses
     them over every front end."""
@@ -1872,22 +1919,22 @@ class MXFP8SRCompressor(Compressor):
         name, groups = cls._name(), {}
         for i, (p, t, k, rk) in enumerate(zip(payloads, tensors, keys, rot_keys)):
             if not cls.compresses(t):
-                raise ValueError(f"{name} needs float32 tensors")
+                raise ValueError(f"{name} needs float32, float16 or bfloat16 tensors")
             k, rk = int(k) & 0xffffffff, int(rk) & 0xffffffff
             if _on_device(p) != _on_device(t):
                 raise ValueError(f"{name}: tensor {i}'s operands live in one place, a device "
                                  f"or the host")
             if _on_device(t):
                 cls._check_device_segment(i, t, p)
-                groups.setdefault(t.device, []).append((t.reshape(-1), p, k, rk))
+                groups.setdefault((t.device, _mx_dtype(t)), []).append((t.reshape(-1), p, k, rk))
                 continue
-            ga = t.detach().numpy() if _is_torch(t) else t
-            pa = _payload_array(p)
+            ga, pa = _mx_host(t), _payload_array(p)
             if pa.size != mx.payload_bytes(ga.size, cls.FMT):
                 raise ValueError(f"{name}: tensor {i}'s operands differ in size")
-            pa[:] = mx_sr.compress(ga, cls.FMT, k, step, cls.ROTATE, rk)
-        OneBitEFCompressor._run(
-            groups, plans, lambda cache, segs: cache.get_mx_sr(segs, cls.FMT, cls.ROTATE),
+            pa[:] = mx_sr.compress(ga, cls.FMT, k, step, cls.ROTATE, rk, _is_bf16(t))
+        _run_by_dtype(
+            groups, plans,
+            lambda cache, segs, dt: cache.get_mx_sr(segs, cls.FMT, cls.ROTATE, dt),
             lambda plan, stream: plan.compress(step, stream=stream))
         return payloads
 
@@ -1923,8 +1970,9 @@ class MXFP8SRCompressor(Compressor):
                              f"payloads")
         name, groups = cls._name(), {}
         for i, (o, ps, rk) in enumerate(zip(outs, payload_lists, rot_keys)):
-            if not _is_f32(o):
-                raise ValueError(f"{name}: output {i} must be float32, got {o.dtype}")
+            if _mx_dtype(o) is None:
+                raise ValueError(f"{name}: output {i} must be float32, float16 or bfloat16, "
+                                 f"got {o.dtype}")
             dev = [_on_device(x) for x in [o] + list(ps)]
             if any(dev) != all(dev):
                 raise ValueError(f"{name}: output {i} and its payloads live in one place, a "
@@ -1933,20 +1981,22 @@ class MXFP8SRCompressor(Compressor):
             if dev[0]:
                 for p in ps:
                     cls._check_device_segment(i, o, p)
-                groups.setdefault(o.device, []).append((o.reshape(-1), list(ps), rk))
+                groups.setdefault((o.device, _mx_dtype(o)), []).append(
+                    (o.reshape(-1), list(ps), rk))
                 continue
-            oa = (o.detach().numpy() if _is_torch(o) else o).reshape(-1)
+            oa = _mx_host(o)
             oa[:] = mx_sr.fold([_payload_array(p) for p in ps], oa.size, cls.FMT, divisor, True,
-                               rk, step)
-        OneBitEFCompressor._run(
-            groups, plans, lambda cache, segs: cache.get_mx_rht_fold(segs, nsrc, cls.FMT),
+                               rk, step, _MX_OUT[_mx_dtype(o)])
+        _run_by_dtype(
+            groups, plans,
+            lambda cache, segs, dt: cache.get_mx_rht_fold(segs, nsrc, cls.FMT, dt),
             lambda plan, stream: plan.launch(int(divisor), step, stream=stream))
         return outs
 
     @classmethod
     def _check_device_segment(cls, i: int, tensor, payload=None, **_) -> None:
-        """One device segment: a contiguous float32 tensor and a flat uint8
-        payload of the payload's size on its device."""
+        """One device segment: a contiguous tensor and a flat uint8 payload of
+        the payload's size on its device."""
         import torch
         from .mx import payload_bytes
         size = payload_bytes(tensor.numel(), cls.FMT)

@@ -35,23 +35,6 @@
 
 namespace bpsr {
 
-namespace {
-
-// Four values, |v| <= max, to their codes: fp8 a dword, element e in byte e;
-// fp4 the low 16 bits, element e in nibble e.
-template <int BITS>
-__device__ __forceinline__ uint32_t encode4(const float (&v)[4]) {
-  if constexpr (BITS == 8) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
-  } else {
-    uint32_t w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(0u, v[0], v[1], 1.0f, 0);
-    return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, v[2], v[3], 1.0f, 1) & 0xffffu;
-  }
-}
-
-}  // namespace
-
 template <int BITS, int POL>
 __global__ __launch_bounds__(kBlock) void mx_compress_kernel(MxCompress p) {
   __shared__ __attribute__((aligned(16))) unsigned char sx[kMxTileBlocks];

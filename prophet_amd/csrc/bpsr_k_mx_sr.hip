@@ -35,17 +35,6 @@ namespace bpsr {
 
 namespace {
 
-template <int BITS>
-struct SrFmt;
-template <>
-struct SrFmt<8> {
-  static constexpr uint32_t kEmax = 8, kMant = 0x600000u, kMbits = 3, kBias = 7;
-};
-template <>
-struct SrFmt<4> {
-  static constexpr uint32_t kEmax = 2, kMant = 0x400000u, kMbits = 1, kBias = 1;
-};
-
 // and_mask 0x1f, or_mask 0, xor_mask 4
 constexpr int kSwizzleXor4 = (4 << 10) | 0x1f;
 
@@ -100,23 +89,6 @@ __device__ __forceinline__ void sign_words(uint32_t first_block, uint32_t lane, 
 // 0x80000000 where bit 4 (lane % 8) + e of the block's word is set.
 __device__ __forceinline__ uint32_t sign_of(uint32_t w, uint32_t lane, int e) {
   return (w >> (4 * (lane & 7) + (uint32_t)e)) << 31;
-}
-
-// The code of the f32 bits u, |u| <= max, under 16 random bits: with t the
-// magnitude in units of 2^-16 of the local step, offset so that its high part
-// is the code, (t + r16) >> 16.
-template <int BITS>
-__device__ __forceinline__ uint32_t sr_code(uint32_t u, uint32_t r16) {
-  constexpr uint32_t mb = SrFmt<BITS>::kMbits, bias = SrFmt<BITS>::kBias, drop = 23 - mb;
-  const uint32_t a = u & kKeyMask, e = a >> 23;
-  const uint32_t normal = (a >> (drop - 16)) - (((127 - bias) << mb) << 16);
-  // below the format's smallest normal: the significand shifted down
-  const uint32_t m = (a & 0x7fffffu) | (e ? 0x800000u : 0u);
-  uint32_t sh = (151 - bias - mb) - (e > 1u ? e : 1u);
-  sh = sh > 40u ? 40u : sh;
-  const uint32_t sub = (uint32_t)(((uint64_t)m << 16) >> sh);
-  const uint32_t t = e >= 128 - bias ? normal : sub;
-  return ((t + r16) >> 16) | ((u >> 31) << (BITS - 1));
 }
 
 }  // namespace

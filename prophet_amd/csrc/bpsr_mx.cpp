@@ -2,8 +2,11 @@
 // include/bpsr/reduce.h): the operand checks, the plans' tables (bpsr_mx.h) and
 // the C entry points — the error-feedback compress and the fold, and the
 // stateless wires' compress and rotated fold (byteps_reduce_mx_sr_*,
-// byteps_reduce_mx_rht_fold_*).  Every check runs before the first HIP call of
-// its entry: a refused call has touched nothing.
+// byteps_reduce_mx_rht_fold_*).  A plan carries the element type of its
+// gradients or outputs (the _typed creates): FLOAT32 runs bpsr_k_mx.hip and
+// bpsr_k_mx_sr.hip, FLOAT16 and BFLOAT16 run bpsr_k_mx_half.hip.  Every check
+// runs before the first HIP call of its entry: a refused call has touched
+// nothing.
 #include <algorithm>
 #include <cstring>
 
@@ -16,6 +19,8 @@ struct byteps_reduce_mx_plan {
   enum Kind { kCompress, kFold, kSrCompress, kRhtFold };
   Kind kind = kCompress;
   bool rotate = false;  // kSrCompress
+  // of the gradient (compress) or the output (fold): FLOAT32, FLOAT16 or BFLOAT16
+  int dtype = BYTEPS_REDUCE_FLOAT32;
   uint32_t bits = 0;
   int nsrc = 0;  // fold
   uint32_t nrecs = 0;
@@ -58,13 +63,17 @@ int check_disjoint(std::vector<Range>& ranges) {
 
 // The records of one segment: kMxTile elements each, contiguous and ascending,
 // the last one ragged; `header`: an empty segment still gets one record.
+// `esize`: the bytes of an element of `a`; `b` is f32.
 void cut(std::vector<MxRec>& recs, unsigned char* a, unsigned char* b, uint64_t nelem,
-         uint32_t seg, bool header) {
+         uint32_t seg, bool header, uint64_t esize) {
   const uintptr_t x = (uintptr_t)a | (uintptr_t)b;
-  const uint32_t flags = (x % 16 == 0 ? kMxVec : 0u) | (x % 4 == 0 ? kMxAligned : 0u);
+  const uint32_t flags =
+      esize == 4 ? (x % 16 == 0 ? kMxVec : 0u) | (x % 4 == 0 ? kMxAligned : 0u)
+                 : ((uintptr_t)a % 16 == 0 ? kMxVec : 0u) | ((uintptr_t)b % 16 == 0 ? kMxVecB : 0u) |
+                       kMxAligned;
   if (nelem == 0 && header) recs.push_back(MxRec{nullptr, nullptr, seg, 0, 0, flags});
   for (uint64_t e = 0; e < nelem; e += kMxTile)
-    recs.push_back(MxRec{a + e * 4, b ? b + e * 4 : nullptr, seg, (uint32_t)e,
+    recs.push_back(MxRec{a + e * esize, b ? b + e * 4 : nullptr, seg, (uint32_t)e,
                          (uint32_t)std::min<uint64_t>(kMxTile, nelem - e), flags});
 }
 
@@ -87,9 +96,16 @@ hipError_t plan_free(byteps_reduce_mx_plan* p) {
   return e;
 }
 
-int check_table(const void* segs, int nsegs, int bits, byteps_reduce_mx_plan** out) {
+// The bytes of an element of `dtype`, 0 for a type the wires do not take.
+uint64_t mx_elem_size(int dtype) {
+  return dtype == kFloat32 ? 4 : dtype == kFloat16 || dtype == kBFloat16 ? 2 : 0;
+}
+
+int check_table(const void* segs, int nsegs, int bits, int dtype, byteps_reduce_mx_plan** out) {
   if (!out) return fail(BYTEPS_REDUCE_EARGS, "null plan out-pointer");
   *out = nullptr;
+  if (!mx_elem_size(dtype))
+    return fail(BYTEPS_REDUCE_EDTYPE, "dtype %d: FLOAT32, FLOAT16 or BFLOAT16", dtype);
   if (nsegs < 0 || (nsegs > 0 && !segs)) return fail(BYTEPS_REDUCE_EARGS, "bad segment table");
   if (bits != 8 && bits != 4)
     return fail(BYTEPS_REDUCE_EARGS, "element bits %d: 8 (e4m3) or 4 (e2m1)", bits);
@@ -120,7 +136,13 @@ uint64_t byteps_reduce_mx_payload_bytes(uint64_t nelem, int bits) {
 
 int byteps_reduce_mx_plan_create(const byteps_mx_desc* segs, int nsegs, int bits,
                                  byteps_reduce_mx_plan** out) {
-  if (int rc = check_table(segs, nsegs, bits, out)) return rc;
+  return byteps_reduce_mx_plan_create_typed(segs, nsegs, bits, BYTEPS_REDUCE_FLOAT32, out);
+}
+
+int byteps_reduce_mx_plan_create_typed(const byteps_mx_desc* segs, int nsegs, int bits,
+                                       int dtype, byteps_reduce_mx_plan** out) {
+  if (int rc = check_table(segs, nsegs, bits, dtype, out)) return rc;
+  const uint64_t es = mx_elem_size(dtype);
   std::vector<MxRec> recs;
   std::vector<MxSeg> stab((size_t)nsegs);
   std::vector<Range> ranges;
@@ -128,24 +150,25 @@ int byteps_reduce_mx_plan_create(const byteps_mx_desc* segs, int nsegs, int bits
   for (int i = 0; i < nsegs; ++i) {
     const byteps_mx_desc& d = segs[i];
     if (int rc = check_operand(d.nelem, d.payload, 16, "payload", i)) return rc;
-    if (int rc = check_operand(d.nelem, d.grad, 4, "gradient", i)) return rc;
+    if (int rc = check_operand(d.nelem, d.grad, (unsigned)es, "gradient", i)) return rc;
     if (int rc = check_operand(d.nelem, d.resid, 4, "residual", i)) return rc;
     if (d.nelem > 0 && (!d.grad || !d.resid || !d.payload))
       return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
     // an empty segment still gets its header where it names a payload
     bool ok = !d.payload ||
               add_range(ranges, d.payload, mx_payload_bytes(d.nelem, (uint32_t)bits), i);
-    ok = ok && add_range(ranges, d.grad, d.nelem * 4, i) &&
+    ok = ok && add_range(ranges, d.grad, d.nelem * es, i) &&
          add_range(ranges, d.resid, d.nelem * 4, i);
     if (!ok) return fail(BYTEPS_REDUCE_EARGS, "segment %d: operand wraps the address space", i);
     cut(recs, static_cast<unsigned char*>(const_cast<void*>(d.grad)),
-        static_cast<unsigned char*>(d.resid), d.nelem, (uint32_t)i, d.payload != nullptr);
+        static_cast<unsigned char*>(d.resid), d.nelem, (uint32_t)i, d.payload != nullptr, es);
     stab[(size_t)i] = MxSeg{static_cast<unsigned char*>(d.payload), d.nelem};
     total += d.nelem;
     if (recs.size() >= (1ull << 31)) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
   }
   if (int rc = check_disjoint(ranges)) return rc;
   auto* p = new byteps_reduce_mx_plan();
+  p->dtype = dtype;
   p->bits = (uint32_t)bits;
   p->nrecs = (uint32_t)recs.size();
   p->nelem = total;
@@ -166,14 +189,24 @@ int byteps_reduce_mx_plan_compress(byteps_reduce_mx_plan* p, void* stream) {
   const MxCompress a{static_cast<const MxRec*>(p->table), static_cast<const MxSeg*>(p->side),
                      p->nrecs};
   // more than 4 sources: the process-wide tuning as it stands
-  const hipError_t e = launch_mx_compress(a, p->bits, p->nelem * 4,
-                                          launch_tuning_for_n(kMxMaxSrcs), stream_of(stream));
+  const Tuning tu = launch_tuning_for_n(kMxMaxSrcs);
+  const hipError_t e =
+      p->dtype == kFloat32
+          ? launch_mx_compress(a, p->bits, p->nelem * 4, tu, stream_of(stream))
+          : launch_mx_half_compress(a, p->dtype, p->bits, p->nelem * 4, tu, stream_of(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx compress kernel launch");
 }
 
 int byteps_reduce_mx_fold_plan_create(const byteps_mx_fold_desc* segs, int nsegs, int nsrc,
                                       int bits, byteps_reduce_mx_plan** out) {
-  if (int rc = check_table(segs, nsegs, bits, out)) return rc;
+  return byteps_reduce_mx_fold_plan_create_typed(segs, nsegs, nsrc, bits, BYTEPS_REDUCE_FLOAT32,
+                                                 out);
+}
+
+int byteps_reduce_mx_fold_plan_create_typed(const byteps_mx_fold_desc* segs, int nsegs, int nsrc,
+                                            int bits, int dtype, byteps_reduce_mx_plan** out) {
+  if (int rc = check_table(segs, nsegs, bits, dtype, out)) return rc;
+  const uint64_t es = mx_elem_size(dtype);
   if (nsrc < 1 || nsrc > kMxMaxSrcs)
     return fail(BYTEPS_REDUCE_EARGS, "nsrc %d outside 1..%d", nsrc, kMxMaxSrcs);
   std::vector<MxRec> recs;
@@ -183,11 +216,11 @@ int byteps_reduce_mx_fold_plan_create(const byteps_mx_fold_desc* segs, int nsegs
   uint64_t total = 0;
   for (int i = 0; i < nsegs; ++i) {
     const byteps_mx_fold_desc& d = segs[i];
-    if (int rc = check_operand(d.nelem, d.out, 4, "output", i)) return rc;
+    if (int rc = check_operand(d.nelem, d.out, (unsigned)es, "output", i)) return rc;
     stab[(size_t)i] = MxSeg{nullptr, d.nelem};
     if (d.nelem == 0) continue;
     if (!d.out || !d.payloads) return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
-    bool ok = add_range(ranges, d.out, d.nelem * 4, i);
+    bool ok = add_range(ranges, d.out, d.nelem * es, i);
     for (int s = 0; s < nsrc; ++s) {
       const void* pl = d.payloads[s];
       if (!pl) return fail(BYTEPS_REDUCE_EARGS, "segment %d: null payload %d", i, s);
@@ -196,13 +229,14 @@ int byteps_reduce_mx_fold_plan_create(const byteps_mx_fold_desc* segs, int nsegs
       rows[(size_t)i * (size_t)nsrc + (size_t)s] = static_cast<const unsigned char*>(pl);
     }
     if (!ok) return fail(BYTEPS_REDUCE_EARGS, "segment %d: operand wraps the address space", i);
-    cut(recs, static_cast<unsigned char*>(d.out), nullptr, d.nelem, (uint32_t)i, false);
+    cut(recs, static_cast<unsigned char*>(d.out), nullptr, d.nelem, (uint32_t)i, false, es);
     total += d.nelem;
     if (recs.size() >= (1ull << 31)) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
   }
   if (int rc = check_disjoint(ranges)) return rc;
   auto* p = new byteps_reduce_mx_plan();
   p->kind = byteps_reduce_mx_plan::kFold;
+  p->dtype = dtype;
   p->bits = (uint32_t)bits;
   p->nsrc = nsrc;
   p->nrecs = (uint32_t)recs.size();
@@ -229,14 +263,24 @@ int byteps_reduce_mx_fold_plan_launch(byteps_reduce_mx_plan* p, int divisor, voi
                  p->nrecs,
                  p->nsrc,
                  divisor};
-  const hipError_t e = launch_mx_fold(a, p->bits, p->nelem * 4, launch_tuning_for_n(kMxMaxSrcs),
-                                      stream_of(stream));
+  const Tuning tu = launch_tuning_for_n(kMxMaxSrcs);
+  const hipError_t e =
+      p->dtype == kFloat32
+          ? launch_mx_fold(a, p->bits, p->nelem * 4, tu, stream_of(stream))
+          : launch_mx_half_fold(a, p->dtype, p->bits, p->nelem * 2, tu, stream_of(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx fold kernel launch");
 }
 
 int byteps_reduce_mx_sr_plan_create(const byteps_mx_sr_desc* segs, int nsegs, int bits,
                                     int rotate, byteps_reduce_mx_plan** out) {
-  if (int rc = check_table(segs, nsegs, bits, out)) return rc;
+  return byteps_reduce_mx_sr_plan_create_typed(segs, nsegs, bits, rotate, BYTEPS_REDUCE_FLOAT32,
+                                               out);
+}
+
+int byteps_reduce_mx_sr_plan_create_typed(const byteps_mx_sr_desc* segs, int nsegs, int bits,
+                                          int rotate, int dtype, byteps_reduce_mx_plan** out) {
+  if (int rc = check_table(segs, nsegs, bits, dtype, out)) return rc;
+  const uint64_t es = mx_elem_size(dtype);
   if (rotate != 0 && rotate != 1) return fail(BYTEPS_REDUCE_EARGS, "rotate %d: 0 or 1", rotate);
   std::vector<MxRec> recs;
   std::vector<MxSrSeg> stab((size_t)nsegs);
@@ -244,16 +288,16 @@ int byteps_reduce_mx_sr_plan_create(const byteps_mx_sr_desc* segs, int nsegs, in
   for (int i = 0; i < nsegs; ++i) {
     const byteps_mx_sr_desc& d = segs[i];
     if (int rc = check_operand(d.nelem, d.payload, 16, "payload", i)) return rc;
-    if (int rc = check_operand(d.nelem, d.grad, 4, "gradient", i)) return rc;
+    if (int rc = check_operand(d.nelem, d.grad, (unsigned)es, "gradient", i)) return rc;
     if (d.nelem > 0 && (!d.grad || !d.payload))
       return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
     // an empty segment still gets its header where it names a payload
     const bool ok = (!d.payload ||
                      add_range(ranges, d.payload, mx_payload_bytes(d.nelem, (uint32_t)bits), i)) &&
-                    add_range(ranges, d.grad, d.nelem * 4, i);
+                    add_range(ranges, d.grad, d.nelem * es, i);
     if (!ok) return fail(BYTEPS_REDUCE_EARGS, "segment %d: operand wraps the address space", i);
     cut(recs, static_cast<unsigned char*>(const_cast<void*>(d.grad)), nullptr, d.nelem,
-        (uint32_t)i, d.payload != nullptr);
+        (uint32_t)i, d.payload != nullptr, es);
     stab[(size_t)i] = MxSrSeg{static_cast<unsigned char*>(d.payload), d.nelem, d.key, d.rot_key,
                               {0, 0}};
     if (recs.size() >= (1ull << 31)) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
@@ -261,6 +305,7 @@ int byteps_reduce_mx_sr_plan_create(const byteps_mx_sr_desc* segs, int nsegs, in
   if (int rc = check_disjoint(ranges)) return rc;
   auto* p = new byteps_reduce_mx_plan();
   p->kind = byteps_reduce_mx_plan::kSrCompress;
+  p->dtype = dtype;
   p->rotate = rotate == 1;
   p->bits = (uint32_t)bits;
   p->nrecs = (uint32_t)recs.size();
@@ -280,13 +325,24 @@ int byteps_reduce_mx_sr_plan_compress(byteps_reduce_mx_plan* p, uint32_t step, v
     return fail(BYTEPS_REDUCE_EARGS, "stochastic compress on a plan of another kind");
   const MxSrCompress a{static_cast<const MxRec*>(p->table), static_cast<const MxSrSeg*>(p->side),
                        p->nrecs, step};
-  const hipError_t e = launch_mx_sr_compress(a, p->bits, p->rotate, stream_of(stream));
+  const hipError_t e =
+      p->dtype == kFloat32
+          ? launch_mx_sr_compress(a, p->bits, p->rotate, stream_of(stream))
+          : launch_mx_half_sr_compress(a, p->dtype, p->bits, p->rotate, stream_of(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx sr compress kernel launch");
 }
 
 int byteps_reduce_mx_rht_fold_plan_create(const byteps_mx_rht_fold_desc* segs, int nsegs,
                                           int nsrc, int bits, byteps_reduce_mx_plan** out) {
-  if (int rc = check_table(segs, nsegs, bits, out)) return rc;
+  return byteps_reduce_mx_rht_fold_plan_create_typed(segs, nsegs, nsrc, bits,
+                                                     BYTEPS_REDUCE_FLOAT32, out);
+}
+
+int byteps_reduce_mx_rht_fold_plan_create_typed(const byteps_mx_rht_fold_desc* segs, int nsegs,
+                                                int nsrc, int bits, int dtype,
+                                                byteps_reduce_mx_plan** out) {
+  if (int rc = check_table(segs, nsegs, bits, dtype, out)) return rc;
+  const uint64_t es = mx_elem_size(dtype);
   if (nsrc < 1 || nsrc > kMxMaxSrcs)
     return fail(BYTEPS_REDUCE_EARGS, "nsrc %d outside 1..%d", nsrc, kMxMaxSrcs);
   std::vector<MxRec> recs;
@@ -296,11 +352,11 @@ int byteps_reduce_mx_rht_fold_plan_create(const byteps_mx_rht_fold_desc* segs, i
   uint64_t total = 0;
   for (int i = 0; i < nsegs; ++i) {
     const byteps_mx_rht_fold_desc& d = segs[i];
-    if (int rc = check_operand(d.nelem, d.out, 4, "output", i)) return rc;
+    if (int rc = check_operand(d.nelem, d.out, (unsigned)es, "output", i)) return rc;
     stab[(size_t)i] = MxSrSeg{nullptr, d.nelem, 0, d.rot_key, {0, 0}};
     if (d.nelem == 0) continue;
     if (!d.out || !d.payloads) return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
-    bool ok = add_range(ranges, d.out, d.nelem * 4, i);
+    bool ok = add_range(ranges, d.out, d.nelem * es, i);
     for (int s = 0; s < nsrc; ++s) {
       const void* pl = d.payloads[s];
       if (!pl) return fail(BYTEPS_REDUCE_EARGS, "segment %d: null payload %d", i, s);
@@ -309,13 +365,14 @@ int byteps_reduce_mx_rht_fold_plan_create(const byteps_mx_rht_fold_desc* segs, i
       rows[(size_t)i * (size_t)nsrc + (size_t)s] = static_cast<const unsigned char*>(pl);
     }
     if (!ok) return fail(BYTEPS_REDUCE_EARGS, "segment %d: operand wraps the address space", i);
-    cut(recs, static_cast<unsigned char*>(d.out), nullptr, d.nelem, (uint32_t)i, false);
+    cut(recs, static_cast<unsigned char*>(d.out), nullptr, d.nelem, (uint32_t)i, false, es);
     total += d.nelem;
     if (recs.size() >= (1ull << 31)) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
   }
   if (int rc = check_disjoint(ranges)) return rc;
   auto* p = new byteps_reduce_mx_plan();
   p->kind = byteps_reduce_mx_plan::kRhtFold;
+  p->dtype = dtype;
   p->bits = (uint32_t)bits;
   p->nsrc = nsrc;
   p->nrecs = (uint32_t)recs.size();
@@ -344,8 +401,11 @@ int byteps_reduce_mx_rht_fold_plan_launch(byteps_reduce_mx_plan* p, int divisor,
                     p->nsrc,
                     divisor,
                     step};
-  const hipError_t e = launch_mx_rht_fold(a, p->bits, p->nelem * 4,
-                                          launch_tuning_for_n(kMxMaxSrcs), stream_of(stream));
+  const Tuning tu = launch_tuning_for_n(kMxMaxSrcs);
+  const hipError_t e =
+      p->dtype == kFloat32
+          ? launch_mx_rht_fold(a, p->bits, p->nelem * 4, tu, stream_of(stream))
+          : launch_mx_half_rht_fold(a, p->dtype, p->bits, p->nelem * 2, tu, stream_of(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx rht fold kernel launch");
 }
 

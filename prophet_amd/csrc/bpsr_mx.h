@@ -40,14 +40,17 @@ constexpr uint64_t mx_payload_bytes(uint64_t n, uint32_t bits) {
 // One tile of a compress or of a fold: both pointers already advanced to the
 // tile's first element.  A compress of an empty segment that names a payload
 // is one record of count 0: it writes the header.
-enum : uint32_t { kMxVec = 1, kMxAligned = 2 };
+enum : uint32_t { kMxVec = 1, kMxAligned = 2, kMxVecB = 4 };
 struct MxRec {
   unsigned char* a;  // compress: the gradient; fold: the output
   unsigned char* b;  // compress: the residual; fold: null
   uint32_t seg;      // the segment (MxSeg)
   uint32_t e0;       // the tile's first element in its segment
   uint32_t count;    // elements, 0..kMxTile
-  uint32_t flags;    // kMxVec: a and b 16-byte aligned; kMxAligned: 4-byte aligned
+  // f32 plans — kMxVec: a and b 16-byte aligned; kMxAligned: 4-byte aligned.
+  // 2-byte plans — kMxVec: a 16-byte aligned; kMxVecB: b 16-byte aligned (an
+  // operand is always aligned to its element there).
+  uint32_t flags;
 };
 static_assert(sizeof(MxRec) == 32, "MxRec layout");
 
@@ -114,5 +117,18 @@ hipError_t launch_mx_sr_compress(const MxSrCompress& p, uint32_t bits, bool rota
                                  hipStream_t s);
 hipError_t launch_mx_rht_fold(const MxRhtFold& p, uint32_t bits, uint64_t out_bytes,
                               const Tuning& tu, hipStream_t s);
+
+// The same four launches over 2-byte tensors (the kernels are
+// bpsr_k_mx_half.hip): `dtype` is kFloat16 or kBFloat16, the type of MxRec::a —
+// the gradient of a compress, the output of a fold.  MxRec::b, the residual,
+// stays f32; `resid_bytes` / `out_bytes` are what the launch writes.
+hipError_t launch_mx_half_compress(const MxCompress& p, int dtype, uint32_t bits,
+                                   uint64_t resid_bytes, const Tuning& tu, hipStream_t s);
+hipError_t launch_mx_half_sr_compress(const MxSrCompress& p, int dtype, uint32_t bits,
+                                      bool rotate, hipStream_t s);
+hipError_t launch_mx_half_fold(const MxFold& p, int dtype, uint32_t bits, uint64_t out_bytes,
+                               const Tuning& tu, hipStream_t s);
+hipError_t launch_mx_half_rht_fold(const MxRhtFold& p, int dtype, uint32_t bits,
+                                   uint64_t out_bytes, const Tuning& tu, hipStream_t s);
 
 }  // namespace bpsr

@@ -1,6 +1,7 @@
-// What the block-scaled kernels (bpsr_k_mx.hip, bpsr_k_mx_sr.hip) share on the
-// device: the tile's lane map, the exchanges inside a block's eight lanes, the
-// scale constants and the decode of four codes.  bpsr_mx.h has the layout.
+// What the block-scaled kernels (bpsr_k_mx.hip, bpsr_k_mx_sr.hip and, for 2-byte
+// tensors, bpsr_k_mx_half.hip) share on the device: the tile's lane map, the
+// exchanges inside a block's lanes, the scale constants and the conversions of
+// four codes.  bpsr_mx.h has the layout.
 #pragma once
 
 #include "bpsr_cast_plan.h"
@@ -35,6 +36,19 @@ struct MxFmt<4> {
   static constexpr float kMax = 6.0f;
 };
 
+// The stateless wires' view of a format (prophet_amd/mx_sr.py).
+template <int BITS>
+struct SrFmt;
+template <>
+struct SrFmt<8> {
+  static constexpr uint32_t kEmax = 8, kMant = 0x600000u, kMbits = 3, kBias = 7;
+};
+template <>
+struct SrFmt<4> {
+  static constexpr uint32_t kEmax = 2, kMant = 0x400000u, kMbits = 1, kBias = 1;
+};
+
+// A lane's j-th vector (f32 tiles) or unit (2-byte tiles) of the tile.
 __device__ __forceinline__ uint32_t vector_of(int j, uint32_t lane) {
   return (uint32_t)j * kBlock + lane;
 }
@@ -76,6 +90,36 @@ __device__ __forceinline__ void decode4(uint32_t w, float (&f)[4]) {
     f[2] = hi.x;
     f[3] = hi.y;
   }
+}
+
+// Four values, |v| <= max, to their codes: fp8 a dword, element e in byte e;
+// fp4 the low 16 bits, element e in nibble e.
+template <int BITS>
+__device__ __forceinline__ uint32_t encode4(const float (&v)[4]) {
+  if constexpr (BITS == 8) {
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
+  } else {
+    uint32_t w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(0u, v[0], v[1], 1.0f, 0);
+    return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, v[2], v[3], 1.0f, 1) & 0xffffu;
+  }
+}
+
+// The code of the f32 bits u, |u| <= max, under 16 random bits: with t the
+// magnitude in units of 2^-16 of the local step, offset so that its high part
+// is the code, (t + r16) >> 16.
+template <int BITS>
+__device__ __forceinline__ uint32_t sr_code(uint32_t u, uint32_t r16) {
+  constexpr uint32_t mb = SrFmt<BITS>::kMbits, bias = SrFmt<BITS>::kBias, drop = 23 - mb;
+  const uint32_t a = u & kKeyMask, e = a >> 23;
+  const uint32_t normal = (a >> (drop - 16)) - (((127 - bias) << mb) << 16);
+  // below the format's smallest normal: the significand shifted down
+  const uint32_t m = (a & 0x7fffffu) | (e ? 0x800000u : 0u);
+  uint32_t sh = (151 - bias - mb) - (e > 1u ? e : 1u);
+  sh = sh > 40u ? 40u : sh;
+  const uint32_t sub = (uint32_t)(((uint64_t)m << 16) >> sh);
+  const uint32_t t = e >= 128 - bias ? normal : sub;
+  return ((t + r16) >> 16) | ((u >> 31) << (BITS - 1));
 }
 
 }  // namespace

@@ -35,6 +35,13 @@ n_hi, u32 0}``, ``ceil(n / 32)`` scale bytes padded with zeros to a multiple of
 the decodes in argument order, then one divide by ``f32(divisor)`` when
 ``divisor > 1``.  Sizes come from the caller: a header is never trusted.  There
 is no floating-point reduction anywhere in the scheme, so every byte is pinned.
+
+Half-precision tensors (DESIGN.md §11.16;
+``prophet_amd/csrc/bpsr_k_mx_half.hip``).  A float16 or bf16 gradient is
+widened exactly to float32 (``widen``) and the lines above run on that: its
+payload is the payload of its upcast, and ``r`` stays float32.  A fold into a
+float16 or bf16 output computes the float32 result above and converts it once
+(``narrow``).
 """
 from __future__ import annotations
 
@@ -84,6 +91,41 @@ def payload_bytes(n: int, fmt) -> int:
 
 def _f32(x):
     return np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+
+
+def widen(g, bf16: bool = False):
+    """The gradient as a flat float32 array, exactly: a float16 array is
+    widened, ``bf16`` says ``g`` holds bf16 bits (uint16), float32 is itself."""
+    if bf16:
+        bits = np.ascontiguousarray(g).reshape(-1).view(np.uint16)
+        return (bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
+    return _f32(g)
+
+
+def narrow(x, out_dtype=None):
+    """The float32 array ``x`` in a fold's output type, converted once:
+    ``None`` or ``"float32"`` as it is; ``"float16"`` a float16 array;
+    ``"bfloat16"`` bf16 bits (uint16).  Nearest, ties to even, overflow to
+    infinity, subnormals kept; a NaN as the f32 -> fp16 / bf16 casts of
+    ``Compression.fp16`` / ``bf16`` make it (``f2h_bits``, ``f32_to_bf16_rne``
+    of ``prophet_amd/csrc/bpsr_ops.h``): the sign, quiet, the payload's top
+    bits."""
+    x = _f32(x)
+    if out_dtype in (None, "float32"):
+        return x
+    u = x.view(np.uint32)
+    nan = (u & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
+    if out_dtype == "float16":
+        with np.errstate(all="ignore"):
+            h = x.astype(np.float16).view(np.uint16)
+        as_nan = ((u >> np.uint32(16)) & np.uint32(0x8000)) | np.uint32(0x7e00) \
+            | ((u >> np.uint32(13)) & np.uint32(0x3ff))
+        return np.where(nan, as_nan, h).astype(np.uint16).view(np.float16)
+    if out_dtype == "bfloat16":
+        rne = (u.astype(np.uint64) + np.uint64(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) \
+            >> np.uint64(16)
+        return np.where(nan, (u >> np.uint32(16)) | np.uint32(0x40), rne).astype(np.uint16)
+    raise ValueError(f"mx: unknown output type {out_dtype!r} (float32, float16, bfloat16)")
 
 
 def _pow2(biased):
@@ -154,10 +196,12 @@ def quantise(c, fmt):
     return x, q, d
 
 
-def compress(g, r, fmt):
+def compress(g, r, fmt, bf16: bool = False):
     """One step: ``(payload, r')`` — the payload as a new uint8 array, the new
-    residual as a new float32 array — from the float32 arrays ``g`` and ``r``."""
-    g, r = _f32(g), _f32(r)
+    residual as a new float32 array — from the gradient ``g`` (float32,
+    float16, or with ``bf16`` its bf16 bits; ``widen``) and the float32
+    residual ``r``."""
+    g, r = widen(g, bf16), _f32(r)
     if g.size != r.size:
         raise ValueError(f"mx: {g.size} elements, {r.size} residuals")
     if g.size > MAX_ELEMS:
@@ -211,9 +255,10 @@ def decode(payload, n: int, fmt):
     return d
 
 
-def fold(payloads, n: int, fmt, divisor: int = 1):
+def fold(payloads, n: int, fmt, divisor: int = 1, out_dtype=None):
     """The N-way decode: the float32 left fold of ``decode(p, n, fmt)`` over
-    ``payloads`` in order, divided by ``f32(divisor)`` when ``divisor > 1``."""
+    ``payloads`` in order, divided by ``f32(divisor)`` when ``divisor > 1``,
+    then ``narrow(.., out_dtype)``: one conversion of the float32 result."""
     if not 1 <= len(payloads) <= MAX_SRCS:
         raise ValueError(f"mx: {len(payloads)} sources outside 1..{MAX_SRCS}")
     if int(divisor) < 1:
@@ -224,9 +269,9 @@ def fold(payloads, n: int, fmt, divisor: int = 1):
             out = out + decode(p, n, fmt)
         if int(divisor) > 1:
             out = out / np.float32(int(divisor))
-    return out.astype(np.float32)
+    return narrow(out.astype(np.float32), out_dtype)
 
 
 __all__ = ["HEADER_BYTES", "BLOCK", "MAX_SRCS", "MAX_ELEMS", "bits_of", "scale_bytes",
-           "code_bytes", "payload_bytes", "encode", "value", "scales", "quantise", "compress",
-           "header", "fields", "decode", "fold"]
+           "code_bytes", "payload_bytes", "widen", "narrow", "encode", "value", "scales",
+           "quantise", "compress", "header", "fields", "decode", "fold"]

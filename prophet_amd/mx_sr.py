@@ -49,6 +49,10 @@ fold: ``t`` the float32 left fold of the decodes, ``z`` the butterflies of
 then one divide by ``f32(divisor)`` above 1.  A block where any source has
 ``X_b == 255`` is ``0x7fc00000`` in every element.  Where finite decodes
 overflow inside the sum or the butterflies only "not finite" is contracted.
+
+A float16 or bf16 gradient is widened exactly to float32 first, and a fold into
+a float16 or bf16 output converts the float32 result once (``mx.widen``,
+``mx.narrow``).
 """
 from __future__ import annotations
 
@@ -164,9 +168,11 @@ def quantise(blocks, r16, fmt):
     return x, np.where(bad, 0, sr_encode(v, r16, fmt)).astype(np.uint8)
 
 
-def compress(g, fmt, key: int, step: int, rotate_blocks: bool = False, rot_key: int = 0):
-    """The payload (a new uint8 array) of the float32 array ``g``."""
-    g = mx._f32(g)
+def compress(g, fmt, key: int, step: int, rotate_blocks: bool = False, rot_key: int = 0,
+             bf16: bool = False):
+    """The payload (a new uint8 array) of the gradient ``g``: float32, float16,
+    or with ``bf16`` its bf16 bits, widened exactly first (``mx.widen``)."""
+    g = mx.widen(g, bf16)
     if g.size > mx.MAX_ELEMS:
         raise ValueError("mx_sr: more than 2^31 elements")
     n, bits = g.size, mx.bits_of(fmt)
@@ -197,11 +203,12 @@ def rotated(payload) -> bool:
 
 
 def fold(payloads, n: int, fmt, divisor: int = 1, rotate_blocks: bool = False,
-         rot_key: int = 0, step: int = 0):
+         rot_key: int = 0, step: int = 0, out_dtype=None):
     """The N-way decode of payloads compressed under one ``rotate_blocks``,
-    ``rot_key`` and ``step``: a new float32 array of ``n`` elements."""
+    ``rot_key`` and ``step``: a new array of ``n`` elements, the float32
+    result converted once to ``out_dtype`` (``mx.narrow``)."""
     if not rotate_blocks:
-        return mx.fold(payloads, n, fmt, divisor)
+        return mx.fold(payloads, n, fmt, divisor, out_dtype)
     n = int(n)
     out = mx.fold(payloads, n, fmt, 1)            # t, and the checks
     t = mx._blocks(out)
@@ -216,7 +223,7 @@ def fold(payloads, n: int, fmt, divisor: int = 1, rotate_blocks: bool = False,
         if int(divisor) > 1:
             z = z / np.float32(int(divisor))
     z = np.where(bad[:, None], _NAN.view(np.float32), z).astype(np.float32)
-    return z.reshape(-1)[:n].copy()
+    return mx.narrow(z.reshape(-1)[:n].copy(), out_dtype)
 
 
 __all__ = ["rotation_key", "sign_words", "butterflies", "rotate", "scales", "sr_encode",

@@ -81,6 +81,8 @@ EXPORTS = (
     "byteps_reduce_mx_fold_plan_launch", "byteps_reduce_mx_plan_destroy",
     "byteps_reduce_mx_sr_plan_create", "byteps_reduce_mx_sr_plan_compress",
     "byteps_reduce_mx_rht_fold_plan_create", "byteps_reduce_mx_rht_fold_plan_launch",
+    "byteps_reduce_mx_plan_create_typed", "byteps_reduce_mx_fold_plan_create_typed",
+    "byteps_reduce_mx_sr_plan_create_typed", "byteps_reduce_mx_rht_fold_plan_create_typed",
     "byteps_reduce_powersgd_scratch_bytes", "byteps_reduce_powersgd_plan_create",
     "byteps_reduce_powersgd_plan_project_p", "byteps_reduce_powersgd_plan_orthogonalize",
     "byteps_reduce_powersgd_plan_project_q", "byteps_reduce_powersgd_plan_finish",
@@ -298,6 +300,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.byteps_reduce_mx_rht_fold_plan_create.argtypes = [ctypes.POINTER(MXRHTFoldDesc), _int, _int,
                                                         _int, ctypes.POINTER(_vp)]
     L.byteps_reduce_mx_rht_fold_plan_launch.argtypes = [_vp, _int, ctypes.c_uint32, _vp]
+    L.byteps_reduce_mx_plan_create_typed.argtypes = [ctypes.POINTER(MXDesc), _int, _int, _int,
+                                                     ctypes.POINTER(_vp)]
+    L.byteps_reduce_mx_fold_plan_create_typed.argtypes = [ctypes.POINTER(MXFoldDesc), _int, _int,
+                                                          _int, _int, ctypes.POINTER(_vp)]
+    L.byteps_reduce_mx_sr_plan_create_typed.argtypes = [ctypes.POINTER(MXSRDesc), _int, _int,
+                                                        _int, _int, ctypes.POINTER(_vp)]
+    L.byteps_reduce_mx_rht_fold_plan_create_typed.argtypes = [
+        ctypes.POINTER(MXRHTFoldDesc), _int, _int, _int, _int, ctypes.POINTER(_vp)]
     L.byteps_reduce_powersgd_scratch_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, _int]
     L.byteps_reduce_powersgd_scratch_bytes.restype = ctypes.c_uint64
     L.byteps_reduce_powersgd_plan_create.argtypes = [ctypes.POINTER(PowerSGDDesc), _int, _int,
@@ -520,40 +530,47 @@ class GpuReducer:
         launch: ``prophet_amd.topk.fold`` byte for byte."""
         return TopKFoldPlan(self.lib, segments, nsrc)
 
-    def mx_plan(self, segments: Sequence[tuple], fmt: str) -> "MXPlan":
+    def mx_plan(self, segments: Sequence[tuple], fmt: str,
+                dtype: int = DType.FLOAT32) -> "MXPlan":
         """The block-scaled compress of a whole iteration
         (byteps_reduce_mx_plan_create): ``segments`` are ``(grad, resid,
-        payload, nelem)`` — float32 tensors of ``nelem`` elements and uint8
+        payload, nelem)`` — gradients of ``dtype`` (FLOAT32, FLOAT16 or
+        BFLOAT16) and float32 residuals of ``nelem`` elements and uint8
         payloads of ``mx.payload_bytes(nelem, fmt)`` bytes, 16-byte aligned —
         all of the format ``fmt`` (``"fp8"`` or ``"fp4"``).
         :meth:`MXPlan.compress` is ONE launch, byte for byte
         ``prophet_amd.mx.compress``."""
-        return MXPlan(self.lib, segments, fmt)
+        return MXPlan(self.lib, segments, fmt, dtype)
 
-    def mx_fold_plan(self, segments: Sequence[tuple], nsrc: int, fmt: str) -> "MXFoldPlan":
+    def mx_fold_plan(self, segments: Sequence[tuple], nsrc: int, fmt: str,
+                     dtype: int = DType.FLOAT32) -> "MXFoldPlan":
         """The N-way decode-and-sum (byteps_reduce_mx_fold_plan_create):
         ``segments`` are ``(out, payloads, nelem)`` with ``nsrc`` (1..16)
-        payloads each, added in that order.  :meth:`MXFoldPlan.launch` is ONE
-        launch: ``prophet_amd.mx.fold`` byte for byte."""
-        return MXFoldPlan(self.lib, segments, nsrc, fmt)
+        payloads each, added in that order, and outputs of ``dtype`` (FLOAT32,
+        FLOAT16 or BFLOAT16).  :meth:`MXFoldPlan.launch` is ONE launch:
+        ``prophet_amd.mx.fold`` byte for byte."""
+        return MXFoldPlan(self.lib, segments, nsrc, fmt, dtype)
 
-    def mx_sr_plan(self, segments: Sequence[tuple], fmt: str, rotate: bool = False) -> "MXSRPlan":
+    def mx_sr_plan(self, segments: Sequence[tuple], fmt: str, rotate: bool = False,
+                   dtype: int = DType.FLOAT32) -> "MXSRPlan":
         """The stateless block-scaled compress of a whole iteration
         (byteps_reduce_mx_sr_plan_create): ``segments`` are ``(grad, payload,
-        nelem, key, rot_key)`` — a float32 tensor, a uint8 payload of
+        nelem, key, rot_key)`` — a tensor of ``dtype`` (FLOAT32, FLOAT16 or
+        BFLOAT16), a uint8 payload of
         ``mx.payload_bytes(nelem, fmt)`` bytes, 16-byte aligned, the key its
         elements round under and the key its blocks are rotated under (read
         only where ``rotate``).  :meth:`MXSRPlan.compress` is ONE launch, byte
         for byte ``prophet_amd.mx_sr.compress``."""
-        return MXSRPlan(self.lib, segments, fmt, rotate)
+        return MXSRPlan(self.lib, segments, fmt, rotate, dtype)
 
-    def mx_rht_fold_plan(self, segments: Sequence[tuple], nsrc: int,
-                         fmt: str) -> "MXRHTFoldPlan":
+    def mx_rht_fold_plan(self, segments: Sequence[tuple], nsrc: int, fmt: str,
+                         dtype: int = DType.FLOAT32) -> "MXRHTFoldPlan":
         """The N-way decode-and-sum of rotated payloads
         (byteps_reduce_mx_rht_fold_plan_create): ``segments`` are ``(out,
-        payloads, nelem, rot_key)``.  :meth:`MXRHTFoldPlan.launch` is ONE
-        launch: ``prophet_amd.mx_sr.fold`` byte for byte."""
-        return MXRHTFoldPlan(self.lib, segments, nsrc, fmt)
+        payloads, nelem, rot_key)`` with outputs of ``dtype``.
+        :meth:`MXRHTFoldPlan.launch` is ONE launch: ``prophet_amd.mx_sr.fold``
+        byte for byte."""
+        return MXRHTFoldPlan(self.lib, segments, nsrc, fmt, dtype)
 
     def powersgd_plan(self, segments: Sequence[tuple], rank: int) -> "PowerSGDPlan":
         """PowerSGD low-rank compression of a whole iteration
@@ -1155,10 +1172,13 @@ class _MXPlanBase(_OneBitPlanBase):
     """What the block-scaled plans share (the 1-bit plans' handle and held
     tensors) and the format's element bits."""
 
-    def __init__(self, lib, fmt):
+    def __init__(self, lib, fmt, dtype=DType.FLOAT32):
         from .mx import bits_of
         super().__init__(lib)
         self.fmt, self.bits = fmt, bits_of(fmt)
+        # of the gradients (compress) or the outputs (fold); the library checks it
+        self.dtype = int(dtype)
+        self.esize = 2 if self.dtype in (DType.FLOAT16, DType.BFLOAT16) else 4
 
     def close(self) -> None:
         if self.handle:
@@ -1171,16 +1191,17 @@ class MXPlan(_MXPlanBase):
     """A block-scaled compress plan (``byteps_reduce_mx_plan_create``).  Tensor
     operands are bounds-checked before the library sees them."""
 
-    def __init__(self, lib, segments, fmt):
+    def __init__(self, lib, segments, fmt, dtype=DType.FLOAT32):
         from .mx import payload_bytes
-        super().__init__(lib, fmt)
+        super().__init__(lib, fmt, dtype)
         segments = [tuple(s) for s in segments]
         for s in segments:
             if len(s) != 4:
                 raise ValueError(f"mx plan: a segment of {len(s)} items")
             if int(s[3]) < 0:
                 raise ValueError(f"negative element count {s[3]}")
-            _fits(int(s[3]) * 4, s[0], s[1])
+            _fits(int(s[3]) * self.esize, s[0])
+            _fits(int(s[3]) * 4, s[1])
             _fits(payload_bytes(s[3], fmt), s[2])
         self._keep = segments
         self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
@@ -1188,8 +1209,8 @@ class MXPlan(_MXPlanBase):
         descs = (MXDesc * max(1, len(segments)))()
         for d, s in zip(descs, segments):
             d.grad, d.resid, d.payload, d.nelem = _ptr(s[0]), _ptr(s[1]), _ptr(s[2]), int(s[3])
-        _check(lib.byteps_reduce_mx_plan_create(descs, len(segments), self.bits,
-                                                ctypes.byref(self.handle)))
+        _check(lib.byteps_reduce_mx_plan_create_typed(descs, len(segments), self.bits,
+                                                      self.dtype, ctypes.byref(self.handle)))
 
     def compress(self, stream=None) -> None:
         """One launch (byteps_reduce_mx_plan_compress)."""
@@ -1200,9 +1221,9 @@ class MXPlan(_MXPlanBase):
 class MXFoldPlan(_MXPlanBase):
     """A block-scaled fold plan (``byteps_reduce_mx_fold_plan_create``)."""
 
-    def __init__(self, lib, segments, nsrc, fmt):
+    def __init__(self, lib, segments, nsrc, fmt, dtype=DType.FLOAT32):
         from .mx import payload_bytes
-        super().__init__(lib, fmt)
+        super().__init__(lib, fmt, dtype)
         self.nsrc = int(nsrc)
         segments = [(s[0], list(s[1]), int(s[2])) for s in segments]
         for out, payloads, nelem in segments:
@@ -1210,7 +1231,7 @@ class MXFoldPlan(_MXPlanBase):
                 raise ValueError(f"negative element count {nelem}")
             if len(payloads) != self.nsrc:
                 raise ValueError(f"mx fold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
-            _fits(nelem * 4, out)
+            _fits(nelem * self.esize, out)
             _fits(payload_bytes(nelem, fmt), *payloads)
         self._keep = segments
         self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
@@ -1221,8 +1242,8 @@ class MXFoldPlan(_MXPlanBase):
             row = (_vp * max(1, len(payloads)))(*[_ptr(p) for p in payloads])
             rows.append(row)
             d.out, d.payloads, d.nelem = _ptr(out), ctypes.cast(row, ctypes.POINTER(_vp)), nelem
-        _check(lib.byteps_reduce_mx_fold_plan_create(descs, len(segments), self.nsrc, self.bits,
-                                                     ctypes.byref(self.handle)))
+        _check(lib.byteps_reduce_mx_fold_plan_create_typed(
+            descs, len(segments), self.nsrc, self.bits, self.dtype, ctypes.byref(self.handle)))
 
     def launch(self, divisor: int = 1, stream=None) -> None:
         """One launch (byteps_reduce_mx_fold_plan_launch)."""
@@ -1235,9 +1256,9 @@ class MXSRPlan(_MXPlanBase):
     (``byteps_reduce_mx_sr_plan_create``).  Tensor operands are bounds-checked
     before the library sees them."""
 
-    def __init__(self, lib, segments, fmt, rotate=False):
+    def __init__(self, lib, segments, fmt, rotate=False, dtype=DType.FLOAT32):
         from .mx import payload_bytes
-        super().__init__(lib, fmt)
+        super().__init__(lib, fmt, dtype)
         self.rotate = bool(rotate)
         segments = [tuple(s) for s in segments]
         for s in segments:
@@ -1245,7 +1266,7 @@ class MXSRPlan(_MXPlanBase):
                 raise ValueError(f"mx sr plan: a segment of {len(s)} items")
             if int(s[2]) < 0:
                 raise ValueError(f"negative element count {s[2]}")
-            _fits(int(s[2]) * 4, s[0])
+            _fits(int(s[2]) * self.esize, s[0])
             _fits(payload_bytes(s[2], fmt), s[1])
         self._keep = segments
         self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
@@ -1254,8 +1275,9 @@ class MXSRPlan(_MXPlanBase):
         for d, s in zip(descs, segments):
             d.grad, d.payload, d.nelem = _ptr(s[0]), _ptr(s[1]), int(s[2])
             d.key, d.rot_key = int(s[3]) & 0xffffffff, int(s[4]) & 0xffffffff
-        _check(lib.byteps_reduce_mx_sr_plan_create(descs, len(segments), self.bits,
-                                                   int(self.rotate), ctypes.byref(self.handle)))
+        _check(lib.byteps_reduce_mx_sr_plan_create_typed(
+            descs, len(segments), self.bits, int(self.rotate), self.dtype,
+            ctypes.byref(self.handle)))
 
     def compress(self, step: int, stream=None) -> None:
         """One launch (byteps_reduce_mx_sr_plan_compress)."""
@@ -1267,9 +1289,9 @@ class MXRHTFoldPlan(_MXPlanBase):
     """A rotated block-scaled fold plan
     (``byteps_reduce_mx_rht_fold_plan_create``)."""
 
-    def __init__(self, lib, segments, nsrc, fmt):
+    def __init__(self, lib, segments, nsrc, fmt, dtype=DType.FLOAT32):
         from .mx import payload_bytes
-        super().__init__(lib, fmt)
+        super().__init__(lib, fmt, dtype)
         self.nsrc = int(nsrc)
         segments = [(s[0], list(s[1]), int(s[2]), int(s[3]) & 0xffffffff) for s in segments]
         for out, payloads, nelem, _ in segments:
@@ -1277,7 +1299,7 @@ class MXRHTFoldPlan(_MXPlanBase):
                 raise ValueError(f"negative element count {nelem}")
             if len(payloads) != self.nsrc:
                 raise ValueError(f"mx rht fold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
-            _fits(nelem * 4, out)
+            _fits(nelem * self.esize, out)
             _fits(payload_bytes(nelem, fmt), *payloads)
         self._keep = segments
         self.first = next((s[0] for s in segments if hasattr(s[0], "device")), None)
@@ -1289,8 +1311,8 @@ class MXRHTFoldPlan(_MXPlanBase):
             rows.append(row)
             d.out, d.payloads = _ptr(out), ctypes.cast(row, ctypes.POINTER(_vp))
             d.nelem, d.rot_key = nelem, rot_key
-        _check(lib.byteps_reduce_mx_rht_fold_plan_create(descs, len(segments), self.nsrc,
-                                                         self.bits, ctypes.byref(self.handle)))
+        _check(lib.byteps_reduce_mx_rht_fold_plan_create_typed(
+            descs, len(segments), self.nsrc, self.bits, self.dtype, ctypes.byref(self.handle)))
 
     def launch(self, divisor: int = 1, step: int = 0, stream=None) -> None:
         """One launch (byteps_reduce_mx_rht_fold_plan_launch)."""

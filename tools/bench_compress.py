@@ -258,6 +258,11 @@ def main() -> int:
                         "sign flip and a 32 x 32 Hadamard matmul where rotated), and the "
                         "8-source rotated fold against the mx fold; the ResNet-50 table and one "
                         "segment")
+    p.add_argument("--mx-half", action="store_true",
+                   help="the block-scaled wires over one bf16 tensor of --elems: mxfp8_ef, "
+                        "mxfp8_sr and mxfp4_rht_sr, compress and 8-source fold, against the "
+                        "float32 kernel on the upcast tensor and against torch's upcast + "
+                        "float32 compress / float32 fold + torch's downcast")
     p.add_argument("--powersgd", action="store_true",
                    help="PowerSGD at rank 4: the four phases and their sum against torch's add, "
                         "matmul, linalg.qr, matmul, mm and sub per tensor; the ResNet-50 table's "
@@ -265,6 +270,8 @@ def main() -> int:
     args = p.parse_args()
     if args.powersgd:
         return powersgd_mode(args)
+    if args.mx_half:
+        return mx_half_mode(args)
     if args.mx:
         return mx_mode(args)
     if args.mx_sr:
@@ -2003,6 +2010,135 @@ def mx_sr_mode(args) -> int:
         with open(args.out, "a") as f:
             f.write(line + "\n")
     return 0 if all(gates.values()) and all(v for c in checks.values() for v in c.values()) else 1
+
+
+def mx_half_mode(args) -> int:
+    """The block-scaled wires over a bf16 tensor: mxfp8_ef,
+    mxfp8_sr and mxfp4_rht_sr, the compress and the 8-source fold of one
+    ``--elems`` tensor, each against two things in the same run: the float32
+    kernel on the upcast tensor, and today's route for a half tensor — torch's
+    upcast into a ready float32 buffer and the float32 compress; the float32
+    fold into a float32 buffer and torch's downcast.  Before timing, the bf16
+    compress's payload is compared with the float32 one's byte for byte, and
+    the bf16 fold's output with the downcast float32 fold."""
+    import torch
+
+    from prophet_amd import mx
+    from prophet_amd.dtypes import DType
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    NSRC, STEP, KEY, RK, n = 8, 3, 1000, 77, args.elems
+    BF = DType.BFLOAT16
+    out = {"tool": "bench_compress", "mode": "block-scaled wires over a bf16 tensor",
+           "elems": n, "nsrc": NSRC, "sets": args.sets, "rounds": args.rounds,
+           "inner": args.inner, "device": torch.cuda.get_device_name(0)}
+    checks = {}
+
+    def wire(label, fmt, kind):
+        nb = mx.payload_bytes(n, fmt)
+        rot = kind == "rht"
+
+        def comp_plan(g, r, p, dtype):
+            if kind == "ef":
+                return red.mx_plan([(g, r, p, n)], fmt, dtype)
+            return red.mx_sr_plan([(g, p, n, KEY, RK)], fmt, rot, dtype)
+
+        def fold_plan(o, ps, dtype):
+            if rot:
+                return red.mx_rht_fold_plan([(o, ps, n, RK)], NSRC, fmt, dtype)
+            return red.mx_fold_plan([(o, ps, n)], NSRC, fmt, dtype)
+
+        with step(f"setup, {label}", 300):
+            gen = torch.Generator(device=dev).manual_seed(13)
+            sets = []
+            for _ in range(args.sets):
+                s = {"g16": torch.randn(n, device=dev, generator=gen).bfloat16(),
+                     "r16": torch.zeros(n, device=dev), "r32": torch.zeros(n, device=dev),
+                     "tmp": torch.empty(n, device=dev),
+                     "o16": torch.empty(n, dtype=torch.bfloat16, device=dev),
+                     "o32": torch.empty(n, device=dev),
+                     "p16": torch.empty(nb, dtype=torch.uint8, device=dev),
+                     "p32": torch.empty(nb, dtype=torch.uint8, device=dev),
+                     "src": [torch.empty(nb, dtype=torch.uint8, device=dev) for _ in range(NSRC)]}
+                s["g32"] = s["g16"].float()
+                s["c16"] = comp_plan(s["g16"], s["r16"], s["p16"], BF)
+                s["c32"] = comp_plan(s["g32"], s["r32"], s["p32"], DType.FLOAT32)
+                s["ctoday"] = comp_plan(s["tmp"], s["r32"], s["p32"], DType.FLOAT32)
+                for j in range(NSRC):                # the fold's sources: NSRC other gradients
+                    gj = (torch.randn(n, device=dev, generator=gen) * (j + 1)).bfloat16()
+                    pl = comp_plan(gj, s["tmp"].zero_(), s["src"][j], BF)
+                    pl.compress(*((STEP,) if kind != "ef" else ()))
+                    pl.close()
+                    del gj
+                s["f16"] = fold_plan(s["o16"], s["src"], BF)
+                s["f32"] = fold_plan(s["o32"], s["src"], DType.FLOAT32)
+                s["ftoday"] = fold_plan(s["tmp"], s["src"], DType.FLOAT32)
+                sets.append(s)
+            torch.cuda.synchronize()
+
+        run = (lambda pl: pl.compress()) if kind == "ef" else (lambda pl: pl.compress(STEP))
+        launch = (lambda pl: pl.launch(1, STEP)) if rot else (lambda pl: pl.launch(1))
+
+        def today_compress(i):
+            sets[i]["tmp"].copy_(sets[i]["g16"])
+            run(sets[i]["ctoday"])
+
+        def today_fold(i):
+            launch(sets[i]["ftoday"])
+            sets[i]["o16"].copy_(sets[i]["tmp"])
+
+        with step(f"check, {label}", 300):
+            s = sets[0]
+            run(s["c16"])
+            run(s["c32"])
+            launch(s["f16"])
+            launch(s["ftoday"])
+            torch.cuda.synchronize()
+            checks[label] = {
+                "payload_equals_float32_route": bool(torch.equal(s["p16"], s["p32"])),
+                "fold_equals_downcast_float32_fold": bool(torch.equal(
+                    s["o16"].view(torch.int16), s["tmp"].bfloat16().view(torch.int16)))}
+            for t in ("r16", "r32"):
+                s[t].zero_()
+        cands = {"compress": (lambda i: run(sets[i]["c16"]), args.inner),
+                 "f32_compress": (lambda i: run(sets[i]["c32"]), args.inner),
+                 "today_compress": (today_compress, args.inner),
+                 "fold": (lambda i: launch(sets[i]["f16"]), args.inner),
+                 "f32_fold": (lambda i: launch(sets[i]["f32"]), args.inner),
+                 "today_fold": (today_fold, args.inner)}
+        res = timed_rounds(torch, cands, len(sets), args)
+        w, side = mx.bits_of(fmt) / 8 + 1 / 32, 8 if kind == "ef" else 0
+        for name, per in (("compress", 2 + side + w), ("f32_compress", 4 + side + w),
+                          ("fold", 2 + NSRC * w), ("f32_fold", 4 + NSRC * w)):
+            res[name]["bytes_per_elem"] = round(per, 4)
+            res[name]["roofline_frac"] = round(per * n / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        for what in ("compress", "fold"):
+            res[what]["speedup_over_today"] = round(res[f"today_{what}"]["ms"] / res[what]["ms"], 4)
+            res[what]["ratio_to_f32"] = round(res[what]["ms"] / res[f"f32_{what}"]["ms"], 4)
+        for s in sets:
+            for name in ("c16", "c32", "ctoday", "f16", "f32", "ftoday"):
+                s[name].close()
+        return res
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    for label, fmt, kind in (("mxfp8_ef", "fp8", "ef"), ("mxfp8_sr", "fp8", "sr"),
+                             ("mxfp4_rht_sr", "fp4", "rht")):
+        out[label] = wire(label, fmt, kind)
+        torch.cuda.empty_cache()
+    out["checks"] = checks
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    return 0 if all(v for c in checks.values() for v in c.values()) else 1
 
 
 def powersgd_mode(args) -> int:
