@@ -95,7 +95,10 @@ extern "C" {
  *    additive, still 5: byteps_reduce_powersgd_* (byteps_powersgd_desc: PowerSGD
  *                       low-rank compression with error feedback)
  *    additive, still 5: byteps_reduce_mx_*_plan_create_typed (the block-scaled
- *                       wires over FLOAT16 and BFLOAT16 tensors) */
+ *                       wires over FLOAT16 and BFLOAT16 tensors)
+ *    additive, still 5: byteps_reduce_mx_refold_plan_create / _launch
+ *                       (byteps_mx_refold_desc: the server round of the
+ *                       block-scaled error-feedback wires) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -935,6 +938,40 @@ int byteps_reduce_mx_sr_plan_create_typed(const byteps_mx_sr_desc* segs, int nse
 int byteps_reduce_mx_rht_fold_plan_create_typed(const byteps_mx_rht_fold_desc* segs, int nsegs,
                                                 int nsrc, int bits, int dtype,
                                                 byteps_reduce_mx_plan** out);
+
+/* The server round of the block-scaled error-feedback wires (DESIGN.md §11.17;
+ * the definition is prophet_amd/mx.py's refold, byte for byte).  A segment is
+ * one key: `srcs` are the nsrc (1..16) payloads the workers pushed, all of n
+ * FLOAT32 elements and the plan's format; `resid` is the server's FLOAT32
+ * residual of n elements; `out` is the payload every worker pulls.  The round is
+ * the compress above of the fold above, with divisor 1:
+ *
+ *   c_i = (d_0,i + d_1,i + ... + d_{nsrc-1},i) + r_i     the adds in argument order
+ *
+ * then X_b, q_i and r'_i as a compress gives them, r' written over r and one
+ * payload (header, scale bytes, codes, padding) to `out`.  A source block with
+ * X_b == 255 or an overflowed sum makes the block non-finite: X_b = 255, codes
+ * of 0, r' = 0x7fc00000.  The server does not divide; a worker's fold of what
+ * it pulled does.  _launch is ONE launch on `stream`: the sum lives in
+ * registers, there is no scratch memory and no host synchronisation.  Sizes
+ * come from the plan, a source's header is never read.  The plan is a
+ * byteps_reduce_mx_plan, freed by _plan_destroy.
+ *
+ * EARGS before any HIP call, every buffer untouched: nsrc outside 1..16, bits
+ * other than 8 or 4, a null pointer with nelem > 0, nelem > 2^31, a residual
+ * that is not 4-byte aligned, a payload (source or output) that is not 16-byte
+ * aligned, any two byte ranges of a plan's operands overlapping (the output
+ * payload aliases no source and no residual), a null plan, a _refold_plan_launch
+ * on a plan of another kind or another launch on this one. */
+typedef struct byteps_mx_refold_desc {
+  const void* const* srcs; /* nsrc of them; read by _refold_plan_create alone */
+  void* resid;
+  void* out;
+  uint64_t nelem;
+} byteps_mx_refold_desc;
+int byteps_reduce_mx_refold_plan_create(const byteps_mx_refold_desc* segs, int nsegs, int nsrc,
+                                        int bits, byteps_reduce_mx_plan** out);
+int byteps_reduce_mx_refold_plan_launch(byteps_reduce_mx_plan* plan, void* stream);
 
 /* PowerSGD low-rank compression with error feedback (the
  * definition is prophet_amd/powersgd.py).  A segment is one row-major n x m

@@ -429,6 +429,15 @@ class CastPlanCache:
             for o, ps in segs)
         return self._get(key, lambda: _new_mx_fold_plan(segs, nsrc, fmt, dtype))
 
+    def get_mx_refold(self, segs, nsrc: int, fmt: str):
+        """The block-scaled refold plan (``GpuReducer.mx_refold_plan``) over
+        ``segs`` of ``(payloads, resid, out_payload)`` device tensors on the
+        current device."""
+        key = ("mx_refold", fmt, int(nsrc)) + tuple(
+            (int(r.data_ptr()), int(o.data_ptr()), int(r.numel()))
+            + tuple(int(p.data_ptr()) for p in ps) for ps, r, o in segs)
+        return self._get(key, lambda: _new_mx_refold_plan(segs, nsrc, fmt))
+
     def get_mx_sr(self, segs, fmt: str, rotate: bool = False, dtype: int = 0):
         """The stateless block-scaled compress plan (``GpuReducer.mx_sr_plan``)
         over ``segs`` of flat ``(grad, payload, key, rot_key)`` device tensors
@@ -475,6 +484,11 @@ def _new_mx_plan(segs, fmt: str, dtype: int = 0):
 def _new_mx_fold_plan(segs, nsrc: int, fmt: str, dtype: int = 0):
     from .torch_ops import _red
     return _red().mx_fold_plan([(o, ps, int(o.numel())) for o, ps in segs], nsrc, fmt, dtype)
+
+
+def _new_mx_refold_plan(segs, nsrc: int, fmt: str):
+    from .torch_ops import _red
+    return _red().mx_refold_plan([(ps, r, o, int(r.numel())) for ps, r, o in segs], nsrc, fmt)
 
 
 def _new_mx_sr_plan(segs, fmt: str, rotate: bool, dtype: int = 0):
@@ -1359,6 +1373,20 @@ class OneBitEFCompressor(Compressor):
             return torch.empty(payload_bytes(n), dtype=torch.uint8, device=x.device)
         return np.empty(payload_bytes(n), dtype=np.uint8)
 
+    @classmethod
+    def payload_nbytes(cls, n: int) -> int:
+        """The bytes of the payload of ``n`` elements."""
+        from .onebit import payload_bytes
+        return payload_bytes(n)
+
+    @classmethod
+    def init_payload(cls, n: int):
+        """The payload of ``n`` zeros, a new uint8 array: the header ``{0.0,
+        n}`` and zeros — what a key's init push carries."""
+        zero = np.zeros(cls.payload_nbytes(n), dtype=np.uint8)
+        zero[4:12] = np.array([int(n)], dtype="<u8").view(np.uint8)
+        return zero
+
     residual_like = classmethod(_ErrorFeedback.residual_like.__func__)
 
     @classmethod
@@ -1702,9 +1730,12 @@ class MXFP8EFCompressor(Compressor):
     bfloat16 outputs, converting its float32 result once.  Everything else
     passes through.
 
-    There is no server round for these wires yet: ``Worker.init_tensor``
-    refuses them over every front end.  ``fold_many_into`` is what a worker
-    that gathered every worker's payload computes."""
+    The server round is opt-in: ``Worker.init_tensor`` takes
+    these wires, float32 tensors only, over a ``ServerFrontend`` that names
+    them in ``packed_wires`` — its ``packed_round.PackedRound`` store then runs
+    ``refold_many_into``, one fused launch a round — and refuses them over
+    every other front end.  ``fold_many_into`` is what a worker that gathered
+    every worker's payload computes."""
 
     ERROR_FEEDBACK = True
     PACKED = True
@@ -1723,6 +1754,22 @@ class MXFP8EFCompressor(Compressor):
             import torch
             return torch.empty(size, dtype=torch.uint8, device=x.device)
         return np.empty(size, dtype=np.uint8)
+
+    @classmethod
+    def payload_nbytes(cls, n: int) -> int:
+        """The bytes of the payload of ``n`` elements."""
+        from .mx import payload_bytes
+        return payload_bytes(n, cls.FMT)
+
+    @classmethod
+    def init_payload(cls, n: int):
+        """The payload of ``n`` zeros, a new uint8 array: the header ``{bits,
+        n}`` and zeros — what a key's init push carries."""
+        from .mx import bits_of
+        zero = np.zeros(cls.payload_nbytes(n), dtype=np.uint8)
+        zero[0:4] = np.array([bits_of(cls.FMT)], dtype="<u4").view(np.uint8)
+        zero[4:12] = np.array([int(n)], dtype="<u8").view(np.uint8)
+        return zero
 
     residual_like = classmethod(_ErrorFeedback.residual_like.__func__)
 
@@ -1819,6 +1866,45 @@ class MXFP8EFCompressor(Compressor):
                       lambda cache, segs, dt: cache.get_mx_fold(segs, nsrc, cls.FMT, dt),
                       lambda plan, stream: plan.launch(int(divisor), stream=stream))
         return outs
+
+    @classmethod
+    def refold_many_into(cls, out_payloads, residuals, payload_lists,
+                         plans: CastPlanCache | None = None):
+        """The server round: ``out_payloads[i], residuals[i] =
+        mx.refold(payload_lists[i], residuals[i].size, residuals[i], FMT)`` for
+        every i — every list of the same length N, 1..16, the float32 residual
+        in place — the device tensors as one block-scaled refold plan per
+        device (ONE launch, the folded sum never written); returns
+        ``out_payloads``."""
+        from . import mx
+        if len(out_payloads) != len(payload_lists) or len(residuals) != len(payload_lists):
+            raise ValueError("refold_many_into: as many output payloads and residuals as "
+                             "payload lists")
+        nsrc = len(payload_lists[0]) if payload_lists else 1
+        if not 1 <= nsrc <= mx.MAX_SRCS or any(len(ps) != nsrc for ps in payload_lists):
+            raise ValueError(f"refold_many_into: every segment takes the same "
+                             f"1..{mx.MAX_SRCS} payloads")
+        name, groups = f"mx{cls.FMT}_ef", {}
+        for i, (o, r, ps) in enumerate(zip(out_payloads, residuals, payload_lists)):
+            if not _is_f32(r):
+                raise ValueError(f"{name}: residual {i} must be float32, got {r.dtype}")
+            dev = [_on_device(x) for x in [o, r] + list(ps)]
+            if any(dev) != all(dev):
+                raise ValueError(f"{name}: segment {i}'s operands live in one place, a device "
+                                 f"or the host")
+            if dev[0]:
+                for p in [o] + list(ps):
+                    cls._check_device_segment(i, r, payload=p)
+                groups.setdefault(r.device, []).append((list(ps), r.reshape(-1), o))
+                continue
+            ra, oa = _mx_host(r), _payload_array(o)
+            if oa.size != mx.payload_bytes(ra.size, cls.FMT):
+                raise ValueError(f"{name}: segment {i}'s operands differ in size")
+            oa[:], ra[:] = mx.refold([_payload_array(p) for p in ps], ra.size, ra, cls.FMT)
+        OneBitEFCompressor._run(groups, plans,
+                                lambda cache, segs: cache.get_mx_refold(segs, nsrc, cls.FMT),
+                                lambda plan, stream: plan.launch(stream=stream))
+        return out_payloads
 
     @classmethod
     def _check_device_segment(cls, i: int, tensor, resid=None, payload=None) -> None:

@@ -2,11 +2,12 @@
 // include/bpsr/reduce.h): the operand checks, the plans' tables (bpsr_mx.h) and
 // the C entry points — the error-feedback compress and the fold, and the
 // stateless wires' compress and rotated fold (byteps_reduce_mx_sr_*,
-// byteps_reduce_mx_rht_fold_*).  A plan carries the element type of its
-// gradients or outputs (the _typed creates): FLOAT32 runs bpsr_k_mx.hip and
-// bpsr_k_mx_sr.hip, FLOAT16 and BFLOAT16 run bpsr_k_mx_half.hip.  Every check
-// runs before the first HIP call of its entry: a refused call has touched
-// nothing.
+// byteps_reduce_mx_rht_fold_*), and the error-feedback wires' server round
+// (byteps_reduce_mx_refold_*, FLOAT32 alone: bpsr_k_mx_refold.hip).  A plan
+// carries the element type of its gradients or outputs (the _typed creates):
+// FLOAT32 runs bpsr_k_mx.hip and bpsr_k_mx_sr.hip, FLOAT16 and BFLOAT16 run
+// bpsr_k_mx_half.hip.  Every check runs before the first HIP call of its entry:
+// a refused call has touched nothing.
 #include <algorithm>
 #include <cstring>
 
@@ -15,14 +16,14 @@
 
 struct byteps_reduce_mx_plan {
   // which launch takes it: _plan_compress, _fold_plan_launch, _sr_plan_compress,
-  // _rht_fold_plan_launch
-  enum Kind { kCompress, kFold, kSrCompress, kRhtFold };
+  // _rht_fold_plan_launch, _refold_plan_launch
+  enum Kind { kCompress, kFold, kSrCompress, kRhtFold, kRefold };
   Kind kind = kCompress;
   bool rotate = false;  // kSrCompress
   // of the gradient (compress) or the output (fold): FLOAT32, FLOAT16 or BFLOAT16
   int dtype = BYTEPS_REDUCE_FLOAT32;
   uint32_t bits = 0;
-  int nsrc = 0;  // fold
+  int nsrc = 0;  // fold, refold
   uint32_t nrecs = 0;
   uint64_t nelem = 0;  // of all segments (store policy)
   // on the device: the records, the segments, the rows of source pointers (fold)
@@ -269,6 +270,69 @@ int byteps_reduce_mx_fold_plan_launch(byteps_reduce_mx_plan* p, int divisor, voi
           ? launch_mx_fold(a, p->bits, p->nelem * 4, tu, stream_of(stream))
           : launch_mx_half_fold(a, p->dtype, p->bits, p->nelem * 2, tu, stream_of(stream));
   return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx fold kernel launch");
+}
+
+int byteps_reduce_mx_refold_plan_create(const byteps_mx_refold_desc* segs, int nsegs, int nsrc,
+                                        int bits, byteps_reduce_mx_plan** out) {
+  if (int rc = check_table(segs, nsegs, bits, BYTEPS_REDUCE_FLOAT32, out)) return rc;
+  if (nsrc < 1 || nsrc > kMxMaxSrcs)
+    return fail(BYTEPS_REDUCE_EARGS, "nsrc %d outside 1..%d", nsrc, kMxMaxSrcs);
+  std::vector<MxRec> recs;
+  std::vector<MxSeg> stab((size_t)nsegs);
+  std::vector<const unsigned char*> rows((size_t)nsegs * (size_t)nsrc, nullptr);
+  std::vector<Range> ranges;
+  uint64_t total = 0;
+  for (int i = 0; i < nsegs; ++i) {
+    const byteps_mx_refold_desc& d = segs[i];
+    if (int rc = check_operand(d.nelem, d.out, 16, "output payload", i)) return rc;
+    if (int rc = check_operand(d.nelem, d.resid, 4, "residual", i)) return rc;
+    if (d.nelem > 0 && (!d.resid || !d.out || !d.srcs))
+      return fail(BYTEPS_REDUCE_EARGS, "segment %d: null pointer", i);
+    // an empty segment still gets its header where it names an output payload
+    bool ok = (!d.out || add_range(ranges, d.out, mx_payload_bytes(d.nelem, (uint32_t)bits), i)) &&
+              add_range(ranges, d.resid, d.nelem * 4, i);
+    for (int s = 0; d.nelem > 0 && s < nsrc; ++s) {
+      const void* pl = d.srcs[s];
+      if (!pl) return fail(BYTEPS_REDUCE_EARGS, "segment %d: null payload %d", i, s);
+      if (int rc = check_operand(d.nelem, pl, 16, "payload", i)) return rc;
+      ok = ok && add_range(ranges, pl, mx_payload_bytes(d.nelem, (uint32_t)bits), i);
+      rows[(size_t)i * (size_t)nsrc + (size_t)s] = static_cast<const unsigned char*>(pl);
+    }
+    if (!ok) return fail(BYTEPS_REDUCE_EARGS, "segment %d: operand wraps the address space", i);
+    cut(recs, static_cast<unsigned char*>(d.resid), nullptr, d.nelem, (uint32_t)i,
+        d.out != nullptr, 4);
+    stab[(size_t)i] = MxSeg{static_cast<unsigned char*>(d.out), d.nelem};
+    total += d.nelem;
+    if (recs.size() >= (1ull << 31)) return fail(BYTEPS_REDUCE_EARGS, "plan too large");
+  }
+  // the output payload aliases no source and no residual; sources are distinct
+  if (int rc = check_disjoint(ranges)) return rc;
+  auto* p = new byteps_reduce_mx_plan();
+  p->kind = byteps_reduce_mx_plan::kRefold;
+  p->bits = (uint32_t)bits;
+  p->nsrc = nsrc;
+  p->nrecs = (uint32_t)recs.size();
+  p->nelem = total;
+  hipError_t e = upload(&p->table, recs);
+  if (e == hipSuccess) e = upload(&p->side, stab);
+  if (e == hipSuccess) e = upload(&p->rows, rows);
+  if (e != hipSuccess) {
+    (void)plan_free(p);
+    return hip_fail(e, "mx refold plan table upload");
+  }
+  *out = p;
+  return BYTEPS_REDUCE_OK;
+}
+
+int byteps_reduce_mx_refold_plan_launch(byteps_reduce_mx_plan* p, void* stream) {
+  if (!p) return fail(BYTEPS_REDUCE_EARGS, "null plan");
+  if (p->kind != byteps_reduce_mx_plan::kRefold)
+    return fail(BYTEPS_REDUCE_EARGS, "refold launch on a plan of another kind");
+  const MxRefold a{static_cast<const MxRec*>(p->table), static_cast<const MxSeg*>(p->side),
+                   static_cast<const unsigned char* const*>(p->rows), p->nrecs, p->nsrc};
+  const Tuning tu = launch_tuning_for_n(kMxMaxSrcs);
+  const hipError_t e = launch_mx_refold(a, p->bits, p->nelem * 4, tu, stream_of(stream));
+  return e == hipSuccess ? BYTEPS_REDUCE_OK : hip_fail(e, "mx refold kernel launch");
 }
 
 int byteps_reduce_mx_sr_plan_create(const byteps_mx_sr_desc* segs, int nsegs, int bits,

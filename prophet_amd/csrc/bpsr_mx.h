@@ -42,8 +42,8 @@ constexpr uint64_t mx_payload_bytes(uint64_t n, uint32_t bits) {
 // is one record of count 0: it writes the header.
 enum : uint32_t { kMxVec = 1, kMxAligned = 2, kMxVecB = 4 };
 struct MxRec {
-  unsigned char* a;  // compress: the gradient; fold: the output
-  unsigned char* b;  // compress: the residual; fold: null
+  unsigned char* a;  // compress: the gradient; fold: the output; refold: the residual
+  unsigned char* b;  // compress: the residual; fold, refold: null
   uint32_t seg;      // the segment (MxSeg)
   uint32_t e0;       // the tile's first element in its segment
   uint32_t count;    // elements, 0..kMxTile
@@ -83,6 +83,22 @@ hipError_t launch_mx_compress(const MxCompress& p, uint32_t bits, uint64_t resid
                               const Tuning& tu, hipStream_t s);
 hipError_t launch_mx_fold(const MxFold& p, uint32_t bits, uint64_t out_bytes, const Tuning& tu,
                           hipStream_t s);
+
+// The server round (byteps_reduce_mx_refold_*; the kernel is
+// bpsr_k_mx_refold.hip): the fold's sum plus the residual, compressed, in one
+// launch.  Records are MxRec with `a` the residual's tile and `b` null; a
+// segment's `payload` is the one written, its sources row `seg` of `srcs`.  An
+// empty segment that names an output payload is one record of count 0.
+struct MxRefold {
+  const MxRec* recs;
+  const MxSeg* segs;
+  const unsigned char* const* srcs;  // as MxFold::srcs
+  uint32_t nrecs;
+  int nsrc;
+};
+
+hipError_t launch_mx_refold(const MxRefold& p, uint32_t bits, uint64_t resid_bytes,
+                            const Tuning& tu, hipStream_t s);
 
 // The stateless wires (byteps_reduce_mx_sr_*, byteps_reduce_mx_rht_fold_*,
 // DESIGN.md §11.15; the definition is prophet_amd/mx_sr.py; the kernels are

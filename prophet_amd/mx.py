@@ -35,6 +35,8 @@ n_hi, u32 0}``, ``ceil(n / 32)`` scale bytes padded with zeros to a multiple of
 the decodes in argument order, then one divide by ``f32(divisor)`` when
 ``divisor > 1``.  Sizes come from the caller: a header is never trusted.  There
 is no floating-point reduction anywhere in the scheme, so every byte is pinned.
+``refold`` is the server round: the ``compress`` of that
+fold, undivided, against the server's own residual.
 
 Half-precision tensors (DESIGN.md §11.16;
 ``prophet_amd/csrc/bpsr_k_mx_half.hip``).  A float16 or bf16 gradient is
@@ -272,6 +274,18 @@ def fold(payloads, n: int, fmt, divisor: int = 1, out_dtype=None):
     return narrow(out.astype(np.float32), out_dtype)
 
 
+def refold(payloads, n: int, resid, fmt):
+    """The server round: ``(payload, r')`` — ``compress(fold(payloads, n, fmt),
+    resid, fmt)``, the float32 sum of 1..16 decodes in argument order (no
+    divide: a worker's fold of what it pulls applies the ``average`` divisor)
+    compressed against the server's float32 residual.  Nothing new is defined:
+    a source block with ``X == 255`` makes the sum's block NaN, an overflowed
+    sum makes it inf, and ``compress`` pins both — ``X = 255``, codes 0, ``r' =
+    0x7fc00000``.  The HIP kernel (``prophet_amd/csrc/bpsr_k_mx_refold.hip``)
+    is this line in one launch, the sum never written."""
+    return compress(fold(payloads, n, fmt), resid, fmt)
+
+
 __all__ = ["HEADER_BYTES", "BLOCK", "MAX_SRCS", "MAX_ELEMS", "bits_of", "scale_bytes",
            "code_bytes", "payload_bytes", "widen", "narrow", "encode", "value", "scales",
-           "quantise", "compress", "header", "fields", "decode", "fold"]
+           "quantise", "compress", "header", "fields", "decode", "fold", "refold"]

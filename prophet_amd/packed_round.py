@@ -1,17 +1,21 @@
 """The server round of a packed wire (``Compression.onebit_ef``, DESIGN.md
-§11.11): request type ``kCompressedPushPull``.
+§11.11; ``Compression.mxfp8_ef`` / ``mxfp4_ef``, §11.17): request type
+``kCompressedPushPull``.
 
-The element-wise server cannot fold a 1-bit payload.  ``PackedRound`` is the
-store ``ServerFrontend`` hands such requests to: per key it keeps one payload
-slot a worker, an f32 residual of its own, the output payload and a round
-counter.  The last arrival of a round runs ``OneBitEFCompressor.
-refold_many_into`` — decode the N payloads, sum, compress the sum against the
-store's residual — and every worker pulls one bit an element back.
+The element-wise server cannot fold a packed payload.  ``PackedRound`` is the
+store ``ServerFrontend`` hands such requests to: per key it keeps the key's
+compressor, one payload slot a worker, an f32 residual of its own, the output
+payload and a round counter.  The last arrival of a round runs the compressor's
+``refold_many_into`` — decode the N payloads, sum, compress the sum against the
+store's residual — and every worker pulls 1, 8.25 or 4.25 bits an element back.
+
+A key's wire is the first word of its init payload's header: 0 is the 1-bit
+wire (``{0.0f, n}``), 8 or 4 a block-scaled one (``{bits, n_lo, n_hi, 0}``).
 
 Keys live where their first pushed payload lives: a device (a cached refold
-plan, three launches on the store's own stream) or numpy on the host
-(``onebit.refold``).  Device work is ordered by events, never by a device-wide
-sync:
+plan on the store's own stream: three launches for the 1-bit wire, one for a
+block-scaled one) or numpy on the host (``onebit.refold``, ``mx.refold``).
+Device work is ordered by events, never by a device-wide sync:
 
 * a push copies into the worker's slot on the pusher's current stream, after
   the refold that last read the slot, and records the slot's event;
@@ -32,7 +36,11 @@ import threading
 import numpy as np
 
 from . import onebit
-from .compression import CastPlanCache, OneBitEFCompressor
+from .compression import (CastPlanCache, MXFP4EFCompressor, MXFP8EFCompressor,
+                          OneBitEFCompressor)
+
+# the first word of an init payload's header: the key's compressor
+_WIRES = {0: OneBitEFCompressor, 8: MXFP8EFCompressor, 4: MXFP4EFCompressor}
 
 
 def _is_device(x) -> bool:
@@ -48,8 +56,8 @@ def _host_bytes(x):
 class _Key:
     """One key's state; everything under ``cond``."""
 
-    def __init__(self, n: int, nbytes: int):
-        self.n, self.nbytes = n, nbytes
+    def __init__(self, comp, n: int, nbytes: int):
+        self.comp, self.n, self.nbytes = comp, n, nbytes
         self.cond = threading.Condition()
         self.inited: set = set()          # workers whose init push arrived
         self.arrived: set = set()         # workers that pushed the open round
@@ -64,13 +72,15 @@ class _Key:
 
 
 class PackedRound:
-    """The packed-payload store of ``num_workers`` workers."""
+    """The packed-payload store of ``num_workers`` workers; ``wires``: the
+    compressors whose keys it takes (the 1-bit wire unless named)."""
 
-    def __init__(self, num_workers: int):
+    def __init__(self, num_workers: int, wires=(OneBitEFCompressor,)):
         if int(num_workers) < 1 or int(num_workers) > onebit.MAX_SRCS:
             raise ValueError(f"a packed round takes 1..{onebit.MAX_SRCS} workers, "
                              f"got {num_workers}")
         self.num_workers = int(num_workers)
+        self.wires = tuple(wires)
         self._keys: dict = {}
         self._lock = threading.Lock()
         self._streams: dict = {}          # device -> the store's own stream
@@ -93,11 +103,16 @@ class PackedRound:
                 # the first init push: sizes come from the header it carries
                 if _is_device(data):
                     raise ValueError(f"key {key}: the init push is built on the host")
-                n = onebit.header(_host_bytes(data)[:onebit.HEADER_BYTES])[1]
-                if onebit.payload_bytes(n) != int(nbytes):
+                head = _host_bytes(data)[:onebit.HEADER_BYTES]
+                word, n = int(head[0:4].view("<u4")[0]), int(head[4:12].view("<u8")[0])
+                comp = _WIRES.get(word)
+                if comp not in self.wires:
+                    raise ValueError(f"key {key}: an init payload of a wire this store does not "
+                                     f"refold (header word {word:#x})")
+                if comp.payload_nbytes(n) != int(nbytes):
                     raise ValueError(f"key {key}: an init payload of {nbytes} bytes for {n} "
                                      f"elements")
-                k = self._keys[key] = _Key(n, int(nbytes))
+                k = self._keys[key] = _Key(comp, n, int(nbytes))
         if int(nbytes) != k.nbytes or _nbytes(data) != k.nbytes:
             raise ValueError(f"key {key}: a payload of {nbytes} bytes, the key's has {k.nbytes}")
         with k.cond:
@@ -164,7 +179,7 @@ class PackedRound:
     def _refold(self, k: _Key) -> None:
         """The round of one key, by its last arrival."""
         if k.device == "host":
-            OneBitEFCompressor.refold_many_into([k.out], [k.resid], [k.slots])
+            k.comp.refold_many_into([k.out], [k.resid], [k.slots])
             return
         import torch
         st = self._stream(k.device)
@@ -172,7 +187,7 @@ class PackedRound:
             st.wait_event(ev)
         k.pull_events = []
         with torch.cuda.stream(st):
-            OneBitEFCompressor.refold_many_into([k.out], [k.resid], [k.slots], plans=k.plans)
+            k.comp.refold_many_into([k.out], [k.resid], [k.slots], plans=k.plans)
         k.round_event = torch.cuda.Event()
         k.round_event.record(st)
 

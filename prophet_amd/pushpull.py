@@ -88,6 +88,9 @@ its own in a flat uint8 staging buffer, ``ServerFrontend`` hands the requests
 to its ``packed_round.PackedRound`` store — decode, sum, compress again against
 the store's residual — and one fold plan decodes what was pulled, dividing for
 ``average``.  ``stats``, ``clip_norm`` and ``apply`` refuse such a context.
+``Compression.mxfp8_ef`` / ``mxfp4_ef`` (float32 tensors)
+travel the same way over a front end that opts in:
+``ServerFrontend(server, size, packed_wires=(Compression.mxfp8_ef, ...))``.
 """
 from __future__ import annotations
 
@@ -108,12 +111,15 @@ class ServerFrontend:
     """The handler in front of the GPU-resident server: decodes the request
     word, checks one key per request (server.cc:150-171) and forwards."""
 
-    # kCompressedPushPull requests (packed payloads: Compression.onebit_ef) go
-    # to a store of this front end's own, packed_round.PackedRound
+    # kCompressedPushPull requests (packed payloads: Compression.onebit_ef, and
+    # the compressors named in ``packed_wires``) go to a store of this front
+    # end's own, packed_round.PackedRound
     carries_packed = True
 
-    def __init__(self, server, size: int | None = None):
+    def __init__(self, server, size: int | None = None, packed_wires=()):
         self.server = server
+        # extra packed compressors whose payloads the store refolds
+        self.packed_wires = tuple(packed_wires)
         cfg = getattr(server, "cfg", None)
         self.size = size if size is not None else (cfg.num_workers if cfg is not None else None)
         self.packed = None                   # the PackedRound, made on first use
@@ -128,7 +134,8 @@ class ServerFrontend:
                         raise ValueError("kCompressedPushPull: the frontend does not know the "
                                          "worker count")
                     from .packed_round import PackedRound
-                    self.packed = PackedRound(self.size)
+                    self.packed = PackedRound(
+                        self.size, (Compression.onebit_ef,) + self.packed_wires)
             return self.packed.push(key, worker, data, nbytes)
         if req != K_DEFAULT_PUSH_PULL:       # server.cc:151 CHECK_EQ(type.requestType, ...)
             raise ValueError(f"request type {req} is not kDefaultPushPull")
@@ -186,7 +193,8 @@ class Context:
 
 @dataclass
 class PackedState:
-    """``Context.extra`` of a packed context (``Compression.onebit_ef``): the
+    """``Context.extra`` of a packed context (``Compression.onebit_ef``,
+    ``mxfp8_ef``, ``mxfp4_ef``): the
     tensor-sized f32 residual and, per partition, ``(element offset, count,
     staging byte offset)`` — every partition a payload of its own in the flat
     uint8 staging buffer, at a 16-byte-aligned offset."""
@@ -417,8 +425,10 @@ class Worker:
         if getattr(compression, "PACKED", False):
             # the server folds element-wise by dtype; a packed payload needs a
             # round type of its own, which the front end carries
-            # — for the compressors whose payloads PackedRound decodes
-            if not getattr(compression, "SERVER_ROUND", False) or \
+            # — for the compressors whose payloads PackedRound decodes, and
+            # those the front end names in packed_wires
+            if not (getattr(compression, "SERVER_ROUND", False)
+                    or compression in getattr(self.frontend, "packed_wires", ())) or \
                     not getattr(self.frontend, "carries_packed", False):
                 raise ValueError(f"{name}: {compression.__name__} payloads do not travel through "
                                  f"push_pull yet; gather them and use fold_many_into")
@@ -456,10 +466,12 @@ class Worker:
         """``init_tensor`` of a packed context: the f32 tensor is cut under the
         partition bound as any other, and every partition travels as a payload
         of its own, with its own scale.  The init push of a key is the payload
-        of its partition's zeros, built on the host: the store's barrier."""
+        of its partition's zeros, built on the host by the compressor: the
+        store's barrier, and how the store learns the key's wire."""
         import numpy as np
-        from .onebit import HEADER_BYTES, payload_bytes
-        if not compression.compresses(data):
+        from .compression import _is_f32
+        payload_bytes = compression.payload_nbytes
+        if not _is_f32(data):
             raise ValueError(f"{name}: {compression.__name__} needs a float32 tensor")
         self.declare(name)
         ctx = self.contexts[name]
@@ -491,10 +503,7 @@ class Worker:
             ctx.extra = PackedState(resid, cuts)
             cmd = cantor_command(K_COMPRESSED_PUSH_PULL, ctx.dtype)
             for (key, _, ln), (_, cnt, _) in zip(ctx.parts, cuts):
-                zero = np.zeros(ln, dtype=np.uint8)
-                zero[4:12] = np.array([cnt], dtype="<u8").view(np.uint8)
-                assert ln >= HEADER_BYTES
-                self.frontend.push(cmd, key, self.rank, zero, ln)
+                self.frontend.push(cmd, key, self.rank, compression.init_payload(cnt), ln)
             ctx.initialized = True
         return ctx
 
@@ -770,11 +779,13 @@ class Worker:
         for c in ctxs:
             if c.compressor is not None and c.name not in pnames:
                 casts.setdefault(c.compressor, []).append(c)
-        # packed contexts: one compress plan over all their partitions
-        psegs = [s for c in packed for s in self._packed_segments(c, tensors[c.name])]
-        if psegs:
-            packed[0].compressor.compress_many_ef_into(
-                [p for _, _, p in psegs], [r for _, r, _ in psegs], [g for g, _, _ in psegs],
+        # packed contexts: one compress plan a compressor over all their partitions
+        psegs: dict = {}
+        for c in packed:
+            psegs.setdefault(c.compressor, []).extend(self._packed_segments(c, tensors[c.name]))
+        for comp, segs in psegs.items():
+            comp.compress_many_ef_into(
+                [p for _, _, p in segs], [r for _, r, _ in segs], [g for g, _, _ in segs],
                 plans=self._cast_plans)
         for comp, cs in casts.items():
             comp.compress_many_with([c.staging for c in cs],
@@ -794,10 +805,9 @@ class Worker:
                     self.frontend.pull(key, _slice(wire[c.name], off, ln), ln, worker=self.rank)
                 else:
                     self.frontend.pull(key, _slice(wire[c.name], off, ln), ln)
-        if psegs:                         # one fold plan (one source) over all of them
-            packed[0].compressor.fold_many_into([g for g, _, _ in psegs],
-                                                [[p] for _, _, p in psegs], divisor,
-                                                plans=self._cast_plans)
+        for comp, segs in psegs.items():  # one fold plan (one source) a compressor
+            comp.fold_many_into([g for g, _, _ in segs], [[p] for _, _, p in segs], divisor,
+                                plans=self._cast_plans)
         if apply is not None:
             self._apply_iteration(ctxs, casts, tensors, divisor, stats, clip_norm, clip_eps,
                                   unscale, apply)

@@ -83,6 +83,7 @@ EXPORTS = (
     "byteps_reduce_mx_rht_fold_plan_create", "byteps_reduce_mx_rht_fold_plan_launch",
     "byteps_reduce_mx_plan_create_typed", "byteps_reduce_mx_fold_plan_create_typed",
     "byteps_reduce_mx_sr_plan_create_typed", "byteps_reduce_mx_rht_fold_plan_create_typed",
+    "byteps_reduce_mx_refold_plan_create", "byteps_reduce_mx_refold_plan_launch",
     "byteps_reduce_powersgd_scratch_bytes", "byteps_reduce_powersgd_plan_create",
     "byteps_reduce_powersgd_plan_project_p", "byteps_reduce_powersgd_plan_orthogonalize",
     "byteps_reduce_powersgd_plan_project_q", "byteps_reduce_powersgd_plan_finish",
@@ -158,6 +159,12 @@ class MXDesc(ctypes.Structure):
 class MXFoldDesc(ctypes.Structure):
     """``byteps_mx_fold_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64)]
+
+
+class MxRefoldDesc(ctypes.Structure):
+    """``byteps_mx_refold_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("srcs", ctypes.POINTER(_vp)), ("resid", _vp), ("out", _vp),
+                ("nelem", ctypes.c_uint64)]
 
 
 class MXSRDesc(ctypes.Structure):
@@ -294,6 +301,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                     ctypes.POINTER(_vp)]
     L.byteps_reduce_mx_fold_plan_launch.argtypes = [_vp, _int, _vp]
     L.byteps_reduce_mx_plan_destroy.argtypes = [_vp]
+    L.byteps_reduce_mx_refold_plan_create.argtypes = [ctypes.POINTER(MxRefoldDesc), _int, _int,
+                                                      _int, ctypes.POINTER(_vp)]
+    L.byteps_reduce_mx_refold_plan_launch.argtypes = [_vp, _vp]
     L.byteps_reduce_mx_sr_plan_create.argtypes = [ctypes.POINTER(MXSRDesc), _int, _int, _int,
                                                   ctypes.POINTER(_vp)]
     L.byteps_reduce_mx_sr_plan_compress.argtypes = [_vp, ctypes.c_uint32, _vp]
@@ -550,6 +560,15 @@ class GpuReducer:
         FLOAT16 or BFLOAT16).  :meth:`MXFoldPlan.launch` is ONE launch:
         ``prophet_amd.mx.fold`` byte for byte."""
         return MXFoldPlan(self.lib, segments, nsrc, fmt, dtype)
+
+    def mx_refold_plan(self, segments: Sequence[tuple], nsrc: int, fmt: str) -> "MxRefoldPlan":
+        """The server round of the block-scaled error-feedback wires
+        (byteps_reduce_mx_refold_plan_create): ``segments`` are ``(payloads,
+        resid, out_payload, nelem)`` — ``nsrc`` (1..16) pushed payloads, the
+        server's flat float32 residual, the payload every worker pulls.
+        :meth:`MxRefoldPlan.launch` is ONE launch: ``prophet_amd.mx.refold``
+        byte for byte, the folded sum never written."""
+        return MxRefoldPlan(self.lib, segments, nsrc, fmt)
 
     def mx_sr_plan(self, segments: Sequence[tuple], fmt: str, rotate: bool = False,
                    dtype: int = DType.FLOAT32) -> "MXSRPlan":
@@ -1249,6 +1268,40 @@ class MXFoldPlan(_MXPlanBase):
         """One launch (byteps_reduce_mx_fold_plan_launch)."""
         _check(self.lib.byteps_reduce_mx_fold_plan_launch(self.handle, int(divisor),
                                                           _stream_of(self.first, stream)))
+
+
+class MxRefoldPlan(_MXPlanBase):
+    """A block-scaled refold plan (``byteps_reduce_mx_refold_plan_create``)."""
+
+    def __init__(self, lib, segments, nsrc, fmt):
+        from .mx import payload_bytes
+        super().__init__(lib, fmt)
+        self.nsrc = int(nsrc)
+        segments = [(list(s[0]), s[1], s[2], int(s[3])) for s in segments]
+        for payloads, resid, out, nelem in segments:
+            if nelem < 0:
+                raise ValueError(f"negative element count {nelem}")
+            if len(payloads) != self.nsrc:
+                raise ValueError(f"mx refold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
+            _fits(nelem * 4, resid)
+            _fits(payload_bytes(nelem, fmt), out, *payloads)
+        self._keep = segments
+        self.first = next((s[1] for s in segments if hasattr(s[1], "device")), None)
+        self.nsegs = len(segments)
+        descs = (MxRefoldDesc * max(1, len(segments)))()
+        rows = []                     # alive through the create call, which copies them
+        for d, (payloads, resid, out, nelem) in zip(descs, segments):
+            row = (_vp * max(1, len(payloads)))(*[_ptr(p) for p in payloads])
+            rows.append(row)
+            d.srcs, d.resid = ctypes.cast(row, ctypes.POINTER(_vp)), _ptr(resid)
+            d.out, d.nelem = _ptr(out), nelem
+        _check(lib.byteps_reduce_mx_refold_plan_create(descs, len(segments), self.nsrc, self.bits,
+                                                       ctypes.byref(self.handle)))
+
+    def launch(self, stream=None) -> None:
+        """One launch (byteps_reduce_mx_refold_plan_launch)."""
+        _check(self.lib.byteps_reduce_mx_refold_plan_launch(self.handle,
+                                                            _stream_of(self.first, stream)))
 
 
 class MXSRPlan(_MXPlanBase):

@@ -240,6 +240,10 @@ def main() -> int:
                    help="the 1-bit server round: the refold plan (fold in registers, finish, "
                         "pack) against the fold plan into a scratch f32 buffer followed by the "
                         "compress plan, 8 sources; the ResNet-50 table and one segment")
+    p.add_argument("--mx-refold", action="store_true",
+                   help="the block-scaled server round, fp8 and fp4: the one-launch refold plan "
+                        "against the fold plan into a scratch f32 buffer followed by the "
+                        "compress plan, 8 sources; the ResNet-50 table and one segment")
     p.add_argument("--topk", action="store_true",
                    help="top-k sparsification: the radix-select compress against torch's add, "
                         "topk(abs), gather and zero-scatter per tensor, and the 8-source fold "
@@ -280,6 +284,8 @@ def main() -> int:
         return topk_mode(args)
     if args.onebit_refold:
         return onebit_refold_mode(args)
+    if args.mx_refold:
+        return mx_refold_mode(args)
     if args.onebit:
         return onebit_mode(args)
     if args.sgd:
@@ -2373,6 +2379,122 @@ def onebit_refold_mode(args) -> int:
     ok = gates["big_refold_beats_composed"] and all(v for c in checks.values()
                                                     for v in c.values())
     return 0 if ok else 1
+
+
+def mx_refold_mode(args) -> int:
+    """The block-scaled server round, the --onebit-refold
+    protocol for both formats.  The refold plan against what it replaces on the
+    same commit: the 8-source fold plan into a scratch f32 buffer, then the
+    compress plan of that buffer against the residual.  Before timing both
+    produce the same output payload and residual bytes, twice over so that the
+    residual carries."""
+    import torch
+
+    from prophet_amd import mx
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    NSRC = 8
+    out = {"tool": "bench_compress", "mode": "mx*_ef refold against fold + compress",
+           "nsrc": NSRC, "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+
+    def shape(label, fmt, seg_rows, arena_elems):
+        nelem = sum(n for _, n in seg_rows)
+        counts = [n for _, n in seg_rows]
+        cut = lambda t: [t[o:o + n] for o, n in seg_rows]      # noqa: E731
+        pay_off, at = [], 0
+        for n in counts:                         # payloads are whole multiples of 16 bytes
+            pay_off.append(at)
+            at += mx.payload_bytes(n, fmt)
+        pcut = lambda t: [t[o:o + mx.payload_bytes(n, fmt)]    # noqa: E731
+                          for o, n in zip(pay_off, counts)]
+        with step(f"setup, {label}", 180):
+            g = torch.Generator(device=dev).manual_seed(11)
+            sets = []
+            for _ in range(args.sets):
+                s = {"r": torch.zeros(arena_elems, device=dev),        # the refold's residual
+                     "rc": torch.zeros(arena_elems, device=dev),       # the composition's
+                     "sum": torch.empty(arena_elems, device=dev),      # its scratch f32 sum
+                     "zero": torch.zeros(arena_elems, device=dev),
+                     "out": torch.empty(at, dtype=torch.uint8, device=dev),
+                     "outc": torch.empty(at, dtype=torch.uint8, device=dev),
+                     "pay": [torch.empty(at, dtype=torch.uint8, device=dev) for _ in range(NSRC)]}
+                for k in range(NSRC):            # the sources: NSRC compressed gradients
+                    gk = torch.randn(arena_elems, device=dev, generator=g)
+                    pl = red.mx_plan(list(zip(cut(gk), cut(s["zero"]), pcut(s["pay"][k]), counts)),
+                                     fmt)
+                    pl.compress()
+                    pl.close()
+                    s["zero"].zero_()
+                rows = [[pcut(s["pay"][k])[i] for k in range(NSRC)] for i in range(len(counts))]
+                s["refold"] = red.mx_refold_plan(
+                    list(zip(rows, cut(s["r"]), pcut(s["out"]), counts)), NSRC, fmt)
+                s["fold"] = red.mx_fold_plan(list(zip(cut(s["sum"]), rows, counts)), NSRC, fmt)
+                s["comp"] = red.mx_plan(list(zip(cut(s["sum"]), cut(s["rc"]), pcut(s["outc"]),
+                                                 counts)), fmt)
+                del s["zero"]
+                sets.append(s)
+            torch.cuda.synchronize()
+
+        def refold(k):
+            sets[k]["refold"].launch()
+
+        def composed(k):
+            sets[k]["fold"].launch(1)
+            sets[k]["comp"].compress()
+
+        with step(f"check, {label}", 180):
+            s = sets[0]
+            for _ in range(2):                   # twice: the residual carries
+                refold(0)
+                composed(0)
+            torch.cuda.synchronize()
+            checks[label] = {
+                "payload_bytes_equal": all(bool(torch.equal(a, b)) for a, b in
+                                           zip(pcut(s["out"]), pcut(s["outc"]))),
+                "residual_bytes_equal": bool(torch.equal(s["r"].view(torch.int32),
+                                                         s["rc"].view(torch.int32)))}
+        res = timed_rounds(torch, {"refold": (refold, args.inner),
+                                   "composed": (composed, args.inner)}, len(sets), args)
+        # bytes an element the designs move, from the definition: a payload is
+        # bits / 8 + 1 / 32; the refold reads N of them and r, writes one and r';
+        # the pair also writes and reads the f32 sum
+        pay = mx.bits_of(fmt) / 8 + 1 / 32
+        for name, per in (("refold", 8 + (NSRC + 1) * pay), ("composed", 16 + (NSRC + 1) * pay)):
+            res[name]["bytes_per_elem"] = per
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        sp = max(res["refold"]["spread_ms"], res["composed"]["spread_ms"])
+        gates[f"{label}_refold_beats_composed"] = res["composed"]["ms"] - res["refold"]["ms"] > sp
+        for s in sets:
+            for name in ("refold", "fold", "comp"):
+                s[name].close()
+        return {"fmt": fmt, "segments": len(seg_rows), "elems": nelem, "results": res}
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    total_bytes, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    for fmt in ("fp8", "fp4"):
+        out[f"iteration_{fmt}"] = shape(f"table_{fmt}", fmt,
+                                        [(o // 2, ln // 2) for o, ln in rows], total_bytes // 2)
+        torch.cuda.empty_cache()
+        out[f"big_{fmt}"] = shape(f"big_{fmt}", fmt, [(0, args.elems)], args.elems)
+        torch.cuda.empty_cache()
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    # the bytes must agree; the ratio is a recorded fact (DESIGN.md §11.17)
+    return 0 if all(v for c in checks.values() for v in c.values()) else 1
 
 
 def end_to_end(nelem: int, iters: int, where: str) -> dict:
