@@ -98,7 +98,10 @@ extern "C" {
  *                       wires over FLOAT16 and BFLOAT16 tensors)
  *    additive, still 5: byteps_reduce_mx_refold_plan_create / _launch
  *                       (byteps_mx_refold_desc: the server round of the
- *                       block-scaled error-feedback wires) */
+ *                       block-scaled error-feedback wires)
+ *    additive, still 5: byteps_reduce_topk_refold_plan_create / _launch
+ *                       (byteps_topk_refold_desc: the server round of the
+ *                       top-k wire) */
 #define BYTEPS_REDUCE_ABI_VERSION 5
 
 /* Data type ids: byteps/common/common.h:52-65 (mshadow order), plus bf16 as a
@@ -804,6 +807,44 @@ int byteps_reduce_topk_fold_plan_create(const byteps_topk_fold_desc* segs, int n
                                         byteps_reduce_topk_plan** out);
 int byteps_reduce_topk_fold_plan_launch(byteps_reduce_topk_plan* plan, int divisor, void* stream);
 int byteps_reduce_topk_plan_destroy(byteps_reduce_topk_plan* plan);
+
+/* The server round of the top-k wire (the definition is
+ * prophet_amd/topk.py's refold, byte for byte).  A segment is one key: `srcs`
+ * are the nsrc (1..16) payloads the workers pushed, all of n FLOAT32 elements
+ * and k entries; `resid` is the server's FLOAT32 residual of n elements; `out`
+ * is the payload of k entries every worker pulls.  The round is the compress
+ * above of the fold above, with divisor 1:
+ *
+ *   c_i = (+0.0 + s_0,i + s_1,i + ... + s_{nsrc-1},i) + r_i   the adds in argument order
+ *
+ * then T, sel and r'_i as a compress gives them, r' written over r and one
+ * payload to `out`.  The server does not divide; a worker's fold of what it
+ * pulled does.  _launch is the compress's fixed sequence of launches on
+ * `stream` with the fold fused into its first pass: the sum lives in LDS and is
+ * never written, and there is no host synchronisation.  Sizes come from the
+ * plan, a source's header is never read: a malformed source gives wrong values,
+ * but no write outside `resid` and `out` and no read outside its 16 + 8 k
+ * bytes.  The plan is a byteps_reduce_topk_plan of a kind of its own: it owns
+ * the compress's scratch, runs one round at a time and is freed by
+ * _plan_destroy.  nelem == 0 (then k == 0) writes a bare header to `out`.
+ *
+ * EARGS before any HIP call, every buffer untouched: nsrc outside 1..16, a null
+ * pointer with nelem > 0, k outside 1..nelem, nelem > 2^31, a residual that is
+ * not 4-byte aligned, a payload (source or output) that is not 16-byte aligned,
+ * any two byte ranges of a plan's operands overlapping (the output payload
+ * aliases no source, no residual and no other segment's payload), a null plan,
+ * a _refold_plan_launch on a plan of another kind or another launch on this
+ * one. */
+typedef struct byteps_topk_refold_desc {
+  const void* const* srcs; /* nsrc of them; read by _refold_plan_create alone */
+  void* resid;
+  void* out;
+  uint64_t nelem;
+  uint64_t k;
+} byteps_topk_refold_desc;
+int byteps_reduce_topk_refold_plan_create(const byteps_topk_refold_desc* segs, int nsegs,
+                                          int nsrc, byteps_reduce_topk_plan** out);
+int byteps_reduce_topk_refold_plan_launch(byteps_reduce_topk_plan* plan, void* stream);
 
 /* Block-scaled 8- and 4-bit wires with error feedback: every
  * 32 consecutive elements share one power-of-two scale, an E8M0 byte, and travel

@@ -139,8 +139,10 @@ deterministic tie rule (the lowest indices win) and no floating-point
 reduction.  ``payload_like(tensor, ratio)`` sizes the payload, which carries
 its ``k`` in its size; ``compress_many_ef_into`` is one fixed sequence of
 launches per device, ``fold_many_into`` adds up to 16 sparse payloads per
-output in one.  There is no server round for it: ``Worker.init_tensor`` refuses
-this compressor over every front end.
+output in one.  Its server round is opt-in and needs a ratio (DESIGN.md
+§11.18): ``Compression.topk_ef.at(ratio)`` named in a front end's
+``packed_wires``, ``refold_many_into`` on the store; without a ratio
+``Worker.init_tensor`` refuses this compressor over every front end.
 
 ``Compression.mxfp8_ef`` and ``Compression.mxfp4_ef`` sit between the 2-byte
 wires and those two: every 32 consecutive elements share one
@@ -411,6 +413,15 @@ class CastPlanCache:
             + tuple(int(p.data_ptr()) for p in ps) for o, ps in segs)
         return self._get(key, lambda: _new_topk_fold_plan(segs, nsrc))
 
+    def get_topk_refold(self, segs, nsrc: int):
+        """The top-k refold plan (``GpuReducer.topk_refold_plan``) over ``segs``
+        of ``(payloads, resid, out_payload)`` device tensors on the current
+        device; ``k`` is the output payload's (``topk.k_of``)."""
+        key = ("topk_refold", int(nsrc)) + tuple(
+            (int(r.data_ptr()), int(o.data_ptr()), int(r.numel()), int(o.numel()))
+            + tuple(int(p.data_ptr()) for p in ps) for ps, r, o in segs)
+        return self._get(key, lambda: _new_topk_refold_plan(segs, nsrc))
+
     def get_mx(self, segs, fmt: str, dtype: int = 0):
         """The block-scaled compress plan (``GpuReducer.mx_plan``) over ``segs``
         of flat ``(grad, resid, payload)`` device tensors on the current device,
@@ -513,6 +524,13 @@ def _new_topk_fold_plan(segs, nsrc: int):
     from .topk import k_of
     from .torch_ops import _red
     return _red().topk_fold_plan([(o, ps, int(o.numel()), k_of(ps[0])) for o, ps in segs], nsrc)
+
+
+def _new_topk_refold_plan(segs, nsrc: int):
+    from .topk import k_of
+    from .torch_ops import _red
+    return _red().topk_refold_plan([(ps, r, o, int(r.numel()), k_of(o)) for ps, r, o in segs],
+                                   nsrc)
 
 
 def _new_onebit_plan(segs):
@@ -1574,24 +1592,63 @@ class TopKEFCompressor(Compressor):
     ``topk.py``, byte for byte the same.  Everything but float32 passes
     through.
 
-    The PS server cannot fold a sparse payload and there is no server round
-    for it yet: ``Worker.init_tensor`` refuses this compressor over every
-    front end.  ``fold_many_into`` is what a worker that gathered every
-    worker's payload computes."""
+    The server round is opt-in and needs a ratio: a key's
+    payload size follows from ``n`` and the ratio, so ``Worker.init_tensor``
+    takes ``TopKEFCompressor.at(ratio)`` — a cached subclass carrying
+    ``RATIO``, with ``payload_nbytes`` and ``init_payload`` — over a
+    ``ServerFrontend`` that names that same class in ``packed_wires``; its
+    ``packed_round.PackedRound`` store then runs ``refold_many_into`` (the
+    compress's launches with the fold fused into the first pass).  This class
+    itself, which has no ratio, is refused over every front end.
+    ``fold_many_into`` is what a worker that gathered every worker's payload
+    computes."""
 
     ERROR_FEEDBACK = True
     PACKED = True
+    RATIO = None                          # set by at(ratio)
+    _AT: dict = {}                        # ratio -> its subclass
+
+    @classmethod
+    def at(cls, ratio: float):
+        """The subclass of this compressor at ``ratio``, the same object for
+        the same ratio (so ``in packed_wires`` and grouping by compressor
+        work)."""
+        ratio = float(ratio)
+        if not 0 < ratio <= 1:
+            raise ValueError(f"topk_ef: ratio {ratio} outside (0, 1]")
+        sub = TopKEFCompressor._AT.get(ratio)
+        if sub is None:
+            sub = TopKEFCompressor._AT[ratio] = type(
+                f"TopKEFCompressor_{ratio!r}", (TopKEFCompressor,), {"RATIO": ratio})
+        return sub
+
+    @classmethod
+    def payload_nbytes(cls, n: int) -> int:
+        """The bytes of the payload of ``n`` elements at ``RATIO``."""
+        from .topk import k_for, payload_bytes
+        if cls.RATIO is None:
+            raise ValueError("topk_ef: a payload's size needs a ratio (TopKEFCompressor.at)")
+        return payload_bytes(k_for(n, cls.RATIO) if int(n) else 0)
+
+    @classmethod
+    def init_payload(cls, n: int):
+        """What a key's init push carries: ``topk.init_payload`` at ``k =
+        k_for(n, RATIO)``."""
+        from . import topk
+        return topk.init_payload(n, (cls.payload_nbytes(n) - topk.HEADER_BYTES) // 8)
 
     @classmethod
     def compresses(cls, tensor) -> bool:
         return _is_f32(tensor)
 
     @classmethod
-    def payload_like(cls, x, ratio: float = 0.01):
+    def payload_like(cls, x, ratio: float | None = None):
         """An uninitialised payload buffer for x at ``k = topk.k_for(n,
-        ratio)``, of x's kind and device."""
+        ratio)`` (``RATIO``, else 0.01, unless named), of x's kind and
+        device."""
         from .topk import k_for, payload_bytes
         n = int(x.numel()) if _is_torch(x) else int(x.size)
+        ratio = (cls.RATIO or 0.01) if ratio is None else ratio
         size = payload_bytes(k_for(n, ratio) if n else 0)
         if _is_torch(x):
             import torch
@@ -1601,7 +1658,7 @@ class TopKEFCompressor(Compressor):
     residual_like = classmethod(_ErrorFeedback.residual_like.__func__)
 
     @classmethod
-    def compress(cls, tensor, ratio: float = 0.01):
+    def compress(cls, tensor, ratio: float | None = None):
         """The stateless form: one step from a zero residual, which is
         dropped.  ``ctx`` is ``(dtype, shape)``."""
         ctx = (tensor.dtype, tuple(tensor.shape))
@@ -1693,6 +1750,48 @@ class TopKEFCompressor(Compressor):
         OneBitEFCompressor._run(groups, plans, lambda cache, segs: cache.get_topk_fold(segs, nsrc),
                                 lambda plan, stream: plan.launch(int(divisor), stream=stream))
         return outs
+
+    @classmethod
+    def refold_many_into(cls, out_payloads, residuals, payload_lists,
+                         plans: CastPlanCache | None = None):
+        """The server round: ``out_payloads[i], residuals[i] =
+        topk.refold(payload_lists[i], residuals[i].size, residuals[i], k)`` for
+        every i — every list of the same length N, 1..16, ``k`` the payloads'
+        size (a segment's sources and output of one size), the float32
+        residual in place — the device tensors as one top-k refold plan per
+        device (the compress's launches, the folded sum never written);
+        returns ``out_payloads``."""
+        from . import topk
+        if len(out_payloads) != len(payload_lists) or len(residuals) != len(payload_lists):
+            raise ValueError("refold_many_into: as many output payloads and residuals as "
+                             "payload lists")
+        nsrc = len(payload_lists[0]) if payload_lists else 1
+        if not 1 <= nsrc <= topk.MAX_SRCS or any(len(ps) != nsrc for ps in payload_lists):
+            raise ValueError(f"refold_many_into: every segment takes the same "
+                             f"1..{topk.MAX_SRCS} payloads")
+        groups: dict = {}
+        for i, (o, r, ps) in enumerate(zip(out_payloads, residuals, payload_lists)):
+            if not _is_f32(r):
+                raise ValueError(f"topk_ef: residual {i} must be float32, got {r.dtype}")
+            dev = [_on_device(x) for x in [o, r] + list(ps)]
+            if any(dev) != all(dev):
+                raise ValueError(f"topk_ef: segment {i}'s operands live in one place, a device "
+                                 f"or the host")
+            if len({topk.k_of(p) for p in [o] + list(ps)}) != 1:
+                raise ValueError(f"topk_ef: segment {i}'s payloads differ in size")
+            if dev[0]:
+                for p in [o] + list(ps):
+                    cls._check_device_segment(i, r, payload=p)
+                groups.setdefault(r.device, []).append((list(ps), r.reshape(-1), o))
+                continue
+            ra = (r.detach().numpy() if _is_torch(r) else r).reshape(-1)
+            oa = _payload_array(o)
+            oa[:], ra[:] = topk.refold([_payload_array(p) for p in ps], ra.size, ra,
+                                       topk.k_of(oa))
+        OneBitEFCompressor._run(groups, plans,
+                                lambda cache, segs: cache.get_topk_refold(segs, nsrc),
+                                lambda plan, stream: plan.launch(stream=stream))
+        return out_payloads
 
     @staticmethod
     def _check_device_segment(i: int, tensor, resid=None, payload=None) -> None:

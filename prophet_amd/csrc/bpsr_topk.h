@@ -12,7 +12,8 @@
 // one table of tiles, ordered by the stream alone:
 //   ZERO, ACCUMULATE-HISTOGRAM, PICK 0, REFINE 1, PICK 1, REFINE 2, PICK 2,
 //   COUNT, SCAN, COMPACT
-// A fold is one launch over a table of output tiles.
+// A fold is one launch over a table of output tiles.  A refold — the server
+// round — is the compress's ten with the fold fused into the second.
 #pragma once
 
 #include "bpsr_internal.h"
@@ -88,9 +89,23 @@ struct TopKFold {
   int divisor;
 };
 
+// The server round: a compress whose records name the
+// server's residual twice (a == b) and whose gradient is the sparse sum of row
+// `seg` of `srcs`, formed in LDS by the first pass and never written.
+struct TopKRefold {
+  TopKCompress c;
+  const unsigned char* const* srcs;  // [nsegs * nsrc] payloads, a segment's row in argument order
+  int nsrc;
+};
+
 // The ten launches on `s`; `resid_bytes`: what ACCUMULATE writes (store policy).
 hipError_t launch_topk_compress(const TopKCompress& p, uint64_t resid_bytes, const Tuning& tu,
                                 hipStream_t s);
+// The same ten with REFOLD-ACCUMULATE (bpsr_k_topk_refold.hip) in ACCUMULATE's place.
+hipError_t launch_topk_refold(const TopKRefold& p, uint64_t resid_bytes, const Tuning& tu,
+                              hipStream_t s);
+// That one launch alone, p.c.nrecs > 0; `pol`: kPolWt or kPolNt.
+hipError_t launch_topk_refold_accum(const TopKRefold& p, int pol, hipStream_t s);
 // The fold; `out_bytes`: what it writes (store policy).
 hipError_t launch_topk_fold(const TopKFold& p, uint64_t out_bytes, const Tuning& tu,
                             hipStream_t s);

@@ -1,5 +1,6 @@
 """The server round of a packed wire (``Compression.onebit_ef``, DESIGN.md
-§11.11; ``Compression.mxfp8_ef`` / ``mxfp4_ef``, §11.17): request type
+§11.11; ``Compression.mxfp8_ef`` / ``mxfp4_ef``, §11.17;
+``Compression.topk_ef.at(ratio)``, §11.18): request type
 ``kCompressedPushPull``.
 
 The element-wise server cannot fold a packed payload.  ``PackedRound`` is the
@@ -9,12 +10,19 @@ payload and a round counter.  The last arrival of a round runs the compressor's
 ``refold_many_into`` — decode the N payloads, sum, compress the sum against the
 store's residual — and every worker pulls 1, 8.25 or 4.25 bits an element back.
 
-A key's wire is the first word of its init payload's header: 0 is the 1-bit
-wire (``{0.0f, n}``), 8 or 4 a block-scaled one (``{bits, n_lo, n_hi, 0}``).
+A key's wire is read from its init payload's header.  The fourth word first:
+``topk.INIT_TAG`` there is a top-k key (``{k, n_lo, n_hi, tag}``; ``k`` may be
+0, 4 or 8 like any other number, so the first word cannot name this wire), its
+compressor the ``TopKEFCompressor.at(ratio)`` among the store's wires whose
+payload of ``n`` elements has those ``16 + 8 k`` bytes.  Every other wire leaves
+that word zero and is named by the first: 0 is the 1-bit wire (``{0.0f, n}``),
+8 or 4 a block-scaled one (``{bits, n_lo, n_hi, 0}``).  Init payloads are never
+folded, so the tag reaches no kernel.
 
 Keys live where their first pushed payload lives: a device (a cached refold
 plan on the store's own stream: three launches for the 1-bit wire, one for a
-block-scaled one) or numpy on the host (``onebit.refold``, ``mx.refold``).
+block-scaled one, the compress's ten for top-k) or numpy on the host
+(``onebit.refold``, ``mx.refold``, ``topk.refold``).
 Device work is ordered by events, never by a device-wide sync:
 
 * a push copies into the worker's slot on the pusher's current stream, after
@@ -35,9 +43,9 @@ import threading
 
 import numpy as np
 
-from . import onebit
+from . import onebit, topk
 from .compression import (CastPlanCache, MXFP4EFCompressor, MXFP8EFCompressor,
-                          OneBitEFCompressor)
+                          OneBitEFCompressor, TopKEFCompressor)
 
 # the first word of an init payload's header: the key's compressor
 _WIRES = {0: OneBitEFCompressor, 8: MXFP8EFCompressor, 4: MXFP4EFCompressor}
@@ -105,8 +113,18 @@ class PackedRound:
                     raise ValueError(f"key {key}: the init push is built on the host")
                 head = _host_bytes(data)[:onebit.HEADER_BYTES]
                 word, n = int(head[0:4].view("<u4")[0]), int(head[4:12].view("<u8")[0])
-                comp = _WIRES.get(word)
-                if comp not in self.wires:
+                if int(head[12:16].view("<u4")[0]) == topk.INIT_TAG:
+                    # a top-k key: the first word is its k, any of 1..n
+                    if not 1 <= word <= n or int(nbytes) != topk.payload_bytes(word):
+                        raise ValueError(f"key {key}: a top-k init payload of {nbytes} bytes for "
+                                         f"k {word} of {n} elements")
+                    tk = [w for w in self.wires
+                          if isinstance(w, type) and issubclass(w, TopKEFCompressor)]
+                    comp = next((w for w in tk if w.RATIO is not None
+                                 and w.payload_nbytes(n) == int(nbytes)), None)
+                else:
+                    comp = _WIRES.get(word)
+                if comp is None or comp not in self.wires:
                     raise ValueError(f"key {key}: an init payload of a wire this store does not "
                                      f"refold (header word {word:#x})")
                 if comp.payload_nbytes(n) != int(nbytes):

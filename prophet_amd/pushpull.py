@@ -91,6 +91,11 @@ the store's residual — and one fold plan decodes what was pulled, dividing for
 ``Compression.mxfp8_ef`` / ``mxfp4_ef`` (float32 tensors)
 travel the same way over a front end that opts in:
 ``ServerFrontend(server, size, packed_wires=(Compression.mxfp8_ef, ...))``.
+So does the top-k wire at a ratio: ``TK =
+Compression.topk_ef.at(ratio)`` in ``packed_wires`` and as ``init_tensor``'s
+``compression``; a partition of ``cnt`` elements travels as ``16 + 8
+k_for(cnt, ratio)`` bytes.  Plain ``Compression.topk_ef`` has no ratio and is
+refused over every front end.
 """
 from __future__ import annotations
 
@@ -194,7 +199,7 @@ class Context:
 @dataclass
 class PackedState:
     """``Context.extra`` of a packed context (``Compression.onebit_ef``,
-    ``mxfp8_ef``, ``mxfp4_ef``): the
+    ``mxfp8_ef``, ``mxfp4_ef``, ``topk_ef.at(ratio)``): the
     tensor-sized f32 residual and, per partition, ``(element offset, count,
     staging byte offset)`` — every partition a payload of its own in the flat
     uint8 staging buffer, at a 16-byte-aligned offset."""

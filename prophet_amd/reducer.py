@@ -76,6 +76,7 @@ EXPORTS = (
     "byteps_reduce_topk_payload_bytes", "byteps_reduce_topk_plan_create",
     "byteps_reduce_topk_plan_compress", "byteps_reduce_topk_fold_plan_create",
     "byteps_reduce_topk_fold_plan_launch", "byteps_reduce_topk_plan_destroy",
+    "byteps_reduce_topk_refold_plan_create", "byteps_reduce_topk_refold_plan_launch",
     "byteps_reduce_mx_payload_bytes", "byteps_reduce_mx_plan_create",
     "byteps_reduce_mx_plan_compress", "byteps_reduce_mx_fold_plan_create",
     "byteps_reduce_mx_fold_plan_launch", "byteps_reduce_mx_plan_destroy",
@@ -149,6 +150,12 @@ class TopKFoldDesc(ctypes.Structure):
     """``byteps_topk_fold_desc`` (include/bpsr/reduce.h)."""
     _fields_ = [("out", _vp), ("payloads", ctypes.POINTER(_vp)), ("nelem", ctypes.c_uint64),
                 ("k", ctypes.c_uint64)]
+
+
+class TopKRefoldDesc(ctypes.Structure):
+    """``byteps_topk_refold_desc`` (include/bpsr/reduce.h)."""
+    _fields_ = [("srcs", ctypes.POINTER(_vp)), ("resid", _vp), ("out", _vp),
+                ("nelem", ctypes.c_uint64), ("k", ctypes.c_uint64)]
 
 
 class MXDesc(ctypes.Structure):
@@ -292,6 +299,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                       ctypes.POINTER(_vp)]
     L.byteps_reduce_topk_fold_plan_launch.argtypes = [_vp, _int, _vp]
     L.byteps_reduce_topk_plan_destroy.argtypes = [_vp]
+    L.byteps_reduce_topk_refold_plan_create.argtypes = [ctypes.POINTER(TopKRefoldDesc), _int,
+                                                        _int, ctypes.POINTER(_vp)]
+    L.byteps_reduce_topk_refold_plan_launch.argtypes = [_vp, _vp]
     L.byteps_reduce_mx_payload_bytes.argtypes = [ctypes.c_uint64, _int]
     L.byteps_reduce_mx_payload_bytes.restype = ctypes.c_uint64
     L.byteps_reduce_mx_plan_create.argtypes = [ctypes.POINTER(MXDesc), _int, _int,
@@ -539,6 +549,15 @@ class GpuReducer:
         payloads each, added in that order.  :meth:`TopKFoldPlan.launch` is ONE
         launch: ``prophet_amd.topk.fold`` byte for byte."""
         return TopKFoldPlan(self.lib, segments, nsrc)
+
+    def topk_refold_plan(self, segments: Sequence[tuple], nsrc: int) -> "TopKRefoldPlan":
+        """The server round of the top-k wire
+        (byteps_reduce_topk_refold_plan_create): ``segments`` are ``(payloads,
+        resid, out, nelem, k)`` with ``nsrc`` pushed payloads each, the
+        server's float32 residual and the output payload, all of ``k`` entries.
+        :meth:`TopKRefoldPlan.launch` is the compress's launches with the fold
+        fused into the first pass: ``prophet_amd.topk.refold`` byte for byte."""
+        return TopKRefoldPlan(self.lib, segments, nsrc)
 
     def mx_plan(self, segments: Sequence[tuple], fmt: str,
                 dtype: int = DType.FLOAT32) -> "MXPlan":
@@ -1185,6 +1204,39 @@ class TopKFoldPlan(_TopKPlanBase):
         """One launch (byteps_reduce_topk_fold_plan_launch)."""
         _check(self.lib.byteps_reduce_topk_fold_plan_launch(self.handle, int(divisor),
                                                             _stream_of(self.first, stream)))
+
+
+class TopKRefoldPlan(_TopKPlanBase):
+    """A top-k refold plan (``byteps_reduce_topk_refold_plan_create``)."""
+
+    def __init__(self, lib, segments, nsrc):
+        super().__init__(lib)
+        self.nsrc = int(nsrc)
+        segments = [(list(s[0]), s[1], s[2], int(s[3]), int(s[4])) for s in segments]
+        for payloads, resid, out, nelem, k in segments:
+            if nelem < 0 or k < 0:
+                raise ValueError(f"negative count in ({nelem}, {k})")
+            if len(payloads) != self.nsrc:
+                raise ValueError(f"topk refold plan: {len(payloads)} payloads, nsrc {self.nsrc}")
+            _fits(nelem * 4, resid)
+            _fits(16 + 8 * k, out, *payloads)
+        self._keep = segments
+        self.first = next((s[1] for s in segments if hasattr(s[1], "device")), None)
+        self.nsegs = len(segments)
+        descs = (TopKRefoldDesc * max(1, len(segments)))()
+        rows = []                     # alive through the create call, which copies them
+        for d, (payloads, resid, out, nelem, k) in zip(descs, segments):
+            row = (_vp * max(1, len(payloads)))(*[_ptr(p) for p in payloads])
+            rows.append(row)
+            d.srcs, d.resid = ctypes.cast(row, ctypes.POINTER(_vp)), _ptr(resid)
+            d.out, d.nelem, d.k = _ptr(out), nelem, k
+        _check(lib.byteps_reduce_topk_refold_plan_create(descs, len(segments), self.nsrc,
+                                                         ctypes.byref(self.handle)))
+
+    def launch(self, stream=None) -> None:
+        """The round (byteps_reduce_topk_refold_plan_launch)."""
+        _check(self.lib.byteps_reduce_topk_refold_plan_launch(self.handle,
+                                                              _stream_of(self.first, stream)))
 
 
 class _MXPlanBase(_OneBitPlanBase):

@@ -25,6 +25,9 @@ out[idx_s] + val_s`` (one float32 add each), then one divide by
 ``f32(divisor)`` when ``divisor > 1``.  Sizes come from the caller (``k`` from
 the payload's byte count when not given): a header is never trusted.  There is
 no floating-point reduction anywhere in the scheme, so every byte is pinned.
+
+``refold(payloads, n, r, k)`` is the server round: ``compress(fold(payloads, n,
+1, k), r, k)`` against the server's own residual — nothing new is defined.
 """
 from __future__ import annotations
 
@@ -35,6 +38,9 @@ import numpy as np
 HEADER_BYTES = 16
 MAX_SRCS = 16
 MAX_ELEMS = 1 << 31
+# the fourth header word of a key's init payload ("topk"): how the packed-round
+# store tells a top-k key from the wires whose first header word names them
+INIT_TAG = 0x6b706f74
 
 
 def payload_bytes(k: int) -> int:
@@ -151,5 +157,27 @@ def fold(payloads, n: int, divisor: int = 1, k: int | None = None):
     return out.astype(np.float32)
 
 
-__all__ = ["HEADER_BYTES", "MAX_SRCS", "MAX_ELEMS", "payload_bytes", "k_for", "k_of", "keys",
-           "select", "compress", "header", "entries", "decode", "fold"]
+def refold(payloads, n: int, resid, k: int | None = None):
+    """The server round: ``compress(fold(payloads, n, 1,
+    k), resid, k)`` — ``(payload, r')`` as new arrays.  1..16 payloads of the
+    same ``k`` (from their byte count when not given), folded left in argument
+    order from +0.0; the server does not divide."""
+    if k is None:
+        k = k_of(np.ascontiguousarray(payloads[0]).reshape(-1).view(np.uint8)) if payloads else 0
+    return compress(fold(payloads, n, 1, k), resid, k)
+
+
+def init_payload(n: int, k: int):
+    """What a key's init push carries (``packed_round.PackedRound``): the
+    compress of ``n`` zeros — indices 0..k-1, values +0.0 — with ``INIT_TAG``
+    in the fourth header word, which every other wire's init header, and every
+    payload a kernel reads or writes, leaves zero.  It is never folded."""
+    z = np.zeros(int(n), dtype=np.float32)
+    payload, _ = compress(z, z, int(k))
+    payload[12:16] = np.array([INIT_TAG], dtype="<u4").view(np.uint8)
+    return payload
+
+
+__all__ = ["HEADER_BYTES", "MAX_SRCS", "MAX_ELEMS", "INIT_TAG", "payload_bytes", "k_for", "k_of",
+           "keys", "select", "compress", "header", "entries", "decode", "fold", "refold",
+           "init_payload"]

@@ -244,6 +244,11 @@ def main() -> int:
                    help="the block-scaled server round, fp8 and fp4: the one-launch refold plan "
                         "against the fold plan into a scratch f32 buffer followed by the "
                         "compress plan, 8 sources; the ResNet-50 table and one segment")
+    p.add_argument("--topk-refold", action="store_true",
+                   help="the top-k server round at ratios 0.01 and 0.001: the refold plan (the "
+                        "sparse sum in LDS inside the select's first pass) against the fold plan "
+                        "into a scratch f32 buffer followed by the compress plan, 8 sources; the "
+                        "ResNet-50 table and one segment")
     p.add_argument("--topk", action="store_true",
                    help="top-k sparsification: the radix-select compress against torch's add, "
                         "topk(abs), gather and zero-scatter per tensor, and the 8-source fold "
@@ -280,6 +285,8 @@ def main() -> int:
         return mx_mode(args)
     if args.mx_sr:
         return mx_sr_mode(args)
+    if args.topk_refold:
+        return topk_refold_mode(args)
     if args.topk:
         return topk_mode(args)
     if args.onebit_refold:
@@ -2494,6 +2501,127 @@ def mx_refold_mode(args) -> int:
         with open(args.out, "a") as f:
             f.write(line + "\n")
     # the bytes must agree; the ratio is a recorded fact
+    return 0 if all(v for c in checks.values() for v in c.values()) else 1
+
+
+def topk_refold_mode(args) -> int:
+    """The top-k server round, the --mx-refold protocol at
+    ratios 0.01 and 0.001.  The refold plan against what it replaces on the same
+    commit: the 8-source fold plan into a scratch f32 buffer, then the compress
+    plan of that buffer against the residual.  Before timing both produce the
+    same output payload and residual bytes, twice over so that the residual
+    carries."""
+    import torch
+
+    from prophet_amd import topk
+    from prophet_amd.reducer import GpuReducer
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"error": "no GPU: nothing is measured without one"}))
+        return 2
+    dev = torch.device("cuda:0")
+    NSRC = 8
+    out = {"tool": "bench_compress", "mode": "topk_ef refold against fold + compress",
+           "nsrc": NSRC, "sets": args.sets, "rounds": args.rounds, "inner": args.inner,
+           "device": torch.cuda.get_device_name(0)}
+    gates, checks = {}, {}
+
+    def shape(label, ratio, seg_rows, arena_elems):
+        counts = [n for _, n in seg_rows]
+        ks = [topk.k_for(n, ratio) for n in counts]
+        nelem, ktot = sum(counts), sum(ks)
+        cut = lambda t: [t[o:o + n] for o, n in seg_rows]      # noqa: E731
+        pay_off, at = [], 0
+        for k in ks:                             # every payload at a 16-byte boundary
+            pay_off.append(at)
+            at += (topk.payload_bytes(k) + 15) & ~15
+        pcut = lambda t: [t[o:o + topk.payload_bytes(k)]       # noqa: E731
+                          for o, k in zip(pay_off, ks)]
+        with step(f"setup, {label}", 180):
+            g = torch.Generator(device=dev).manual_seed(11)
+            sets = []
+            for _ in range(args.sets):
+                s = {"r": torch.zeros(arena_elems, device=dev),        # the refold's residual
+                     "rc": torch.zeros(arena_elems, device=dev),       # the composition's
+                     "sum": torch.empty(arena_elems, device=dev),      # its scratch f32 sum
+                     "zero": torch.zeros(arena_elems, device=dev),
+                     "out": torch.empty(at, dtype=torch.uint8, device=dev),
+                     "outc": torch.empty(at, dtype=torch.uint8, device=dev),
+                     "pay": [torch.empty(at, dtype=torch.uint8, device=dev) for _ in range(NSRC)]}
+                for j in range(NSRC):            # the sources: NSRC compressed gradients
+                    gj = torch.randn(arena_elems, device=dev, generator=g)
+                    pl = red.topk_plan(list(zip(cut(gj), cut(s["zero"]), pcut(s["pay"][j]),
+                                                counts, ks)))
+                    pl.compress()
+                    pl.close()
+                    s["zero"].zero_()
+                rows = [[pcut(s["pay"][j])[i] for j in range(NSRC)] for i in range(len(counts))]
+                s["refold"] = red.topk_refold_plan(
+                    list(zip(rows, cut(s["r"]), pcut(s["out"]), counts, ks)), NSRC)
+                s["fold"] = red.topk_fold_plan(list(zip(cut(s["sum"]), rows, counts, ks)), NSRC)
+                s["comp"] = red.topk_plan(list(zip(cut(s["sum"]), cut(s["rc"]), pcut(s["outc"]),
+                                                   counts, ks)))
+                del s["zero"]
+                sets.append(s)
+            torch.cuda.synchronize()
+
+        def refold(i):
+            sets[i]["refold"].launch()
+
+        def composed(i):
+            sets[i]["fold"].launch(1)
+            sets[i]["comp"].compress()
+
+        with step(f"check, {label}", 180):
+            s = sets[0]
+            for _ in range(2):                   # twice: the residual carries
+                refold(0)
+                composed(0)
+            torch.cuda.synchronize()
+            checks[label] = {
+                "payload_bytes_equal": all(bool(torch.equal(a, b)) for a, b in
+                                           zip(pcut(s["out"]), pcut(s["outc"]))),
+                "residual_bytes_equal": bool(torch.equal(s["r"].view(torch.int32),
+                                                         s["rc"].view(torch.int32)))}
+        res = timed_rounds(torch, {"refold": (refold, args.inner),
+                                   "composed": (composed, args.inner)}, len(sets), args)
+        # bytes an element the designs move, from the definition: the first pass
+        # reads N payloads and r and writes c, REFINE 1, REFINE 2, COUNT and
+        # COMPACT read c once each, COMPACT writes one payload and the k changed
+        # residual vectors (16 bytes each at these ratios); the pair also writes
+        # and reads the f32 sum
+        sparse = (8 * NSRC + 24) * ktot / nelem
+        for name, per in (("refold", 24 + sparse), ("composed", 32 + sparse)):
+            res[name]["bytes_per_elem"] = round(per, 4)
+            res[name]["roofline_frac"] = round(per * nelem / (res[name]["ms"] * 1e-3)
+                                               / HBM_BYTES_PER_S, 4)
+        res["ratio_refold_over_composed"] = round(res["refold"]["ms"] / res["composed"]["ms"], 4)
+        sp = max(res["refold"]["spread_ms"], res["composed"]["spread_ms"])
+        gates[f"{label}_refold_beats_composed"] = res["composed"]["ms"] - res["refold"]["ms"] > sp
+        for s in sets:
+            for name in ("refold", "fold", "comp"):
+                s[name].close()
+        return {"ratio": ratio, "segments": len(seg_rows), "elems": nelem, "entries": ktot,
+                "results": res}
+
+    with step("init", 60):
+        red = GpuReducer(device=0)
+    total_bytes, rows = read_table(args.table)
+    out["table"] = os.path.basename(args.table)
+    for ratio in (0.01, 0.001):
+        out[f"iteration_{ratio}"] = shape(f"table_{ratio}", ratio,
+                                          [(o // 2, ln // 2) for o, ln in rows], total_bytes // 2)
+        torch.cuda.empty_cache()
+        out[f"big_{ratio}"] = shape(f"big_{ratio}", ratio, [(0, args.elems)], args.elems)
+        torch.cuda.empty_cache()
+    out.update({"checks": checks, "gates": gates})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    # the bytes must agree; the ratio is a recorded fact (DESIGN.md §11.18)
     return 0 if all(v for c in checks.values() for v in c.values()) else 1
 
 
